@@ -6,12 +6,22 @@ process per GPU, weak scaling (per-GPU batch fixed), synthetic NCTHW clips resid
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0): clips/s over the whole job, plus
+Prints ONE JSON line (rank 0): clips/s over the whole job and ms_per_step of the K timed steps.
+A plain run does only that: set up, warm up, time the K steps (and write the outputs, --dump-outputs).
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files: loss, logits, and the flat
+parameters and gradient after that step (a fixed, seeded sample of each when it exceeds 16 MB).  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+--full adds the measurements that take runs of their own:
+  value_exact_fp32 / value_two_term_backward -- the same job with the exact fp32-MFMA / two-term backward GEMMs
   roofline     -- the dominant kernel family (by device time in one instrumented step):
                   algorithmic bytes (in+out elements of each conv pass) over
                   its HIP-event-measured duration, vs the 8 TB/s HBM peak
   cpu_baseline -- the CPU oracle (stock-PyTorch restatement of the reference) timed on the
                   host cores on the stated workload (B=8 steps, bounded to ~1 minute), rank 0, N=1 only.
+  allreduce_ms_per_bucket_standalone -- multi-rank: one gradient bucket's all-reduce on its own
+(--no-exact-fp32, --no-kernel-timing, --no-cpu-baseline drop single parts of --full.)
 """
 import argparse
 import json
@@ -246,6 +256,24 @@ def cpu_baseline(T, H, B=8, sample_B=2):
                       "rounds reported, 3 steps at %d threads" % (B, T, H, B, avail, min(8, avail), sample_B, avail)}
 
 
+DUMP_ARRAY_BYTES = 16 << 20     # per array; four arrays stay well under 64 MB
+
+
+def dump_outputs(d, arrays):
+    """Write each tensor as d/<name>.npy in float32.  An array larger than DUMP_ARRAY_BYTES is written as a fixed sample:
+    the elements at sorted indices drawn without replacement from a generator seeded with 0 (the same for every run of the
+    same shape)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        cap = DUMP_ARRAY_BYTES // 4
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,8 +294,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-exact-fp32", action="store_true", help="skip the second timed run with the exact fp32-MFMA backward GEMMs")
-    ap.add_argument("--dump-launches", default=None, help="write the per-launch HIP-event table (JSON) here")
+    ap.add_argument("--dump-launches", default=None, help="write the per-launch HIP-event table (JSON) here (needs --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, logits, parameters, gradient) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: exact-fp32 / two-term backward runs, the "
+                         "instrumented per-kernel step, the CPU baseline, the standalone all-reduce per bucket")
     args = ap.parse_args()
+    if args.dump_launches and not (args.full and not args.no_kernel_timing):
+        ap.error("--dump-launches needs --full (and kernel timing)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -327,7 +362,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss_, _ = tr.step(xs, ys)
+            loss_, logits_ = tr.step(xs, ys)
         barrier()
         dt_ = time.perf_counter() - t0
         if world > 1:
@@ -335,16 +370,19 @@ def main():
             tdt = torch.tensor([dt_], device=dev, dtype=torch.float64)
             dist.all_reduce(tdt, op=dist.ReduceOp.MAX)
             dt_ = tdt.item()
+        timed_run.logits = logits_
         return dt_, loss_
 
     dt, loss = timed_run()
     ms = 1000.0 * dt / args.steps
     value = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": timed_run.logits, "params": tr.fp.flat, "grad": tr.fp.grad})
 
     # the same step with the exact fp32-MFMA backward GEMMs (the switches are read per launch): reported beside the default
     exact = two_term = None
     from x3dhip import _lib, engine
-    if not args.no_exact_fp32 and not mixed:          # the exact fp32-MFMA backward kernels read fp32 tensors only
+    if args.full and not args.no_exact_fp32 and not mixed:  # the exact fp32-MFMA backward kernels read fp32 tensors only
         with _lib.options(dgrad_f32=1, wgrad_f32=1):  # library options are read per launch; the captured graphs are re-captured
             tr.invalidate_graphs()
             dt_e, _ = timed_run()
@@ -398,7 +436,7 @@ def main():
             "graph_mode": ("two graphs around bucket 0 (overlap)" if (world > 1 and tr.use_graph and tr._overlap())
                            else "single graph" if tr.use_graph else "eager"),
             "buckets_bytes": [4 * (b_ - a_) for a_, b_ in tr.reducer.buckets]}
-    if world > 1:
+    if args.full and world > 1:
         import torch.distributed as dist
         per = []
         for (a_, b_) in tr.reducer.buckets:
@@ -422,7 +460,8 @@ def main():
         out["ms_per_step_exact_fp32"] = round(exact[1], 3)
         out["value_two_term_backward"] = round(two_term[0], 2)
         out["ms_per_step_two_term_backward"] = round(two_term[1], 3)
-    if not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if kernel_timing:
         # one instrumented eager step: HIP events around every launch, same tensors.  EVERY rank runs these steps (they
         # contain the gradient all-reduce: the collectives must match across ranks); only rank 0 records and reports.
         tr_e = tr
@@ -434,7 +473,7 @@ def main():
         if rank != 0:
             tr_e.step(x, y)
             torch.cuda.synchronize()
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and kernel_timing:
         # The eager step is host-bound (a ctypes launch costs more than most of these kernels run): with an empty queue
         # an event pair would measure the host's time between the two records.  ~60 ms of unrelated GEMM work is queued
         # first, so the whole instrumented step is enqueued behind it and the events see back-to-back device execution.
@@ -498,7 +537,7 @@ def main():
                                   for k, v in sorted(kt.by_kernel.items(), key=lambda kv: -kv[1][0])[:12]}
         out["kernel_breakdown_ms"] = {k: [round(v[0], 3), v[2], round(v[1] / (v[0] * 1e-3) / 1e9, 1) if v[0] > 0 else 0]
                                       for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "M":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "M":
         out["cpu_baseline"] = cpu_baseline(T, H, B)
     if world > 1:
         import torch.distributed as dist

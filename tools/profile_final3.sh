@@ -3,7 +3,7 @@
 set -x
 TAG=${1:-d}
 R=$(pwd); OUT=$R/gpurun_out/r3/prof; mkdir -p $OUT
-python3 bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+python3 bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 echo "bench done"
 bash tools/profile_round3.sh $TAG
 python tools/multigrid_sweep.py 8 > $OUT/${TAG}_multigrid_shapes.txt 2>&1

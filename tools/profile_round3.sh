@@ -6,7 +6,7 @@ TAG=${1:-a}
 R=$(pwd)
 OUT=$R/gpurun_out/r3/prof
 mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/kt -- python3 $R/bench.py --no-cpu-baseline --no-exact-fp32 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/kt.err
+rocprofv3 --kernel-trace --stats -d $OUT/kt -- python3 $R/bench.py --full --no-cpu-baseline --no-exact-fp32 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/kt.err
 echo "kernel trace done"
 B="python3 $R/bench.py --no-graph --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-exact-fp32"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -- $B > $OUT/pmc_f.log 2>&1

@@ -1,5 +1,6 @@
-mkdir -p gpurun_out/r4/prof
+OUT=${1:?usage: bash tools/run_bench.sh OUTDIR}
+mkdir -p $OUT
 S=$(date +%s)
-python3 bench.py > gpurun_out/r4/prof/p3_bench_default.json 2> gpurun_out/r4/prof/p3_bench_default.err
+python3 bench.py --full > $OUT/p3_bench_default.json 2> $OUT/p3_bench_default.err
 echo "bench wall seconds: $(( $(date +%s) - S ))"
-tail -c 700 gpurun_out/r4/prof/p3_bench_default.json
+tail -c 700 $OUT/p3_bench_default.json
