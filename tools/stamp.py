@@ -29,3 +29,16 @@ def commit():
 
 def meta():
     return {"csrc_sha16": csrc_sha16(), "commit": commit()}
+
+
+def csrc_eval_sha16():
+    """The same identity for the evaluation library (libx3deval.so): sha256 over csrc_eval/ (every file, by name) and
+    include/x3deval.h, first 16 hex digits.  Kept apart from csrc_sha16, which the gradient-hash record is keyed on."""
+    h = hashlib.sha256()
+    d = os.path.join(ROOT, "x3d-multigrid_amd", "csrc_eval")
+    files = sorted(f for f in glob.glob(os.path.join(d, "*")) if os.path.isfile(f) and not f.endswith(".o")) + \
+        [os.path.join(ROOT, "include", "x3deval.h")]
+    for f in files:
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, "rb").read())
+    return h.hexdigest()[:16]
