@@ -709,7 +709,10 @@ def test_elementwise_se_bwd_merged_sample_kernel_equals_the_two_launches(case):
         assert _rel(o1[k], o0[k]) < 5e-6, k
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 4, 16, 16), (1, 3, 3, 15, 11), (1, 3, 2, 64, 64), (2, 3, 4, 158, 158)])
+@pytest.mark.parametrize("shape", [(2, 3, 4, 16, 16), (1, 3, 3, 15, 11), (1, 3, 2, 64, 64), (2, 3, 4, 158, 158),
+                                   # the headline clip length T = 16, and the 5-tap temporal kernel with T below, at and above
+                                   # its width
+                                   (1, 3, 16, 32, 32), (3, 3, 13, 20, 20), (9, 3, 1, 16, 16), (2, 3, 5, 17, 23)])
 def test_stem(shape):
     from x3dhip import ops
     dev = _dev()
@@ -742,37 +745,46 @@ def test_stem(shape):
 
 
 def test_elementwise_and_sgd():
+    """The three original shapes; since the fp64 tests of csrc/bn.hip (below) every bound here is ALSO held to their rule:
+    inputs are fp32 values, elementwise outputs to k 2^-24 sum |terms|, tile sums to 32 * 2^-24 sum |terms| per tile."""
     from x3dhip import ops
     dev = _dev()
     for (N, C, P) in [(2, 5, 4 * 7 * 7), (1, 3, 3 * 5 * 5), (2, 4, 5000)]:
-        a3 = _g(N, C, P, 1, 1, seed=1)
-        res = _g(N, C, P, 1, 1, seed=2)
-        c3 = torch.stack([1 + 0.2 * _g(N, C, seed=3), 0.3 * _g(N, C, seed=4)], -1)
-        cd = torch.stack([1 + 0.2 * _g(N, C, seed=5), 0.3 * _g(N, C, seed=6)], -1)
+        a3 = _f32(_g(N, C, P, 1, 1, seed=1))
+        res = _f32(_g(N, C, P, 1, 1, seed=2))
+        c3 = _f32(torch.stack([1 + 0.2 * _g(N, C, seed=3), 0.3 * _g(N, C, seed=4)], -1))
+        cd = _f32(torch.stack([1 + 0.2 * _g(N, C, seed=5), 0.3 * _g(N, C, seed=6)], -1))
         to = lambda t: None if t is None else t.float().contiguous().to(dev)
         bc = lambda c, k: c[..., k, None, None, None]
         for use_cd in (False, True):
             ref = torch.relu(bc(c3, 0) * a3 + bc(c3, 1) + ((bc(cd, 0) * res + bc(cd, 1)) if use_cd else res))
             out = ops.bn_add_relu_fwd(to(a3), to(c3), to(res), to(cd) if use_cd else None)
             assert _rel(out, ref) < 1e-6
-            dout = _g(N, C, P, 1, 1, seed=7)
+            r2, terms = bn_ref.bn_add_relu_fwd(a3, c3, res, cd if use_cd else None, with_terms=True)
+            _check_terms(out, r2, terms, K_ADD_RELU, "bn_add_relu_fwd")
+            dout = _f32(_g(N, C, P, 1, 1, seed=7))
             g_ref = dout * (ref > 0)
             g, p1, p2 = ops.bn_add_relu_bwd(to(dout), out, to(a3), to(res) if use_cd else None)
             assert _rel(g, g_ref) < 1e-6
             st = p1.double().sum(2).cpu()
             assert _rel(st[..., 0], g_ref.sum(dim=(2, 3, 4))) < 1e-4
             assert _rel(st[..., 1], (g_ref * a3).sum(dim=(2, 3, 4))) < 1e-4
+            g2, part, part_d, mag, mag_d = bn_ref.bn_add_relu_bwd(dout, out.cpu().double(), a3, res if use_cd else None)
+            assert torch.equal(g.cpu().double(), g2)
+            _check_tile_sums(p1, part, mag, "bn_add_relu_bwd partial")
             if use_cd:
                 st2 = p2.double().sum(2).cpu()
                 assert _rel(st2[..., 1], (g_ref * res).sum(dim=(2, 3, 4))) < 1e-4
+                _check_tile_sums(p2, part_d, mag_d, "bn_add_relu_bwd partial_d")
         pooled = ops.bn_relu_pool_fwd(to(a3), to(c3))
         pref = torch.relu(bc(c3, 0) * a3 + bc(c3, 1)).mean(dim=(2, 3, 4))
         assert _rel(pooled, pref) < 1e-5
-        dp = _g(N, C, seed=8)
+        dp = _f32(_g(N, C, seed=8))
         gp, pp = ops.bn_relu_pool_bwd(to(a3), to(c3), to(dp))
         gref = dp[..., None, None, None] / P * ((bc(c3, 0) * a3 + bc(c3, 1)) > 0)
         assert _rel(gp, gref) < 1e-6
         assert _rel(pp.double().sum(2).cpu()[..., 1], (gref * a3).sum(dim=(2, 3, 4))) < 1e-4
+        _pool_checks(ops, dev, a3, c3, dp.view(N, C, 1), 1, "random", "pool %s" % ((N, C, P),))
     # fused SGD vs torch.optim.SGD semantics
     w = _g(1000, seed=1).float()
     gr = _g(1000, seed=2).float()
@@ -902,3 +914,630 @@ def test_head_kernels(R, K, J, C):
             assert int(rng[1]) == 1                                        # head_ce advanced the draw counter
             hd2, _ = ops.head_fwd(to(pooled), to(w1), to(w2), to(b2), p, rng)
             assert float(((hd2 != 0) != (hd != 0)).float().mean()) > 0.2   # a fresh mask
+
+
+# ======================================================================================================================
+# csrc/bn.hip against tests/bn_ref.py (plain fp64 restatements, proved against torch autograd by tests/test_bn_ref_host.py).
+#
+# Tolerances (none is taken from what the kernels produce):
+#   * outputs a kernel computes in fp64 from its inputs and rounds once (save, coef, cb, nsum, running statistics, dgamma,
+#     dbeta, bn_eval_coef, reduce_partials): |got - ref| <= 2^-23 |ref| + 2^-23 scale -- one fp32 rounding with a factor 2
+#     for the order of the fp64 sums; scale = the largest-magnitude term of the output's expression (bn_ref, with_scale);
+#   * elementwise kernels: |got - ref| <= k 2^-24 sum |terms|, k = fp32 roundings of the kernel's expression + 1;
+#   * fp32 tile sums: <= 32 * 2^-24 * sum |terms| per tile (at most 8 sequential additions per thread and an 8-level tree);
+#   * SE arithmetic the kernels do in fp32 and the real-tensor chains: 4 x the fp32 floor of THE REFERENCE (the same
+#     function in plain torch fp32 on the CPU against its fp64 evaluation, relative L2, per case and output), never below
+#     the 2e-6 of test_elementwise_se_bn_fwd_equals_finalize_then_se.
+#
+# Entry point -> test whose other side is bn_ref / torch fp64:
+#   x3d_bn_fwd_finalize        test_reduce_bn_fwd_finalize_against_fp64, ..._subbatchnorm_chain_...
+#   x3d_bn_bwd_finalize        test_reduce_bn_bwd_finalize_against_fp64, ..._subbatchnorm_chain_...
+#   x3d_bn_eval_coef           test_elementwise_subbatchnorm_chain_against_fp64_autograd
+#   x3d_bn_stats_add_relu_fwd  test_elementwise_bn_stats_add_relu_fwd_against_fp64, test_elementwise_kernels_against_fp64
+#   x3d_se_fwd, x3d_se_bn_fwd  test_elementwise_se_fwd_against_fp64, test_elementwise_bn_se_chain_against_fp64_autograd
+#   x3d_se_bn_bwd_finalize     test_elementwise_se_bwd_against_fp64, test_elementwise_bn_se_chain_against_fp64_autograd
+#   x3d_bn_add_relu_fwd / bwd, x3d_bn_rowstats, x3d_bn_affine      test_elementwise_kernels_against_fp64
+#   x3d_bn_relu_pool_fwd / bwd test_elementwise_kernels_against_fp64 (segs 1), test_elementwise_pool_per_frame_against_fp64
+#   x3d_grad_accumulate, x3d_sgd_fused                             test_elementwise_grad_accumulate_and_sgd_against_fp64
+#   x3d_reduce_partials        test_reduce_partials_against_fp64
+# ======================================================================================================================
+from tests import bn_ref
+
+U23, U24 = 2.0 ** -23, 2.0 ** -24
+SUM_K = 32            # fp32 tile sums: 8 sequential additions per thread + 8 tree levels = 16 roundings, factor 2
+
+
+def _f32(t):
+    """fp64 values that ARE fp32 values (what the kernel receives, widened)."""
+    return t.float().double()
+
+
+def _to(t, dev):
+    return None if t is None else t.float().contiguous().to(dev)
+
+
+def _check_rounded_once(got, ref, scale, what):
+    got = got.detach().double().cpu().reshape(ref.shape)
+    assert bool(torch.isfinite(got).all()), what + ": not finite"
+    err, bound = (got - ref).abs(), U23 * ref.abs() + U23 * scale
+    assert bool((err <= bound).all()), "%s: error %.3g x bound (max |err| %.3g)" % (
+        what, (err / bound.clamp_min(1e-300)).max().item(), err.max().item())
+
+
+def _check_terms(got, ref, terms, k, what):
+    got = got.detach().double().cpu().reshape(ref.shape)
+    assert bool(torch.isfinite(got).all()), what + ": not finite"
+    err, bound = (got - ref).abs(), k * U24 * terms.reshape(ref.shape)
+    assert bool((err <= bound).all()), "%s: error %.3g x bound (max |err| %.3g)" % (
+        what, (err / bound.clamp_min(1e-300)).max().item(), err.max().item())
+
+
+def _check_floor(got, ref64, ref32, what, report):
+    """4 x the fp32 floor of the reference, not below 2e-6; relative L2."""
+    floor = _rel(ref32, ref64)
+    bound = max(4 * floor, 2e-6)
+    err = _rel(got, ref64)
+    report.append("%s floor %.2e bound %.2e err %.2e" % (what, floor, bound, err))
+    assert err <= bound, report[-1]
+
+
+def _bn_raw(N, C, P, seed, hard=True):
+    """A conv-like output: per-channel mean of the order of the standard deviation; with `hard` (the kernels that finalize
+    in fp64) channel 0 (C >= 3) is badly conditioned (mean 50, standard deviation 0.01) and channel 1 constant (variance
+    clamp -> invstd = 1 / sqrt(eps)).  The SE tests leave these two out: their bound is the fp32 floor of the reference,
+    which such channels would raise to 1e-2 and more."""
+    raw = _g(N, C, P, seed=seed) * (0.5 + _g(C, seed=seed + 1).abs()).view(1, C, 1) + _g(C, seed=seed + 2).view(1, C, 1)
+    if C >= 3 and hard:
+        raw[:, 0] = 50 + 0.01 * _g(N, P, seed=seed + 3)
+        raw[:, 1] = 1.625
+    return _f32(raw)
+
+
+# (N, C, tiles, S), shared by x3d_bn_fwd_finalize, x3d_bn_bwd_finalize and x3d_bn_stats_add_relu_fwd
+FIN_CASES = [
+    # the model's rows: depthwise partials (1-4 tiles), stages 3-4 (7 / 13 / 25 / 98), stages 1-2 (392 / 784 / 1568)
+    (8, 54, 1, 1), (8, 108, 2, 2), (8, 216, 3, 1), (8, 432, 4, 4), (8, 432, 7, 8), (16, 432, 13, 2), (8, 432, 25, 2),
+    (8, 216, 98, 1), (8, 24, 392, 1), (8, 54, 784, 2), (4, 24, 1568, 1), (2, 54, 1568, 2),
+    # edges of the row reduction (group width G = 64 from 33 tiles on; four-load loop from 4 G tiles on)
+    (2, 3, 63, 1), (3, 5, 64, 3), (2, 3, 65, 2), (5, 3, 191, 1), (2, 3, 192, 1), (2, 3, 193, 2), (3, 2, 255, 1),
+    (2, 2, 256, 1), (2, 2, 257, 1), (1, 3, 449, 1),
+    # N not a multiple of 4 * 64 / G (several samples per wave), every split count
+    (1, 7, 1, 1), (2, 7, 2, 1), (3, 7, 3, 3), (5, 7, 5, 5), (17, 5, 2, 1), (17, 5, 9, 17), (64, 6, 1, 8), (65, 6, 3, 5),
+    (65, 4, 17, 13), (128, 24, 4, 16), (128, 6, 33, 32), (64, 5, 2, 64), (128, 3, 1, 64), (128, 5, 6, 128), (64, 3, 5, 4),
+    (256, 8, 4, 32),                                      # the large-batch case
+    (4, 3, 1, 4),                                         # P = 1: count * N / S == 1 (the cnt > 1 guard)
+    # the two-launch fallback (N > 1024 or S > 256): reduce_tiles_kernel + bn_fwd / bwd_finalize_kernel.  The library does
+    # not report which finalize kernel ran (x3d_note_kernel is not called by these entry points); the path follows from
+    # BN_MAXN = 1024 / BN_MAXS = 256 in the source
+    (1026, 3, 2, 2), (512, 3, 2, 512), (1028, 5, 70, 4),
+]
+
+
+def _fin_P(i, N, C, tiles):
+    """Voxels per row of case i: any P >= tiles (partials_of cuts unevenly); rows of several 2048-element tiles with
+    P % 4 == 0 and != 0 where the tensor stays small, P = tiles (one voxel per tile) on every fourth case."""
+    if (N, C, tiles) == (4, 3, 1):
+        return 1
+    big = max(tiles, (4100, 2051, 4096, 6150)[i % 4])
+    return big if N * C * big <= (1 << 21) else (2 * tiles + 3, tiles + 5, 4 * tiles, tiles)[i % 4]
+
+
+def _fin_inputs(i, case, seed=0):
+    N, C, tiles, S = case
+    P = _fin_P(i, N, C, tiles)
+    raw = _bn_raw(N, C, P, seed=50 + seed)
+    part = bn_ref.partials_of(raw, tiles, seed=i)
+    gamma, beta = _f32(1 + 0.2 * _g(C, seed=51)), _f32(0.3 * _g(C, seed=52))
+    rm0, rv0 = _f32(0.1 * _g(S, C, seed=53)), _f32(1 + 0.1 * _g(S, C, seed=54).abs())
+    return P, raw, part, gamma, beta, rm0, rv0
+
+
+_FIN_IDS = ["%dx%dx%d_s%d" % c for c in FIN_CASES]
+
+
+@pytest.mark.parametrize("i", range(len(FIN_CASES)), ids=_FIN_IDS)
+def test_reduce_bn_fwd_finalize_against_fp64(i):
+    """x3d_bn_fwd_finalize (fused kernel and the two-launch fallback) against bn_ref.bn_fwd_finalize on the same statistics
+    tiles (cut from a real tensor): coef, save, nsum and the running statistics (momentum 0.1 and 0.25, unbiased variance),
+    each to one fp32 rounding; running_mean = None leaves the other outputs bitwise the same."""
+    from x3dhip import ops
+    dev = _dev()
+    case = FIN_CASES[i]
+    N, C, tiles, S = case
+    P, raw, part, gamma, beta, rm0, rv0 = _fin_inputs(i, case)
+    pd, gd, bd = _to(part, dev), _to(gamma, dev), _to(beta, dev)
+    for momentum in (0.1, 0.25):
+        ref, scale = bn_ref.bn_fwd_finalize(part, S, P, gamma, beta, rm0, rv0, momentum, 1e-5, with_scale=True)
+        rm, rv = _to(rm0, dev), _to(rv0, dev)
+        coef, save, nsum = ops.bn_fwd_finalize(pd, S, P, gd, bd, rm, rv, momentum, 1e-5, want_nsum=True)
+        for name, got, r, s in zip(("coef", "save", "nsum", "running_mean", "running_var"), (coef, save, nsum, rm, rv), ref, scale):
+            _check_rounded_once(got, r, s, "%s %s m=%.2f" % (case, name, momentum))
+    if C >= 3:                                                               # the clamp: var = 0 -> invstd = 1 / sqrt(eps)
+        assert _rel(save[1, :, 1], torch.full((S,), float(np.float32(1e-5)) ** -0.5, dtype=torch.float64)) < 1e-6
+    coef2, save2, nsum2 = ops.bn_fwd_finalize(pd, S, P, gd, bd, None, None, 0.25, 1e-5, want_nsum=False)
+    assert nsum2 is None and torch.equal(coef2, coef) and torch.equal(save2, save)
+
+
+@pytest.mark.parametrize("i", range(len(FIN_CASES)), ids=_FIN_IDS)
+def test_reduce_bn_bwd_finalize_against_fp64(i):
+    """x3d_bn_bwd_finalize against bn_ref.bn_bwd_finalize on the same tiles {sum g, sum g raw} of real tensors and the same
+    saved statistics: cb = {A, B, C}, dgamma, dbeta with accumulate 0 and 1, each to one fp32 rounding."""
+    from x3dhip import ops
+    dev = _dev()
+    case = FIN_CASES[i]
+    N, C, tiles, S = case
+    P, raw, part, gamma, beta, _, _ = _fin_inputs(i, case)
+    save = _f32(bn_ref.bn_fwd_finalize(part, S, P, gamma, beta)[1])
+    g = _f32(_g(N, C, P, seed=60))
+    bpart = bn_ref.partials_of(g, tiles, raw, seed=i + 7)
+    pd, gd, sd = _to(bpart, dev), _to(gamma, dev), _to(save, dev)
+    ref, scale = bn_ref.bn_bwd_finalize(bpart, S, P, gamma, save, with_scale=True)
+    cb, dg, db = ops.bn_bwd_finalize(pd, S, P, gd, sd)
+    for name, got, r, s in zip(("cb", "dgamma", "dbeta"), (cb, dg, db), ref, scale):
+        _check_rounded_once(got, r, s, "%s %s" % (case, name))
+    dg0, db0 = _f32(_g(C, seed=61) * 3), _f32(_g(C, seed=62) * 3)
+    ref, scale = bn_ref.bn_bwd_finalize(bpart, S, P, gamma, save, dgamma0=dg0, dbeta0=db0, with_scale=True)
+    dg, db = _to(dg0, dev), _to(db0, dev)
+    cb, dg, db = ops.bn_bwd_finalize(pd, S, P, gd, sd, dgamma=dg, dbeta=db, accumulate=True)
+    for name, got, r, s in zip(("cb", "dgamma", "dbeta"), (cb, dg, db), ref, scale):
+        _check_rounded_once(got, r, s, "%s %s accumulate" % (case, name))
+
+
+# bn_stats_add_relu_fwd: scale and shift (each within the finalize rule: 2 units of 2^-24 relative to |sc|, to the larger
+# term of sh), two fma and an add: k = 2 + 2 + 3 + 1
+STATS_K = 8
+
+
+@pytest.mark.parametrize("i", range(len(FIN_CASES)), ids=_FIN_IDS)
+def test_elementwise_bn_stats_add_relu_fwd_against_fp64(i):
+    """x3d_bn_stats_add_relu_fwd (the training form every block ends with: BN3's finalize recomputed by every workgroup)
+    against bn_ref.bn_fwd_finalize + bn_ref.bn_add_relu_fwd: out, save and the running statistics, with and without cd."""
+    from x3dhip import ops
+    dev = _dev()
+    case = FIN_CASES[i]
+    N, C, tiles, S = case
+    P, raw, part, gamma, beta, rm0, rv0 = _fin_inputs(i, case)
+    momentum = (0.1, 0.25)[i % 2]
+    res = _f32(_g(N, C, P, seed=70))
+    cd = _f32(torch.stack([1 + 0.2 * _g(N, C, seed=71), 0.3 * _g(N, C, seed=72)], -1))
+    ref, scale = bn_ref.bn_fwd_finalize(part, S, P, gamma, beta, rm0, rv0, momentum, 1e-5, with_scale=True)
+    a3d, pd, rd = _to(raw.view(N, C, P, 1, 1), dev), _to(part, dev), _to(res.view(N, C, P, 1, 1), dev)
+    for q in (None, cd):
+        rm, rv = _to(rm0, dev), _to(rv0, dev)
+        out, save = ops.bn_stats_add_relu_fwd(a3d, pd, S, P, _to(gamma, dev), _to(beta, dev), rm, rv, rd, _to(q, dev),
+                                              momentum=momentum, eps=1e-5)
+        _check_rounded_once(save, ref[1], scale[1], "%s save" % (case,))
+        _check_rounded_once(rm, ref[3], scale[3], "%s running_mean" % (case,))
+        _check_rounded_once(rv, ref[4], scale[4], "%s running_var" % (case,))
+        o_ref, terms = bn_ref.bn_add_relu_fwd(raw, ref[0], res, q, with_terms=True)
+        # |shift| may be a small difference of large terms: its rounding is relative to the larger one
+        terms = terms + (scale[0][..., 1] - ref[0][..., 1].abs()).view(N, C, 1)
+        _check_terms(out, o_ref, terms, STATS_K, "%s out cd=%s" % (case, q is not None))
+    if i % 5 == 0:                                                           # running_mean = None: same out / save
+        out2, save2 = ops.bn_stats_add_relu_fwd(a3d, pd, S, P, _to(gamma, dev), _to(beta, dev), None, None, rd, _to(cd, dev),
+                                                momentum=momentum, eps=1e-5)
+        assert torch.equal(out2, out) and torch.equal(save2, save)
+
+
+# (N, C, Wd, tiles, S): every S in 1, 2, 3, 4, 5, 6, 8, 16, 64 (both se_tail_kernel branches; S = 64: empty split butterfly);
+# N in 1, 3, 63, 64, 65, 128, 130 (two samples per lane of the wave form, ragged last batch of eight in se_wgrad_element);
+# Wd in 7, 8, 16, 20, 32, 40, 64; the merge threshold cdiv(tiles, tpr) <= 32 from both sides
+SE_REF_CASES = SE_BN_CASES + SE_BWD_CASES + [
+    (1, 54, 8, 2, 1), (3, 54, 8, 2, 3), (63, 54, 8, 2, 3), (64, 54, 8, 1, 64), (65, 70, 7, 3, 5), (128, 108, 8, 2, 16),
+    (130, 54, 8, 2, 2), (12, 54, 8, 2, 6), (64, 216, 16, 2, 4), (128, 54, 8, 3, 64), (130, 70, 7, 2, 5), (10, 108, 16, 9, 5),
+    (4, 306, 20, 3, 2), (4, 432, 32, 2, 4), (2, 630, 40, 3, 2), (3, 1024, 64, 2, 1), (8, 48, 4, 3, 8),
+    (2, 1024, 64, 32, 1), (2, 1024, 64, 33, 1), (2, 432, 32, 64, 1), (2, 432, 32, 65, 2), (2, 216, 16, 128, 1),
+    (2, 216, 16, 129, 1), (2, 54, 8, 512, 1), (2, 54, 8, 513, 2)]
+
+
+def _se_inputs(i, case):
+    N, C, Wd, tiles, S = case
+    P = (2 * tiles + 3, tiles + 6, 4 * tiles)[i % 3]
+    raw = _bn_raw(N, C, P, seed=80, hard=False)
+    part = bn_ref.partials_of(raw, tiles, seed=i)
+    gamma, beta = _f32(1 + 0.2 * _g(C, seed=81)), _f32(0.3 * _g(C, seed=82))
+    w1, b1 = _f32(_g(Wd, C, seed=83) / C ** 0.5), _f32(0.1 * _g(Wd, seed=84))
+    w2, b2 = _f32(_g(C, Wd, seed=85) / Wd ** 0.5), _f32(0.1 * _g(C, seed=86))
+    rm0, rv0 = _f32(0.1 * _g(S, C, seed=87)), _f32(1 + 0.1 * _g(S, C, seed=88).abs())
+    return P, raw, part, gamma, beta, w1, b1, w2, b2, rm0, rv0
+
+
+_SE_IDS = ["%dx%dx%dx%d_s%d" % c for c in SE_REF_CASES]
+
+
+@pytest.mark.parametrize("i", range(len(SE_REF_CASES)), ids=_SE_IDS)
+def test_elementwise_se_fwd_against_fp64(i):
+    """x3d_se_bn_fwd, and x3d_bn_fwd_finalize + x3d_se_fwd, against bn_ref on the same inputs.  save / nsum / running
+    statistics (fp64 inside): one fp32 rounding.  pool, z, se, coef_out (fp32 arithmetic, hardware exp / rcp): 4 x the fp32
+    floor of the reference, >= 2e-6.  Floors measured on the CPU over these cases (relative L2 of the fp32
+    evaluation against the fp64 one; for se_bn_fwd the fp32 evaluation includes the statistics):
+        se_bn_fwd   pool 1.5e-7 .. 3.5e-7   z 1.8e-7 .. 4.6e-6   se 4.4e-8 .. 7.9e-8   coef_out 1.4e-7 .. 1.2e-6
+        se_fwd      pool 5.1e-8 .. 1.8e-7   z 8.9e-8 .. 1.2e-6   se 3.8e-8 .. 6.8e-8   coef_out 4.2e-8 .. 7.3e-8
+    so the bound is the 2e-6 minimum except for z at Wd = 4 .. 8 with few samples (up to 1.8e-5 at (8, 48, 4, 3, 8)) and
+    coef_out of se_bn_fwd at one sample per split (up to 4.6e-6).  Every figure is printed per case."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    case = SE_REF_CASES[i]
+    N, C, Wd, tiles, S = case
+    P, raw, part, gamma, beta, w1, b1, w2, b2, rm0, rv0 = _se_inputs(i, case)
+    args = [_to(t, dev) for t in (gamma, beta)]
+    wts = [_to(t, dev) for t in (w1, b1, w2, b2)]
+    pd = _to(part, dev)
+    ref, scale = bn_ref.se_bn_fwd(part, S, P, gamma, beta, rm0, rv0, w1, b1, w2, b2, 0.1, 1e-5, with_scale=True)
+    r32 = bn_ref.se_bn_fwd(part, S, P, gamma, beta, rm0, rv0, w1, b1, w2, b2, 0.1, 1e-5, dt=torch.float32)
+    report = []
+    # one launch
+    rm, rv = _to(rm0, dev), _to(rv0, dev)
+    ce, save, nsum, se, z, pool = ops.se_bn_fwd(pd, S, P, args[0], args[1], rm, rv, *wts, 0.1, 1e-5)
+    assert _lib.last_kernel() == "se_bn_fwd_kernel"
+    for name, got, r, s in (("save", save, ref[1], scale[1]), ("nsum", nsum, ref[2], scale[2]),
+                            ("running_mean", rm, ref[6], scale[3]), ("running_var", rv, ref[7], scale[4])):
+        _check_rounded_once(got, r, s, "%s se_bn_fwd %s" % (case, name))
+    for name, got, k in (("coef_out", ce, 0), ("se", se, 3), ("z", z, 4), ("pool", pool, 5)):
+        _check_floor(got, ref[k], r32[k], "%s se_bn_fwd %s" % (case, name), report)
+    # two launches; se_fwd against the reference ON ITS OWN INPUTS (the kernel's coef and nsum)
+    rm, rv = _to(rm0, dev), _to(rv0, dev)
+    coef, save_a, nsum_a = ops.bn_fwd_finalize(pd, S, P, args[0], args[1], rm, rv, 0.1, 1e-5, want_nsum=True)
+    outs = ops.se_fwd(coef, nsum_a, P, *wts)
+    torch.cuda.synchronize()
+    r64 = bn_ref.se_fwd(coef, nsum_a, P, w1, b1, w2, b2)
+    r32 = bn_ref.se_fwd(coef, nsum_a, P, w1, b1, w2, b2, dt=torch.float32)
+    for name, got, a, b in zip(("coef_out", "se", "z", "pool"), outs, r64, r32):
+        _check_floor(got, a, b, "%s se_fwd %s" % (case, name), report)
+    print("\n" + "\n".join(report))
+
+
+@pytest.mark.parametrize("merge", [1, 0])
+@pytest.mark.parametrize("i", range(len(SE_REF_CASES)), ids=_SE_IDS)
+def test_elementwise_se_bwd_against_fp64(i, merge):
+    """x3d_se_bn_bwd_finalize (merged sample kernel, and option no_se_bwd_merge) against bn_ref.se_bn_bwd_finalize on the
+    same inputs: tiles {sum ds, sum ds raw} of real tensors, and the forward's saved statistics / gate / hidden units / pool
+    from the fp64 reference.  A = k se (fp64 inside): one fp32 rounding.  B, C, dgamma, dbeta and the SE weight gradients go
+    through fp32 dz2 / dz1 / dpool: 4 x the fp32 floor of the reference, >= 2e-6.  Floors measured on the CPU over these
+    cases: cb B 7.8e-8 .. 3.1e-7, cb C 8.4e-8 .. 4.0e-7, dgamma 6.1e-8 .. 2.0e-7, dbeta 6.8e-8 .. 4.0e-7, dw2 7.2e-8 .. 2.6e-7,
+    db2 7.9e-8 .. 2.0e-7, dw1 8.3e-8 .. 1.4e-6, db1 6.6e-8 .. 1.4e-6: the bound is the 2e-6 minimum except for dw1 / db1 at a
+    few narrow cases (up to 5.7e-6 at (8, 48, 4, 3, 8)).  Every figure is printed per case.
+    The library does not report which sample kernel ran (no x3d_note_kernel here); both settings are run at every case, and
+    cdiv(tiles, tpr) <= 32 from both sides is in the table: (1024, 32 / 33), (432, 64 / 65), (216, 128 / 129), (54, 512 / 513)."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    case = SE_REF_CASES[i]
+    N, C, Wd, tiles, S = case
+    P, raw, part, gamma, beta, w1, b1, w2, b2, _, _ = _se_inputs(i, case)
+    fwd = bn_ref.se_bn_fwd(part, S, P, gamma, beta, None, None, w1, b1, w2, b2, 0.1, 1e-5)
+    save, nsum, se, z, pool = [_f32(t) for t in fwd[1:6]]
+    ds = _f32(_g(N, C, P, seed=90) * 0.1)
+    bpart = bn_ref.partials_of(ds, tiles, raw, seed=i + 3)
+    ins = (bpart, S, P, gamma, beta, save, nsum, w1, w2, se, z, pool)
+    cb64, g64 = bn_ref.se_bn_bwd_finalize(*ins)
+    cb32, g32 = bn_ref.se_bn_bwd_finalize(*ins, dt=torch.float32)
+    dins = [t if isinstance(t, int) else _to(t, dev) for t in ins]
+    with _lib.options(no_se_bwd_merge=0 if merge else 1):
+        cb, outs = ops.se_bn_bwd_finalize(*dins)
+    torch.cuda.synchronize()
+    report = []
+    _check_rounded_once(cb[..., 0], cb64[..., 0], cb64[..., 0].abs(), "%s cb A" % (case,))
+    _check_floor(cb[..., 1], cb64[..., 1], cb32[..., 1], "%s cb B" % (case,), report)
+    _check_floor(cb[..., 2], cb64[..., 2], cb32[..., 2], "%s cb C" % (case,), report)
+    for k in ("dgamma", "dbeta", "dw1", "db1", "dw2", "db2"):
+        _check_floor(outs[k], g64[k], g32[k], "%s %s" % (case, k), report)
+    print("\n" + "\n".join(report))
+
+
+def _split_bn_se(raw, S, gamma, beta, eps, se_w=None):
+    """Whole-tensor split BN (x3d.py:47-58, training) and, with se_w = (w1, b1, w2, b2), the SE gate on top
+    (x3d.py:153-159): s = bn(raw) * sigmoid(W2 relu(W1 mean_p(bn(raw)) + b1) + b2).  raw [N, C, P]; any dtype; autograd."""
+    parts = []
+    for j in range(S):
+        x = raw[j::S]
+        mean = x.mean(dim=(0, 2), keepdim=True)
+        var = x.var(dim=(0, 2), unbiased=False, keepdim=True)
+        parts.append((x - mean) / torch.sqrt(var + eps) * gamma.view(1, -1, 1) + beta.view(1, -1, 1))
+    y = torch.stack(parts, 1).reshape(raw.shape)                 # [N / S, S, C, P] -> sample n = k * S + j
+    if se_w is None:
+        return y
+    w1, b1, w2, b2 = se_w
+    return y * torch.sigmoid(torch.relu(y.mean(2) @ w1.t() + b1) @ w2.t() + b2).unsqueeze(-1)
+
+
+def _autograd_eval(fn, leaves, upstream, dt):
+    """fn(*leaves) in dtype dt with autograd: (output, gradients of sum(output * upstream) w.r.t. every leaf)."""
+    ls = [t.to(dt).clone().requires_grad_(True) for t in leaves]
+    out = fn(*ls)
+    (out * upstream.to(dt)).sum().backward()
+    return out.detach(), [t.grad for t in ls]
+
+
+# (N, C, Wd, T, H, W, S): the wave form of se_tail_kernel (64 % S == 0), the thread-per-channel form (S = 3, 5), the
+# large-batch shape N = 128 with 8 splits, and a row of more than one 2048-voxel tile (P = 2116)
+CHAIN_CASES = [(4, 54, 8, 9, 14, 14, 2), (6, 70, 7, 3, 9, 7, 3), (128, 54, 8, 2, 5, 5, 8), (5, 216, 16, 4, 23, 23, 5)]
+
+
+@pytest.mark.parametrize("case", CHAIN_CASES)
+def test_elementwise_bn_se_chain_against_fp64_autograd(case):
+    """One chain from real tensors, kernels only: raw -> bn_rowstats -> se_bn_fwd -> bn_affine = s; ds -> bn_rowstats(raw, ds)
+    -> se_bn_bwd_finalize -> bn_affine(ncoef 3) = d raw, against fp64 AUTOGRAD through split BN + SE on the whole tensor
+    (no closed form on the reference side), and the six parameter gradients likewise.  Bound: 4 x the fp32 floor of the
+    reference (torch fp32 autograd on the CPU against fp64), >= 2e-6.  Floors measured on the CPU at these shapes: s 8.5e-8 ..
+    9.3e-8, d raw 8.0e-8 .. 8.7e-8, dgamma / dbeta and the SE weight gradients 6e-8 .. 4e-7: the bound is 2e-6 throughout."""
+    from x3dhip import ops
+    dev = _dev()
+    N, C, Wd, T, H, W, S = case
+    P = T * H * W
+    raw = _f32(_g(N, C, P, seed=1) * (0.5 + _g(C, seed=2).abs()).view(1, C, 1) + _g(C, seed=3).view(1, C, 1))
+    gamma, beta = _f32(1 + 0.2 * _g(C, seed=4)), _f32(0.3 * _g(C, seed=5))
+    w1, b1 = _f32(_g(Wd, C, seed=6) / C ** 0.5), _f32(0.1 * _g(Wd, seed=7))
+    w2, b2 = _f32(_g(C, Wd, seed=8) / Wd ** 0.5), _f32(0.1 * _g(C, seed=9))
+    ds = _f32(_g(N, C, P, seed=10))
+    eps = float(np.float32(1e-5))
+    fn = lambda r, g, b, a1, c1, a2, c2: _split_bn_se(r, S, g, b, eps, (a1, c1, a2, c2))
+    leaves = (raw, gamma, beta, w1, b1, w2, b2)
+    s64, gr64 = _autograd_eval(fn, leaves, ds, torch.float64)
+    s32, gr32 = _autograd_eval(fn, leaves, ds, torch.float32)
+    rd, dd = _to(raw.view(N, C, T, H, W), dev), _to(ds.view(N, C, T, H, W), dev)
+    gd, bd, w1d, b1d, w2d, b2d = [_to(t, dev) for t in leaves[1:]]
+    part = ops.bn_rowstats(rd)
+    ce, save, nsum, se, z, pool = ops.se_bn_fwd(part, S, P, gd, bd, None, None, w1d, b1d, w2d, b2d, 0.1, 1e-5)
+    s = ops.bn_affine(rd, ce)
+    report = []
+    _check_floor(s.view(N, C, P), s64, s32, "%s s" % (case,), report)
+    cb, outs = ops.se_bn_bwd_finalize(ops.bn_rowstats(rd, dd), S, P, gd, bd, save, nsum, w1d, w2d, se, z, pool)
+    draw = ops.bn_affine(rd, cb, dd)
+    torch.cuda.synchronize()
+    _check_floor(draw.view(N, C, P), gr64[0], gr32[0], "%s d raw" % (case,), report)
+    for k, (name, a, b) in enumerate(zip(("dgamma", "dbeta", "dw1", "db1", "dw2", "db2"), gr64[1:], gr32[1:])):
+        _check_floor(outs[name], a, b, "%s %s" % (case, name), report)
+    print("\n" + "\n".join(report))
+
+
+@pytest.mark.parametrize("shape,S", [((4, 6, 3, 9, 7), 2), ((4, 6, 3, 9, 7), 4), ((2, 5, 4, 24, 24), 1), ((6, 3, 5, 21, 20), 3)])
+def test_elementwise_subbatchnorm_chain_against_fp64_autograd(shape, S):
+    """The stand-alone SubBatchNorm3d path, kernels only: bn_rowstats -> bn_fwd_finalize -> bn_affine (train), bn_eval_coef ->
+    bn_affine (eval), bn_rowstats(x, g) -> bn_bwd_finalize -> bn_affine(ncoef 3), against torch in fp64 on the whole tensor
+    (F.batch_norm per split, autograd).  Bound: 4 x the fp32 floor of the reference, >= 2e-6 (floors on the CPU: y 5.7e-8 ..
+    6.7e-8, d x 5.8e-8 .. 6.6e-8, eval y 4.9e-8 .. 6.5e-8, running statistics 4e-9 .. 5e-8: the bound is 2e-6 throughout); bn_eval_coef (fp64 inside): one fp32 rounding."""
+    from x3dhip import ops
+    dev = _dev()
+    N, C = shape[:2]
+    P = shape[2] * shape[3] * shape[4]
+    x = _f32(_g(N, C, P, seed=1) * (0.5 + _g(C, seed=2).abs()).view(1, C, 1) + _g(C, seed=3).view(1, C, 1))
+    gamma, beta = _f32(1 + 0.2 * _g(C, seed=4)), _f32(0.3 * _g(C, seed=5))
+    g = _f32(_g(N, C, P, seed=6))
+    eps = float(np.float32(1e-5))
+    fn = lambda r, a, b: _split_bn_se(r, S, a, b, eps)
+    y64, gr64 = _autograd_eval(fn, (x, gamma, beta), g, torch.float64)
+    y32, gr32 = _autograd_eval(fn, (x, gamma, beta), g, torch.float32)
+    xd, gd = _to(x.view(shape), dev), _to(g.view(shape), dev)
+    gm, bt = _to(gamma, dev), _to(beta, dev)
+    rm, rv = torch.zeros(S, C, device=dev), torch.ones(S, C, device=dev)
+    coef, save, _ = ops.bn_fwd_finalize(ops.bn_rowstats(xd), S, P, gm, bt, rm, rv, 0.1, 1e-5)
+    report = []
+    _check_floor(ops.bn_affine(xd, coef).view(N, C, P), y64, y32, "%s y" % (shape,), report)
+    cb, dg, db = ops.bn_bwd_finalize(ops.bn_rowstats(xd, gd), S, P, gm, save)
+    _check_floor(ops.bn_affine(xd, cb, gd).view(N, C, P), gr64[0], gr32[0], "%s d x" % (shape,), report)
+    _check_floor(dg, gr64[1], gr32[1], "%s dgamma" % (shape,), report)
+    _check_floor(db, gr64[2], gr32[2], "%s dbeta" % (shape,), report)
+    # running statistics after one step from (0, 1) against F.batch_norm per split, then the eval coefficients from them
+    for j in range(S):
+        a, b = torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64)
+        F.batch_norm(x[j::S], a, b, gamma, beta, training=True, momentum=float(np.float32(0.1)), eps=eps)
+        a32, b32 = torch.zeros(C), torch.ones(C)
+        F.batch_norm(x[j::S].float(), a32, b32, gamma.float(), beta.float(), training=True, momentum=0.1, eps=1e-5)
+        _check_floor(rm[j], a, a32, "%s running_mean[%d]" % (shape, j), report)
+        _check_floor(rv[j], b, b32, "%s running_var[%d]" % (shape, j), report)
+    rmean, rvar = rm.mean(0), rv.mean(0)
+    ce = ops.bn_eval_coef(rmean, rvar, gm, bt, N, 1e-5)
+    ce_ref, ce_scale = bn_ref.bn_eval_coef(rmean, rvar, gamma, beta, N, 1e-5, with_scale=True)
+    _check_rounded_once(ce, ce_ref, ce_scale, "%s bn_eval_coef" % (shape,))
+    ye = F.batch_norm(x, rmean.double().cpu(), rvar.double().cpu(), gamma, beta, training=False, eps=eps)
+    ye32 = F.batch_norm(x.float(), rmean.cpu(), rvar.cpu(), gamma.float(), beta.float(), training=False, eps=1e-5)
+    _check_floor(ops.bn_affine(xd, ce).view(N, C, P), ye, ye32, "%s eval y" % (shape,), report)
+    print("\n" + "\n".join(report))
+
+
+def _ew_values(kind, gen):
+    """Generators of [values, per-row coefficient pairs, upstream gradients] of the two input kinds.
+    dyadic: scales are powers of two, values and shifts multiples of 2^-8 within +-8 (half of the values on a grid of 1 / 4, shifts on
+    one of 1 / 2, so exact zeros occur at the ReLU): every fp32 operation of the elementwise kernels is exact.  random: standard normal."""
+    if kind == "random":
+        rn = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)
+        return (lambda *s: _f32(rn(*s)),
+                lambda *s: _f32(torch.stack([1 + 0.2 * rn(*s), 0.3 * rn(*s)], -1)),
+                lambda *s: _f32(rn(*s)))
+    ri = lambda lo, hi, *s: torch.randint(lo, hi, s, generator=gen).double()
+    val = lambda *s: torch.where(ri(0, 2, *s) > 0, ri(-2048, 2049, *s) / 256, ri(-32, 33, *s) / 4)
+    pw2 = lambda *s: torch.tensor([0.25, 0.5, 1.0, 2.0, -1.0], dtype=torch.float64)[torch.randint(0, 5, s, generator=gen)]
+    shift = lambda *s: ri(-4, 5, *s) / 2                     # (with quarter-grid values: a zero per ~65 elements of a row)
+    nz = lambda *s: (ri(1, 2049, *s) / 256) * (2 * ri(0, 2, *s) - 1)
+    return val, (lambda *s: torch.stack([pw2(*s), shift(*s)], -1)), nz
+
+
+def _check_tile_sums(got, ref, mag, what, extra=None):
+    """fp32 tile sums against the fp64 sums of the same terms: 32 * 2^-24 * sum |terms| per tile (+ extra)."""
+    got = got.detach().double().cpu()
+    bound = SUM_K * U24 * mag + (0 if extra is None else extra)
+    err = (got - ref).abs()
+    assert bool((err <= bound).all()), "%s: error %.3g x bound" % (what, (err / bound.clamp_min(1e-300)).max().item())
+
+
+# k = fp32 roundings of the kernel's expression + 1 (csrc/bn.hip)
+K_ADD_RELU = 4        # fmaxf(fmaf(sc, a, sh) + fmaf(rc, r, rh), 0): two fma and an add
+K_AFFINE2 = 2         # fmaf(c0, x, c1)
+K_AFFINE3 = 3         # fmaf(c0, g, fmaf(c1, x, c2))
+K_POOL_BWD = 3        # dpooled * (1.f / Ps): the reciprocal and the product
+K_POOL_FWD = SUM_K    # one fma per term, the tile-sum roundings (16) and the division by Ps: 18 <= 32
+
+EW_SHAPES = [(N, C, P) for P in (1, 3, 4, 100, 325, 2044, 2047, 2048, 2049, 2052, 4096, 4100, 24964, 50176)
+             for (N, C) in ((1, 1), (1, 7))] + [(160, 432, 4)]           # N * C = 69120 rows: past 65535
+
+
+def _pool_checks(ops, dev, a5, c5, dp, segs, kind, what):
+    """x3d_bn_relu_pool_fwd / bwd at one shape (a5 [N, C, T, H, W] fp64, dp [N, C, segs])."""
+    N, C = a5.shape[:2]
+    P = a5[0, 0].numel()
+    a5d, c5d = _to(a5, dev), _to(c5, dev)
+    pooled = ops.bn_relu_pool_fwd(a5d, c5d, per_frame=segs > 1)
+    p_ref, p_mag = bn_ref.bn_relu_pool_fwd(a5, c5, segs)
+    _check_terms(pooled, p_ref, p_mag, K_POOL_FWD, what + " pooled")
+    g, part = ops.bn_relu_pool_bwd(a5d, c5d, _to(dp if segs > 1 else dp.view(N, C), dev))
+    g_ref, d, pre, mag = bn_ref.bn_relu_pool_bwd(a5, c5, dp, segs)
+    got = g.detach().double().cpu().view(N, C, P)
+    Ps = P // segs
+    if kind == "dyadic":                                     # no near ties: the mask is exact, and so is d when Ps = 2^k
+        assert torch.equal(got != 0, g_ref != 0), what + " mask"
+        assert bool((pre == 0).any()) or N * C * P < 4000, what + " (no exact zero at the ReLU)"
+        if Ps & (Ps - 1) == 0:
+            assert torch.equal(got, g_ref), what + " g"
+        tie = torch.zeros_like(pre, dtype=torch.bool)
+    else:
+        # the kernel decides the mask from an fp32 fma: elements within 2^-22 (|sc a| + |sh|) of zero are left out
+        tie = pre.abs() < 2.0 ** -22 * mag
+        assert tie.double().mean().item() <= 1e-5, what + " near-tie share"
+    keep = ~tie
+    _check_terms(got * keep, g_ref * keep, d.abs(), K_POOL_BWD, what + " g")
+    a = a5.reshape(N, C, P)
+    ref_part = bn_ref.ew_tile_sums(g_ref, g_ref * a)
+    mag_part = bn_ref.ew_tile_sums(g_ref.abs(), (g_ref * a).abs())
+    extra = bn_ref.ew_tile_sums(d.abs() * tie, (d * a).abs() * tie)
+    # (K_POOL_BWD roundings in front of every term: they are inside the factor 2 of SUM_K)
+    _check_tile_sums(part, ref_part, mag_part, what + " partial", extra)
+
+
+@pytest.mark.parametrize("kind", ["dyadic", "random"])
+@pytest.mark.parametrize("shape", EW_SHAPES, ids=["%dx%dx%d" % s for s in EW_SHAPES])
+def test_elementwise_kernels_against_fp64(shape, kind):
+    """bn_add_relu_fwd / bwd, bn_relu_pool_fwd / bwd (segs = 1), bn_rowstats (both forms), bn_affine (both forms) and, on random
+    inputs, bn_stats_add_relu_fwd over P around the float4 / 2048-element tile edges, scalar rows and N * C > 65535.
+    dyadic inputs: outputs and masks BITWISE the fp64 reference (the > 0 convention at exact zeros, every index computation);
+    random inputs: k 2^-24 sum |terms|; tile sums: 32 * 2^-24 sum |terms| per tile."""
+    from x3dhip import ops
+    dev = _dev()
+    N, C, P = shape
+    val, coefs, ups = _ew_values(kind, torch.Generator().manual_seed(P + 7 * C))
+    a3, res, x2 = val(N, C, P), val(N, C, P), val(N, C, P)
+    c3, cd = coefs(N, C), coefs(N, C)
+    dout = ups(N, C, P)
+    v5 = lambda t: _to(t.view(N, C, P, 1, 1), dev)
+    what = "%s %s" % (shape, kind)
+    for q in (None, cd):
+        out = ops.bn_add_relu_fwd(v5(a3), _to(c3, dev), v5(res), _to(q, dev))
+        ref, terms = bn_ref.bn_add_relu_fwd(a3, c3, res, q, with_terms=True)
+        if kind == "dyadic":
+            assert torch.equal(out.cpu().double().view(N, C, P), ref), what + " bn_add_relu_fwd"
+        else:
+            _check_terms(out, ref, terms, K_ADD_RELU, what + " bn_add_relu_fwd")
+        g, p1, p2 = ops.bn_add_relu_bwd(v5(dout), out, v5(a3), v5(res) if q is not None else None)
+        o64 = out.cpu().double().view(N, C, P)                                # (the kernel's own output is the mask's input)
+        g_ref, part, part_d, mag, mag_d = bn_ref.bn_add_relu_bwd(dout, o64, a3, res if q is not None else None)
+        assert torch.equal(g.cpu().double().view(N, C, P), g_ref), what + " bn_add_relu_bwd g"       # a select: exact always
+        _check_tile_sums(p1, part, mag, what + " bn_add_relu_bwd partial")
+        if q is not None:
+            _check_tile_sums(p2, part_d, mag_d, what + " bn_add_relu_bwd partial_d")
+    if kind == "dyadic" and N * C * P >= 4000:
+        pre = bn_ref._bc(c3, 0, 3) * a3 + bn_ref._bc(c3, 1, 3) + res
+        assert bool((pre == 0).any()), what + " (no exact zero at the ReLU)"
+    _pool_checks(ops, dev, a3.view(N, C, P, 1, 1), c3, ups(N, C, 1), 1, kind, what + " pool")
+    # stand-alone SubBatchNorm3d kernels
+    for gg in (None, dout):
+        part = ops.bn_rowstats(v5(x2), None if gg is None else v5(gg))
+        ref, mag = bn_ref.bn_rowstats(x2, gg)
+        _check_tile_sums(part, ref, mag, what + " bn_rowstats g=%s" % (gg is not None))
+    c33 = torch.cat([cd, c3[..., :1]], -1)
+    for cf, gg, k in ((c3, None, K_AFFINE2), (c33, dout, K_AFFINE3)):
+        out = ops.bn_affine(v5(x2), _to(cf, dev), None if gg is None else v5(gg))
+        ref, terms = bn_ref.bn_affine(x2, cf, gg, with_terms=True)
+        if kind == "dyadic":
+            assert torch.equal(out.cpu().double().view(N, C, P), ref), what + " bn_affine %d" % cf.shape[-1]
+        else:
+            _check_terms(out, ref, terms, k, what + " bn_affine %d" % cf.shape[-1])
+    if kind == "random":                                     # (scale / shift come from statistics: no dyadic form)
+        tiles, S = min(P, 3), 1
+        raw = _bn_raw(N, C, P, seed=P)
+        part = bn_ref.partials_of(raw, tiles, seed=P)
+        gamma, beta = _f32(1 + 0.2 * _g(C, seed=51)), _f32(0.3 * _g(C, seed=52))
+        fr, fs = bn_ref.bn_fwd_finalize(part, S, P, gamma, beta, with_scale=True)
+        out, save = ops.bn_stats_add_relu_fwd(v5(raw), _to(part, dev), S, P, _to(gamma, dev), _to(beta, dev), None, None,
+                                              v5(res), _to(cd, dev))
+        _check_rounded_once(save, fr[1], fs[1], what + " bn_stats_add_relu_fwd save")
+        ref, terms = bn_ref.bn_add_relu_fwd(raw, fr[0], res, cd, with_terms=True)
+        terms = terms + (fs[0][..., 1] - fr[0][..., 1].abs()).view(N, C, 1)
+        _check_terms(out, ref, terms, STATS_K, what + " bn_stats_add_relu_fwd out")
+
+
+@pytest.mark.parametrize("kind", ["dyadic", "random"])
+@pytest.mark.parametrize("shape", [(2, 5, 1, 7, 5), (2, 5, 4, 7, 7), (1, 3, 13, 5, 5), (3, 4, 16, 7, 7), (2, 3, 16, 3, 5),
+                                   (1, 2, 4, 27, 27), (2, 2, 13, 16, 16), (1, 3, 16, 8, 8)])
+def test_elementwise_pool_per_frame_against_fp64(shape, kind):
+    """x3d_bn_relu_pool_fwd / bwd with segs = T (task 'loc': AdaptiveAvgPool3d((None, 1, 1))), T in 1, 4, 13, 16, odd planes,
+    rows of more than one tile with segment boundaries inside a tile; and segs = 1 on the same tensors."""
+    from x3dhip import ops
+    dev = _dev()
+    N, C, T, H, W = shape
+    val, coefs, ups = _ew_values(kind, torch.Generator().manual_seed(T * H * W))
+    a5, c5 = val(N, C, T, H, W), coefs(N, C)
+    _pool_checks(ops, dev, a5, c5, ups(N, C, T), T, kind, "%s %s segs=T" % (shape, kind))
+    _pool_checks(ops, dev, a5, c5, ups(N, C, 1), 1, kind, "%s %s segs=1" % (shape, kind))
+
+
+K_ACC = 2             # scale * g, or fmaf(scale, g, acc): one rounding
+K_SGD_M = 4           # g * gs, fmaf(wd, w, .), fmaf(mu, m, .): three roundings
+K_SGD_W = 6           # those three, lr * m and the subtraction: five roundings
+
+
+def _x3d_m_parameter_count():
+    import x3d as resnet_x3d
+    from x3dhip.trainer import FlatParams
+    return FlatParams(resnet_x3d.generate_model(x3d_version="M", n_classes=400, dropout=0.5, base_bn_splits=1)).numel
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1000, "X3D-M"])
+def test_elementwise_grad_accumulate_and_sgd_against_fp64(n):
+    """x3d_grad_accumulate (first 0 / 1, scale 1 / 3) and x3d_sgd_fused (first 0 / 1, three steps, grad_scale 1 / 8, weight
+    decay 5e-5 and 0, momentum 0.9 and 0) against bn_ref step by step from the kernel's own fp32 state (k 2^-24 sum |terms|),
+    and the three steps against torch.optim.SGD in fp64 on the CPU.  A local error of step t enters the later weights through
+    the momentum buffer with factors lr mu^k: the end-to-end bound is (1 + mu + mu^2) x the sum of the per-step bounds."""
+    from x3dhip import ops
+    dev = _dev()
+    n = _x3d_m_parameter_count() if n == "X3D-M" else n
+    assert n == 1 or n > 200
+    g1, g2 = _f32(_g(n, seed=1)), _f32(_g(n, seed=2))
+    acc = torch.full((n,), float("nan"), device=dev)
+    ops.grad_accumulate(acc, _to(g1, dev), 1 / 3, True)
+    ref, terms = bn_ref.grad_accumulate(None, g1, 1 / 3, True, with_terms=True)
+    _check_terms(acc, ref, terms, K_ACC, "grad_accumulate first")
+    a0 = acc.cpu().double()
+    ops.grad_accumulate(acc, _to(g2, dev), 1 / 3, False)
+    ref, terms = bn_ref.grad_accumulate(a0, g2, 1 / 3, False, with_terms=True)
+    _check_terms(acc, ref, terms, K_ACC, "grad_accumulate")
+    lr, gs = 0.1, 0.125
+    w0 = _f32(_g(n, seed=3))
+    for wd, mu in ((5e-5, 0.9), (0.0, 0.9), (5e-5, 0.0)) if n < 100000 else ((5e-5, 0.9),):
+        f = lambda v: float(np.float32(v))
+        p = torch.nn.Parameter(w0.clone())
+        opt = torch.optim.SGD([p], lr=f(lr), momentum=f(mu), weight_decay=f(wd))
+        w, m = _to(w0, dev), torch.full((n,), float("nan"), device=dev)
+        total = torch.zeros(n, dtype=torch.float64)
+        for it in range(3):
+            gr = _f32(g1 * (it + 1) + g2)
+            p.grad = gr * gs
+            opt.step()
+            wp, mp = w.cpu().double(), m.cpu().double()
+            ops.sgd_fused(w, _to(gr, dev), m, lr, momentum=mu, weight_decay=wd, grad_scale=gs, first=(it == 0))
+            w_ref, m_ref, tw, tm = bn_ref.sgd(wp, gr, mp, lr, mu, wd, gs, first=(it == 0), with_terms=True)
+            _check_terms(m, m_ref, tm, K_SGD_M, "sgd m step %d wd=%g mu=%g" % (it, wd, mu))
+            _check_terms(w, w_ref, tw, K_SGD_W, "sgd w step %d wd=%g mu=%g" % (it, wd, mu))
+            total += K_SGD_W * U24 * tw
+        err = (w.cpu().double() - p.detach()).abs()
+        assert bool((err <= (1 + mu + mu * mu) * total).all()), "sgd against torch.optim.SGD wd=%g mu=%g" % (wd, mu)
+
+
+@pytest.mark.parametrize("groups", [1, 2, 45, 1000])
+def test_reduce_partials_against_fp64(groups):
+    """x3d_reduce_partials (fp64 accumulation, one rounding) against the fp64 column sums, n not a multiple of 256 (nor of
+    the 64 outputs of a workgroup)."""
+    from x3dhip import ops
+    dev = _dev()
+    for n in (1, 63, 300, 1001, 4097):
+        p = _f32(_g(groups, n, seed=groups + n))
+        out = ops.reduce_partials(_to(p, dev), n)
+        _check_rounded_once(out, p.sum(0), p.abs().max(0).values, "reduce_partials %d x %d" % (groups, n))
