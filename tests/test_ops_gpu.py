@@ -1,6 +1,8 @@
 """Kernel-level parity (GPU): every conv kernel of libx3dhip.so, called through the C ABI,
 against a float64 CPU evaluation of the same fused op built from the oracle's per-op
-functions (oracle/x3d_oracle.py).  Tolerance 2e-5 relative L2 (fp32 kernels vs fp64 truth)."""
+functions (oracle/x3d_oracle.py).  Tolerance 2e-5 relative L2 (fp32 kernels vs fp64 truth); the forward GEMM output
+and the three-term backward GEMMs are held to the fp32 floor (2e-6).  tests/test_exact_gpu.py compares the same entry
+points bitwise with fp64 on inputs whose arithmetic is exact."""
 import numpy as np
 import pytest
 import torch
@@ -111,19 +113,49 @@ PW_CASES = [
 
 @pytest.mark.parametrize("case", PW_CASES)
 def test_pw_fwd(case):
+    """y is held to the rule for arithmetic done in fp32 against fp64 (`_check_floor`): 4 x the fp32 floor of the reference
+    -- the same prologue and conv in torch fp32 on the CPU against their fp64 evaluation, per case -- never below 2e-6
+    (= BTOL[3], which the three-term backward kernels meet).  A forward kernel that loses a split term sits at 4.4e-6
+    (DESIGN.md 4.2), which the former 2e-5 let through.  The bound is taken over the whole tensor AND over slices, each
+    relative to the reference's norm on that slice with that slice's own floor: every sample, every 16-row block of output
+    channels, and the tail voxels [P - P % 32, P) -- one wrong tile is not diluted by the rest.
+    Swish cases (act 2: s * rcp(1 + __expf(-s)) in the kernels) are held to the same rule, with the reference floor taken
+    through the same Swish prologue; they need no extra allowance (measured errors: DESIGN.md 4.2)."""
     from x3dhip import ops
     dev = _dev()
     N, Ci, Co, T, H, W, s, act = case
-    x = _g(N, Ci, T, H, W, seed=1)
-    w = _g(Co, Ci, seed=2) / np.sqrt(Ci)
-    pre = torch.stack([1 + 0.2 * _g(N, Ci, seed=3), 0.3 * _g(N, Ci, seed=4)], -1) if act else None
-    xin = _act(pre[..., 0, None, None, None] * x + pre[..., 1, None, None, None], act) if act else x
-    y_ref = xo.pw(xin, w.view(Co, Ci, 1, 1, 1), s)
+    x = _f32(_g(N, Ci, T, H, W, seed=1))                            # (fp64 values that are fp32 values: what the kernel receives)
+    w = _f32(_g(Co, Ci, seed=2) / np.sqrt(Ci))
+    pre = _f32(torch.stack([1 + 0.2 * _g(N, Ci, seed=3), 0.3 * _g(N, Ci, seed=4)], -1)) if act else None
+
+    def fwd(dt):
+        x_, w_ = x.to(dt), w.to(dt)
+        p_ = pre.to(dt) if act else None
+        xin = _act(p_[..., 0, None, None, None] * x_ + p_[..., 1, None, None, None], act) if act else x_
+        return xo.pw(xin, w_.view(Co, Ci, 1, 1, 1), s)
+    y_ref, y_ref32 = fwd(torch.float64), fwd(torch.float32)
+    P = y_ref[0, 0].numel()
     wd = w.float().to(dev)
     for wp in (None, ops.pw_pack(wd)):          # streaming kernel, then (large layers) the tiled one
         y, partial = ops.pw_fwd(x.float().to(dev), wd, stride=s,
                                 pre=None if pre is None else pre.float().contiguous().to(dev), pre_act=act, wp=wp)
         assert _rel(y, y_ref) < TOL
+        report = []
+        try:
+            got = y.cpu().flatten(2)
+            r64, r32 = y_ref.flatten(2), y_ref32.flatten(2)
+            _check_floor(got, r64, r32, "%s y" % ("packed" if wp is not None else "unpacked"), report)
+            for n in range(N):
+                _check_floor(got[n], r64[n], r32[n], "sample %d" % n, report)
+            for m0 in range(0, Co, 16):
+                _check_floor(got[:, m0:m0 + 16], r64[:, m0:m0 + 16], r32[:, m0:m0 + 16], "rows %d..%d" % (m0, min(m0 + 16, Co) - 1), report)
+            if P % 32:
+                p0 = P - P % 32
+                _check_floor(got[:, :, p0:], r64[:, :, p0:], r32[:, :, p0:], "tail voxels %d..%d" % (p0, P - 1), report)
+        finally:
+            errs = [float(line.split("err ")[1]) for line in report]
+            print("\n[%s act %d %s] %d slices, whole-tensor: %s; largest slice error %.2e" % (
+                case, act, "packed" if wp is not None else "unpacked", len(report), report[0] if report else "-", max(errs or [0])))
         st = partial.double().sum(2).cpu()
         assert _rel(st[..., 0], y_ref.sum(dim=(2, 3, 4))) < 5 * TOL + 1e-6
         assert _rel(st[..., 1], (y_ref ** 2).sum(dim=(2, 3, 4))) < 5 * TOL
@@ -678,7 +710,10 @@ def test_elementwise_se_bn_fwd_equals_finalize_then_se(case):
 
 # (N, C, Wd, tiles, S): SE blocks of stages 3-4 at the multigrid shapes (98 / 25 / 13 / 7 statistics tiles per row), XL widths
 SE_BWD_CASES = [(8, 216, 16, 98, 1), (8, 432, 32, 25, 1), (16, 216, 16, 49, 2), (64, 432, 32, 7, 8), (2, 216, 16, 13, 2),
-                (4, 306, 20, 50, 1), (2, 630, 40, 25, 1), (3, 70, 7, 100, 3), (2, 1024, 64, 30, 1)]
+                (4, 306, 20, 50, 1), (2, 630, 40, 25, 1), (3, 70, 7, 100, 3), (2, 1024, 64, 30, 1),
+                # stage 1-2 blocks at the headline shape: 65 fused-backward tiles per row, so cdiv(tiles, tpr) <= 32 holds
+                # and they take the merged per-sample kernel as well
+                (8, 54, 8, 65, 1), (8, 108, 8, 65, 1)]
 
 
 @pytest.mark.parametrize("case", SE_BWD_CASES)
@@ -709,10 +744,12 @@ def test_elementwise_se_bwd_merged_sample_kernel_equals_the_two_launches(case):
         assert _rel(o1[k], o0[k]) < 5e-6, k
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 4, 16, 16), (1, 3, 3, 15, 11), (1, 3, 2, 64, 64), (2, 3, 4, 158, 158),
-                                   # the headline clip length T = 16, and the 5-tap temporal kernel with T below, at and above
-                                   # its width
-                                   (1, 3, 16, 32, 32), (3, 3, 13, 20, 20), (9, 3, 1, 16, 16), (2, 3, 5, 17, 23)])
+STEM_SHAPES = [(2, 3, 4, 16, 16), (1, 3, 3, 15, 11), (1, 3, 2, 64, 64), (2, 3, 4, 158, 158),
+               # the headline clip length T = 16, and the 5-tap temporal kernel with T below, at and above its width
+               (1, 3, 16, 32, 32), (3, 3, 13, 20, 20), (9, 3, 1, 16, 16), (2, 3, 5, 17, 23)]
+
+
+@pytest.mark.parametrize("shape", STEM_SHAPES)
 def test_stem(shape):
     from x3dhip import ops
     dev = _dev()
@@ -1122,12 +1159,13 @@ def test_elementwise_bn_stats_add_relu_fwd_against_fp64(i):
 # (N, C, Wd, tiles, S): every S in 1, 2, 3, 4, 5, 6, 8, 16, 64 (both se_tail_kernel branches; S = 64: empty split butterfly);
 # N in 1, 3, 63, 64, 65, 128, 130 (two samples per lane of the wave form, ragged last batch of eight in se_wgrad_element);
 # Wd in 7, 8, 16, 20, 32, 40, 64; the merge threshold cdiv(tiles, tpr) <= 32 from both sides
-SE_REF_CASES = SE_BN_CASES + SE_BWD_CASES + [
+# (the inputs of a case depend on its index: the rows SE_BWD_CASES gained later stand at the end)
+SE_REF_CASES = SE_BN_CASES + SE_BWD_CASES[:9] + [
     (1, 54, 8, 2, 1), (3, 54, 8, 2, 3), (63, 54, 8, 2, 3), (64, 54, 8, 1, 64), (65, 70, 7, 3, 5), (128, 108, 8, 2, 16),
     (130, 54, 8, 2, 2), (12, 54, 8, 2, 6), (64, 216, 16, 2, 4), (128, 54, 8, 3, 64), (130, 70, 7, 2, 5), (10, 108, 16, 9, 5),
     (4, 306, 20, 3, 2), (4, 432, 32, 2, 4), (2, 630, 40, 3, 2), (3, 1024, 64, 2, 1), (8, 48, 4, 3, 8),
     (2, 1024, 64, 32, 1), (2, 1024, 64, 33, 1), (2, 432, 32, 64, 1), (2, 432, 32, 65, 2), (2, 216, 16, 128, 1),
-    (2, 216, 16, 129, 1), (2, 54, 8, 512, 1), (2, 54, 8, 513, 2)]
+    (2, 216, 16, 129, 1), (2, 54, 8, 512, 1), (2, 54, 8, 513, 2)] + SE_BWD_CASES[9:]
 
 
 def _se_inputs(i, case):
