@@ -1,0 +1,257 @@
+"""The loop the two Charades scripts share (train_x3d_charades.py:53-215, train_x3d_charades_loc.py:54-221): fine-tuning a
+Kinetics model on a `charades.Charades` dataset, phases 2 * ['train'] + ['val'], training mAP from the logits
+`Trainer.train_step` returns, validation through charades_eval, ReduceLROnPlateau stepped with the validation phase's
+tot_loss, the reference's checkpoint record and print lines.
+
+What differs (MI355X-first): batches are made on the device by charades.Charades (no DataLoader, no workers), the losses
+are summed on the device and read where the reference prints them, the meters never leave the GPU, and one process drives
+one GPU (the reference wraps the model in nn.DataParallel).
+"""
+import math
+import os
+import random
+
+import torch
+
+import x3d as resnet_x3d
+import charades_eval
+from apmeter import APMeter
+from charades import Charades, CHARADES_MEAN, CHARADES_STD
+
+
+class ReduceLROnPlateau:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau restated for anything with `param_groups` (torch's class type-checks
+    for a real Optimizer, and the Trainer is not one -- the reason MultiStepLR is restated in the Kinetics script).
+    Semantics of torch's class for threshold_mode='rel', cooldown, min_lr and eps as given; the attributes carry torch's
+    names, so `state_dict()` loads into torch's class and torch's into this one."""
+
+    def __init__(self, optimizer, mode='min', factor=0.1, patience=10, threshold=1e-4, threshold_mode='rel', cooldown=0,
+                 min_lr=0, eps=1e-8):
+        if factor >= 1.0:
+            raise ValueError("Factor should be < 1.0.")
+        if mode not in ('min', 'max'):
+            raise ValueError("mode " + str(mode) + " is unknown!")
+        if threshold_mode not in ('rel', 'abs'):
+            raise ValueError("threshold mode " + str(threshold_mode) + " is unknown!")
+        self.factor = factor
+        self.optimizer = optimizer
+        if isinstance(min_lr, (list, tuple)):
+            if len(min_lr) != len(optimizer.param_groups):
+                raise ValueError("expected %d min_lrs, got %d" % (len(optimizer.param_groups), len(min_lr)))
+            self.default_min_lr = None
+            self.min_lrs = list(min_lr)
+        else:
+            self.default_min_lr = min_lr
+            self.min_lrs = [min_lr] * len(optimizer.param_groups)
+        self.patience = patience
+        self.cooldown = cooldown
+        self.eps = eps
+        self.last_epoch = 0
+        self._last_lr = [g['lr'] for g in optimizer.param_groups]
+        self.mode_worse = math.inf if mode == 'min' else -math.inf
+        self.mode = mode
+        self.threshold = threshold
+        self.threshold_mode = threshold_mode
+        self.best = self.mode_worse
+        self.cooldown_counter = 0
+        self.num_bad_epochs = 0
+
+    def _is_better(self, a, best):
+        if self.mode == 'min' and self.threshold_mode == 'rel':
+            return a < best * (1.0 - self.threshold)
+        if self.mode == 'min':
+            return a < best - self.threshold
+        if self.threshold_mode == 'rel':
+            return a > best * (self.threshold + 1.0)
+        return a > best + self.threshold
+
+    @property
+    def in_cooldown(self):
+        return self.cooldown_counter > 0
+
+    def step(self, metrics):
+        current = float(metrics)
+        self.last_epoch += 1
+        if self._is_better(current, self.best):
+            self.best = current
+            self.num_bad_epochs = 0
+        else:
+            self.num_bad_epochs += 1
+        if self.in_cooldown:
+            self.cooldown_counter -= 1
+            self.num_bad_epochs = 0
+        if self.num_bad_epochs > self.patience:
+            for i, g in enumerate(self.optimizer.param_groups):
+                old_lr = float(g['lr'])
+                new_lr = max(old_lr * self.factor, self.min_lrs[i])
+                if old_lr - new_lr > self.eps:
+                    g['lr'] = new_lr
+            self.cooldown_counter = self.cooldown
+            self.num_bad_epochs = 0
+        self._last_lr = [g['lr'] for g in self.optimizer.param_groups]
+
+    def get_last_lr(self):
+        return self._last_lr
+
+    def state_dict(self):
+        return {k: v for k, v in self.__dict__.items() if k != 'optimizer'}
+
+    def load_state_dict(self, sd):
+        self.__dict__.update(sd)
+        self.mode_worse = math.inf if self.mode == 'min' else -math.inf
+
+
+def synthetic_videos(anno, device, height=36, width=48, seed=0, fps=24):
+    """{video id: uint8 [round(fps * duration), height, width, 3]} of noise on `device` for every video of an annotation
+    dict (JPEG decoding is out of scope: the scripts run on what is already in HBM)."""
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    out = {}
+    for vid, rec in anno.items():
+        n = int(round(fps * rec['duration']))
+        out[vid] = torch.randint(0, 256, (n, height, width, 3), dtype=torch.uint8, device=device, generator=g)
+    return out
+
+
+def _batches(n, batch_size, order=None):
+    order = list(range(n)) if order is None else order
+    return [order[i:i + batch_size] for i in range(0, n, batch_size)]
+
+
+def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
+    """The reference's checkpoint record (train_x3d_charades.py:203-207)."""
+    ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
+            'scheduler_state_dict': lr_sched.state_dict()}
+    os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
+    path = save_model + str(steps).zfill(6) + '.pt'
+    torch.save(ckpt, path)
+    return path
+
+
+def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
+        save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
+        device=None):
+    """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
+    'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
+    load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
+    optimizer and scheduler state).  crop_size / c_size: the testing and training output sizes (default: the version's
+    table and the reference's hard-coded 224).  Returns a dict: 'steps', 'epochs', 'phases' (one record per phase),
+    'checkpoints', 'lr'."""
+    from x3dhip.trainer import Trainer
+    loc = task == 'loc'
+    frames = 80                                                                  # DOUBLED INSIDE DATASET
+    table_crop = {'S': 160, 'M': 224, 'XL': 312}[x3d_version]
+    resize_size = {'S': [180., 225.], 'M': [256., 256.], 'XL': [360., 450.]}[x3d_version]
+    gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[x3d_version]                           # DOUBLED INSIDE DATASET
+    crop_size = table_crop if crop_size is None else crop_size
+    rng = random.Random(seed)
+    steps = epochs = 0
+
+    common = dict(task=task, frames=frames, gamma_tau=gamma_tau, crop_size=crop_size, c_size=c_size,
+                  scales=[table_crop / i for i in resize_size], mean=CHARADES_MEAN, std=CHARADES_STD, rng=rng)
+    dataset = Charades(anno, 'training', videos, crops=1, **common)
+    val_dataset = Charades(anno, 'testing', videos, crops=10, **common)
+    dev = dataset.device
+    if device is not None and torch.device(device) != dev and torch.device(device) != torch.device(dev.type):
+        raise ValueError("device %s was asked for, but the videos are on %s" % (device, dev))
+    torch.cuda.set_device(dev)
+    iterations_per_epoch = max(1, len(dataset) // batch_size)
+    max_steps = iterations_per_epoch * max_epochs
+    print('train', len(dataset), 'val', len(val_dataset))
+    print('Total iterations:', max_steps, 'Total epochs:', max_epochs)
+    print('datasets created')
+
+    kw = dict(task='loc') if loc else {}
+    x3d = resnet_x3d.generate_model(x3d_version=x3d_version, n_classes=400, n_input_channels=3, dropout=dropout,
+                                    base_bn_splits=1, **kw)
+    if load_ckpt is not None:
+        x3d.load_state_dict(torch.load(load_ckpt, map_location='cpu')['model_state_dict'])
+    x3d.replace_logits(157)                      # before the Trainer: FlatParams flattens the head it finds
+    ck = None
+    if resume is not None:
+        ck = torch.load(resume, map_location='cpu')
+        x3d.load_state_dict(ck['model_state_dict'])
+    x3d.to(dev)
+    print('model loaded')
+
+    lr = init_lr
+    print('INIT LR: %f' % lr)
+    optimizer = Trainer(x3d, lr=lr, momentum=0.9, weight_decay=1e-5, objective='loc' if loc else 'bce',
+                        use_graph=use_graph, num_steps_per_update=num_steps_per_update)
+    lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
+    if ck is not None:
+        optimizer.load_state_dict(ck['optimizer_state_dict'])
+        lr_sched.load_state_dict(ck['scheduler_state_dict'])
+
+    val_apm = APMeter()
+    tr_apm = APMeter()
+    phases, checkpoints = [], []
+    s_times = max(1, iterations_per_epoch // 2)
+    zero = torch.zeros((), device=dev)
+    try:
+        while epochs < max_epochs:
+            print('Step {} Epoch {}'.format(steps, epochs))
+            print('-' * 10)
+            for phase in 2 * ['train'] + ['val']:
+                print(phase)
+                if phase == 'train':
+                    x3d.train(True)
+                    epochs += 1
+                    tot_loss, tot_loc_loss, tot_cls_loss = zero.clone(), zero.clone(), zero.clone()
+                    order = list(range(len(dataset)))
+                    rng.shuffle(order)
+                    rec = dict(phase=phase, epoch=epochs, maps=[], losses=[])
+                    for idx in _batches(len(dataset), batch_size, order):
+                        data = dataset.batch(idx)
+                        loss, logits = optimizer.train_step(data[0], data[1])
+                        if loc:
+                            tr_apm.add_frames(logits, data[1], data[2])
+                            tot_cls_loss += optimizer.last_losses[0].view(())
+                            tot_loc_loss += optimizer.last_losses[1].view(())
+                        else:
+                            tr_apm.add_logits(logits, data[1])
+                            tot_cls_loss += loss.detach().view(())
+                        tot_loss += loss.detach().view(()) / num_steps_per_update
+                        if not optimizer.stepped:
+                            continue
+                        steps += 1
+                        if steps % s_times == 0:
+                            tr_map = float(tr_apm.value().mean())
+                            tr_apm.reset()
+                            n = s_times * num_steps_per_update
+                            if loc:
+                                print(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'
+                                      .format(epochs, phase, steps, float(tot_loc_loss) / n, float(tot_cls_loss) / n,
+                                              float(tot_loss) / s_times, tr_map))
+                            else:
+                                print(' Epoch:{} {} steps: {} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                                    epochs, phase, steps, float(tot_cls_loss) / n, float(tot_loss) / s_times, tr_map))
+                            rec['maps'].append(tr_map)
+                            rec['losses'].append(float(tot_loss) / s_times)
+                            tot_loss, tot_loc_loss, tot_cls_loss = zero.clone(), zero.clone(), zero.clone()
+                        if save_every and steps % save_every == 0:
+                            checkpoints.append(_save_ckpt(x3d, optimizer, lr_sched, save_model, steps))
+                    rec['steps'] = steps
+                    phases.append(rec)
+                else:
+                    vb = _batches(len(val_dataset), max(1, batch_size // 2))
+                    gen = (val_dataset.test_batch(idx) for idx in vb)
+                    res = (charades_eval.validate_loc if loc else charades_eval.validate_cls)(x3d, gen, val_apm)
+                    num_iter = len(vb)
+                    tot_loss = res['loss'] * num_iter / num_steps_per_update
+                    val_map = res['map']
+                    lr_sched.step(tot_loss)
+                    val_apm.reset()
+                    if loc:
+                        print(' Epoch:{} {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                            epochs, phase, res['loc_loss'], res['cls_loss'], (tot_loss * num_steps_per_update) / num_iter,
+                            val_map))
+                    else:
+                        print(' Epoch:{} {} Loc Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                            epochs, phase, res['cls_loss'], (tot_loss * num_steps_per_update) / num_iter, val_map))
+                    phases.append(dict(phase=phase, epoch=epochs, map=val_map, loss=tot_loss, rows=res['rows'],
+                                       lr=optimizer.param_groups[0]['lr'], steps=steps))
+    finally:
+        torch.cuda.synchronize()
+    return dict(steps=steps, epochs=epochs, phases=phases, checkpoints=checkpoints, lr=optimizer.param_groups[0]['lr'],
+                scheduler=lr_sched, optimizer=optimizer, model=x3d)
