@@ -1,0 +1,104 @@
+/*
+ * x3djpeg.h -- C ABI of libx3djpeg.so: a baseline JPEG decoder for the frame folders the reference reads with PIL
+ * (kinetics.py:43-51), bit-exact with Pillow's libjpeg-turbo.  Hybrid: the serial part (marker parsing, Huffman decoding)
+ * is plain C++ on the host, callable from several threads at once; everything per pixel (dequantisation, the "islow"
+ * integer IDCT, "fancy" chroma upsampling, YCbCr -> RGB) runs as two HIP kernels (gfx950 / MI355X) per batch of frames,
+ * which store straight into the caller's uint8 [H, W, 3] frames.
+ *
+ * A separate library from libx3dhip.so on purpose: tools/stamp.py and the gradient-hash record hash the training library's
+ * sources, and nothing here runs inside a training step.
+ *
+ * Conventions (as include/x3ddata.h)
+ *   - plain pointers and sizes; the caller owns every buffer; every kernel is enqueued on the hipStream_t passed as
+ *     `stream`; no device entry point allocates or synchronises
+ *   - return 0 on success, negative X3DJPEG_E* on failure; x3djpeg_last_error() gives the message (thread-local)
+ *   - the host stage keeps no global state and makes no HIP call; it never reads outside [bytes, bytes + len) and never
+ *     writes outside the coefficient buffer it is given
+ *   - deterministic bit for bit: every output byte is written exactly once by a plain vector store
+ *
+ * Accepted files: SOF0 / SOF1 with 8-bit samples, Huffman coded, one interleaved scan; 1 component (greyscale, written to
+ * all three channels) or 3 components (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; restart intervals;
+ * 8- and 16-bit quantisation tables.  Everything else is X3DJPEG_EUNSUPPORTED with the feature named in the message.
+ *
+ * Coefficients: int16 in natural (de-zigzagged) order, per component [blocks_h][blocks_w][64] with the block counts
+ * padded to whole MCUs, the components one after the other (coef_off).  Planes: uint8, per component
+ * [blocks_h * 8][blocks_w * 8], the components one after the other: block b of a frame has its coefficients at element
+ * 64 * b and its component's plane starts at byte 64 * block_start.
+ */
+#ifndef X3DJPEG_H
+#define X3DJPEG_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define X3DJPEG_ABI_VERSION 1
+
+#define X3DJPEG_OK 0
+#define X3DJPEG_EINVAL (-1)        /* bad shape / null pointer / buffer too small */
+#define X3DJPEG_ELAUNCH (-2)       /* hipLaunch error */
+#define X3DJPEG_EUNSUPPORTED (-3)  /* a valid file of a kind this decoder does not take; the message names the feature */
+#define X3DJPEG_ECORRUPT (-4)      /* truncated or inconsistent stream */
+
+/* What x3djpeg_parse reads from the headers of one file. */
+typedef struct X3DJpegInfo {
+    int32_t width, height, ncomp;
+    int32_t hmax, vmax;          /* the luma sampling factors */
+    int32_t mcus_x, mcus_y;
+    int32_t restart_interval;    /* in MCUs; 0: none */
+    int32_t comp_h[3], comp_v[3], comp_tq[3], comp_td[3], comp_ta[3];
+    int32_t blocks_w[3], blocks_h[3];   /* padded to whole MCUs */
+    int32_t cw[3], ch[3];               /* the component's true size: ceil(width * h / hmax), ceil(height * v / vmax) */
+    int32_t block_start[3];             /* first block of the component among the frame's blocks */
+    int32_t nblocks;                    /* of all components */
+    int64_t coef_off[3];                /* in int16 elements: 64 * block_start */
+    int64_t coef_count;                 /* int16 elements of the frame: 64 * nblocks */
+    int64_t scan_off;                   /* byte offset of the entropy-coded data */
+    uint16_t qt[4][64];                 /* natural order */
+    uint8_t huff_bits[8][16];           /* [class * 4 + id][length - 1]: codes per length (class 0 DC, 1 AC) */
+    uint8_t huff_vals[8][256];
+    uint8_t qt_set[4];
+    uint8_t huff_set[8];
+    uint8_t pad[4];
+} X3DJpegInfo;
+
+/* One frame of a batch, on the device. */
+typedef struct X3DJpegFrameJob {
+    const int16_t* coef;   /* the frame's coefficients (nblocks * 64) */
+    uint8_t* planes;       /* the frame's planes (nblocks * 64 bytes) */
+    uint8_t* dst;          /* uint8 [height][width][3]; only bytes [0, 3 * width) of each row are written */
+    int64_t dst_stride;    /* bytes between rows, >= 3 * width */
+    int32_t width, height, ncomp, hmax, vmax, nblocks;
+    int32_t blocks_w[3], blocks_h[3], cw[3], ch[3], block_start[3];
+    int32_t pad[3];        /* qt is 16-byte aligned, the struct 512 bytes */
+    uint16_t qt[3][64];    /* per component, natural order */
+} X3DJpegFrameJob;
+
+int x3djpeg_abi_version(void);
+const char* x3djpeg_last_error(void);
+size_t x3djpeg_info_bytes(void);
+size_t x3djpeg_frame_job_bytes(void);
+
+/* Host stage. */
+int x3djpeg_parse(const uint8_t* bytes, size_t len, X3DJpegInfo* info);
+/* Huffman decoding (byte stuffing, DC prediction, restart intervals) of the scan `info` describes into coef
+ * (info->coef_count int16, zero-filled first).  coef_bytes < 2 * coef_count is X3DJPEG_EINVAL. */
+int x3djpeg_entropy_decode(const uint8_t* bytes, size_t len, const X3DJpegInfo* info, int16_t* coef, size_t coef_bytes);
+
+/* Device stage.  jobs: X3DJpegFrameJob [njobs] on the device; max_blocks, max_w, max_h: the maxima of nblocks, width and
+ * height over the jobs (they size the grids).  Frames of a batch may differ in size and subsampling. */
+/* dequantisation + IDCT + 128, clamped: coef -> planes */
+int x3djpeg_idct(const void* jobs, int njobs, int max_blocks, void* stream);
+/* chroma upsampling + colour conversion: planes -> dst */
+int x3djpeg_to_rgb(const void* jobs, int njobs, int max_w, int max_h, void* stream);
+/* both, in two launches whatever njobs is */
+int x3djpeg_decode_batch(const void* jobs, int njobs, int max_blocks, int max_w, int max_h, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* X3DJPEG_H */

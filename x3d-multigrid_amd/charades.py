@@ -1,6 +1,6 @@
 """Charades dataset for X3D on MI355X -- the drop-in for the reference's ``charades.py`` (make_dataset :68-104, Charades
-:107-164, custom_collate_fn :167-189) over decoded uint8 videos already resident in HBM (JPEG decoding is out of scope, as
-for DeviceVideoKinetics).
+:107-164, custom_collate_fn :167-189) over decoded uint8 videos already resident in HBM (frames.charades_videos decodes
+folders of JPEG frames into that form).
 
 What is the same: the dataset filters and order, the doubling of ``frames`` and ``gamma_tau``, the random draws of a
 training sample in the reference's order from Python's ``random``, the label window at stride 1 under frames at stride

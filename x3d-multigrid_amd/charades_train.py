@@ -103,7 +103,7 @@ class ReduceLROnPlateau:
 
 def synthetic_videos(anno, device, height=36, width=48, seed=0, fps=24):
     """{video id: uint8 [round(fps * duration), height, width, 3]} of noise on `device` for every video of an annotation
-    dict (JPEG decoding is out of scope: the scripts run on what is already in HBM)."""
+    dict (the scripts run on what is already in HBM; frames.charades_videos puts real frame folders there)."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     out = {}

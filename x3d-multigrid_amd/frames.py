@@ -1,0 +1,187 @@
+"""Folders of JPEG frames as a data source: the reference's on-disk protocol (kinetics.py:43-51: `frame_%05d.jpg`, 1-based)
+read from disk on the host and decoded on the GPU by x3dhip.jpegops.JpegDecoder (libx3djpeg.so, bit-exact with the PIL
+decode of the reference's loader).
+
+FrameFolder      one video: frame count and size from the listing and the first file's header, raw bytes on demand
+FolderKinetics   DeviceVideoKinetics' batch / val_batch protocol over frame folders: only the frames a sample draws are
+                 decoded, straight into the [T, H, W, 3] tensor ClipPreprocessor consumes
+decode_folder    a whole video as uint8 [n, H, W, 3] in HBM (what charades.Charades(videos=...) takes)
+"""
+import json
+import os
+import random
+
+import torch
+
+from cycle_batch_sampler import long_cycle_shapes
+from kinetics_multigrid import DeviceVideoKinetics
+
+FRAME_NAME = 'frame_{:05d}.jpg'
+MIN_FRAMES = 80 + 1          # kinetics.py:124: videos with n_frames <= 81 are skipped
+
+
+class FrameFolder:
+    """One video as the reference stores it: files frame_00001.jpg, frame_00002.jpg, ... without a gap (video_loader stops
+    at the first missing file, kinetics.py:43-51).  n_frames and (W, H) come from the listing and the first file's header;
+    nothing is decoded.  name: the file name format (the reference's Charades loader has '<video id>-{:06d}.jpg',
+    charades.py:47)."""
+
+    def __init__(self, path, name=FRAME_NAME):
+        from x3dhip.jpegops import read_header
+        self.path, self.name = path, name
+        names = set(os.listdir(path))
+        n = 0
+        while name.format(n + 1) in names:
+            n += 1
+        if n == 0:
+            raise ValueError("%s holds no %s" % (path, name.format(1)))
+        self.n_frames = n
+        self.width, self.height = read_header(self._bytes(0))
+
+    def _bytes(self, i):
+        with open(os.path.join(self.path, self.name.format(i + 1)), 'rb') as f:
+            return f.read()
+
+    def read(self, indices):
+        """The files of the 0-based frames `indices`, as bytes."""
+        for i in indices:
+            if not 0 <= i < self.n_frames:
+                raise ValueError("frame %d outside the %d frames of %s" % (i, self.n_frames, self.path))
+        return [self._bytes(i) for i in indices]
+
+
+def video_names_and_labels(data, subset):
+    """get_video_names_and_annotations (kinetics.py:74-95): folder name per video of the subset, and its label string (None
+    for 'testing', which has no annotations)."""
+    out = []
+    for key, value in data.items():
+        if value['subset'] != subset:
+            continue
+        if subset == 'testing':
+            out.append(('test/{}'.format(key), None))
+        elif subset == 'train':
+            seg = value['annotations']['segment']
+            label = value['annotations']['label']
+            out.append(('{}/{}_{}_{}'.format(label.replace(' ', '_'), key, str(int(seg[0])).zfill(6),
+                                             str(int(seg[1])).zfill(6)), label))
+        else:
+            label = value['annotations']['label']
+            out.append(('{}/{}'.format(label.replace(' ', '_'), key), label))
+    return out
+
+
+def class_labels(lines):
+    """get_class_labels (kinetics.py:64-71): class index = line number in the label file."""
+    return {name: i for i, name in enumerate(lines)}
+
+
+def list_dataset(root, data, class_to_idx, subset):
+    """make_dataset (kinetics.py:98-158) for n_samples_for_each_video == 1: [(FrameFolder, label)], skipping videos whose
+    folder is missing or that have n_frames <= 81.  label is -1 where the subset has no annotations."""
+    out = []
+    for name, label in video_names_and_labels(data, subset):
+        path = os.path.join(root, name)
+        if not os.path.exists(path):
+            continue
+        if len(os.listdir(path)) <= MIN_FRAMES:
+            continue
+        out.append((FrameFolder(path), -1 if label is None else class_to_idx[label]))
+    return out
+
+
+class FolderKinetics(DeviceVideoKinetics):
+    """DeviceVideoKinetics over frame folders instead of decoded videos: same draws (draw_clip_params / val_crop_indices /
+    center_crop_box, through the parent's batch and val_batch), same return values.  Per sample only the drawn frames
+    are read and decoded, into a [T, H, W, 3] tensor that the clip kernels then index with range(T)."""
+
+    class _Video:
+        """What the parent's loops ask of a video: .shape = (n_frames, H, W, 3)."""
+
+        def __init__(self, folder):
+            self.folder = folder
+            self.shape = (folder.n_frames, folder.height, folder.width, 3)
+
+    def __init__(self, folders, labels, sample_duration=80, gamma_tau=5, crop_size=224, x3d_version='M', rng=None,
+                 device='cuda:0', threads=8):
+        from x3dhip.clip_input import ClipPreprocessor
+        from x3dhip.jpegops import JpegDecoder
+        if len(folders) != len(labels) or not folders:
+            raise ValueError("one label per folder, at least one folder")
+        self.folders = [f if isinstance(f, FrameFolder) else FrameFolder(f) for f in folders]
+        self.videos = [self._Video(f) for f in self.folders]
+        self.labels = labels
+        self.sample_duration, self.gamma_tau, self.crop_size = sample_duration, gamma_tau, crop_size
+        self.long_cycles = long_cycle_shapes(sample_duration, crop_size)
+        self.scales = [crop_size / i for i in self.RESIZE[x3d_version]]
+        self.rng = rng if rng is not None else random
+        self.device = torch.device(device)
+        self.decoder = JpegDecoder(self.device, threads=threads)
+        self._pre = ClipPreprocessor(self.device)
+
+    def pre(self, samples, out=None):
+        """The parent hands over (video, params) per sample; decode each sample's frames (one decoder batch for all
+        samples), then run the clip kernels on them."""
+        files, slots = [], []
+        for v, p in samples:
+            idx = p["frame_idx"]
+            files += v.folder.read(idx)
+            slots.append((v, len(idx)))
+        decoded, at = [], 0
+        same = len({v.shape[1:] for v, _ in slots}) == 1
+        if same:                                             # one destination tensor, one job table
+            H, W = slots[0][0].shape[1:3]
+            buf = torch.empty((len(files), H, W, 3), dtype=torch.uint8, device=self.device)
+            self.decoder.decode_into(files, buf)
+            for v, T in slots:
+                decoded.append(buf[at:at + T])
+                at += T
+        else:
+            bufs = [torch.empty((T, v.shape[1], v.shape[2], 3), dtype=torch.uint8, device=self.device) for v, T in slots]
+            self.decoder.decode(files, out=[b[t] for b in bufs for t in range(b.shape[0])])
+            decoded = bufs
+        clips = [(d, dict(p, frame_idx=list(range(d.shape[0])))) for d, (_, p) in zip(decoded, samples)]
+        return self._pre(clips, out=out)
+
+    @classmethod
+    def from_annotation(cls, root, anno_json, labels_txt, subset, **kw):
+        """The reference's dataset listing (kinetics.py:59-158): anno_json and labels_txt are paths (or an annotation dict
+        and a list of class names)."""
+        data = anno_json
+        if not isinstance(data, dict):
+            with open(anno_json, 'r') as f:
+                data = json.load(f)
+        lines = labels_txt
+        if isinstance(lines, str):
+            lines = open(labels_txt).read().splitlines()
+        entries = list_dataset(root, data, class_labels(lines), subset)
+        if not entries:
+            raise ValueError("no video of subset %r under %s" % (subset, root))
+        return cls([e[0] for e in entries], [e[1] for e in entries], **kw)
+
+
+def decode_folder(path, device, threads=8, decoder=None, chunk=256, name=FRAME_NAME):
+    """A whole video as uint8 [n_frames, H, W, 3] on `device`."""
+    from x3dhip.jpegops import JpegDecoder
+    folder = path if isinstance(path, FrameFolder) else FrameFolder(path, name)
+    dec = decoder if decoder is not None else JpegDecoder(device, threads=threads)
+    out = torch.empty((folder.n_frames, folder.height, folder.width, 3), dtype=torch.uint8, device=dec.device)
+    for s in range(0, folder.n_frames, chunk):
+        e = min(folder.n_frames, s + chunk)
+        dec.decode_into(folder.read(range(s, e)), out[s:e])
+    return out
+
+
+def charades_videos(root, anno, device, threads=8):
+    """{video id: uint8 [n, H, W, 3]} for every video of the annotation dict that has a folder under root, decoded whole:
+    the `videos` argument of charades.Charades and the Charades training scripts.  Frames are named frame_%05d.jpg or, as
+    in the reference's Charades loader (charades.py:47), <video id>-%06d.jpg."""
+    from x3dhip.jpegops import JpegDecoder
+    dec = JpegDecoder(device, threads=threads)
+    videos = {}
+    for vid in anno:
+        path = os.path.join(root, vid)
+        if not os.path.isdir(path):
+            continue
+        name = FRAME_NAME if os.path.exists(os.path.join(path, FRAME_NAME.format(1))) else vid + '-{:06d}.jpg'
+        videos[vid] = decode_folder(path, device, decoder=dec, name=name)
+    return videos

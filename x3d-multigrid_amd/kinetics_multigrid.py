@@ -1,6 +1,7 @@
 """Synthetic stand-in for the reference's Kinetics multigrid dataset (kinetics_multigrid.py).
 
-The reference dataset decodes JPEG frame folders on NFS with PIL (out of scope);
+The reference dataset decodes JPEG frame folders on NFS with PIL (here: frames.FolderKinetics, which decodes
+them on the GPU and then follows DeviceVideoKinetics below);
 what matters for the hot path is the *shape protocol* of ``Kinetics.__getitem__``
 (kinetics_multigrid.py:214-259): the index carries (DataLoader task index, (sample, long-cycle
 state)), the clip comes back as float32 [3, T, H, W] with

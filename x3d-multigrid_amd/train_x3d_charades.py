@@ -3,8 +3,9 @@
 scored by the max over the windows.  The loop itself is charades_train.run, shared with train_x3d_charades_loc.py.
 
     python train_x3d_charades.py -gpu 0 --anno data/charades.json --epochs 2 --batch 8 --size 64
-runs on synthetic videos of the annotation file's lengths (JPEG decoding is out of scope; pass real decoded videos to
-run(videos=...) from Python).
+runs on synthetic videos of the annotation file's lengths; with --frames-root DIR every video of the annotation file that
+has a folder DIR/<video id> of JPEG frames is decoded on the GPU into HBM first (frames.charades_videos), and
+run(videos=...) takes decoded videos from Python.
 """
 import argparse
 import json
@@ -61,10 +62,16 @@ def main(run_fn, default_save):
     parser.add_argument('--accumulate', type=int, default=1)
     parser.add_argument('--no-graph', action='store_true')
     parser.add_argument('--version', default=X3D_VERSION)
+    parser.add_argument('--frames-root', default=None, help='root of the per-video folders of JPEG frames')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     size = {} if args.size is None else dict(crop_size=args.size, c_size=args.size)
+    if args.frames_root is not None:
+        import frames
+        with open(args.anno, 'r') as f:
+            anno = json.load(f)
+        size['videos'] = frames.charades_videos(args.frames_root, anno, 'cuda:0')
     run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version, load_ckpt=args.load,
            resume=args.resume, save_model=args.save, save_every=args.save_every, use_graph=not args.no_graph,
            num_steps_per_update=args.accumulate, **size)

@@ -12,13 +12,16 @@ every 4000 steps with split-BN re-shaping before load.
 What differs (MI355X-first): one process per GPU (``torch.distributed`` over RCCL) instead of
 nn.DataParallel -- BATCH is split evenly over ranks, gradients are all-reduced as one flat
 buffer and averaged in the fused SGD kernel; BN statistics stay rank-local exactly as
-DataParallel replicas' do.  Clips are synthetic NCTHW tensors generated in HBM
-(``--synthetic``, the only mode: JPEG loading is out of scope); the per-step (B,T,H,W) comes
+DataParallel replicas' do.  Clips are synthetic NCTHW tensors generated in HBM (``--synthetic``,
+the default) or, with ``--frames-root/--anno/--labels``, come from the reference's folders of JPEG
+frames: read on the host, decoded on the GPU (frames.FolderKinetics); the per-step (B,T,H,W) comes
 from the same schedule arithmetic as the reference's sampler + dataset.
 
     python train_x3d_kinetics_multigrid.py -gpu 0 --steps 60 --iters-per-epoch 40 --max-epochs 3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         train_x3d_kinetics_multigrid.py --steps 200
+    python train_x3d_kinetics_multigrid.py -gpu 0 --frames-root data/kinetics/frames \
+        --anno data/kinetics/kinetics_train.json --labels data/kinetics/labels.txt
 """
 import argparse
 import os
@@ -152,8 +155,12 @@ def _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps):
 def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_UPSCALE, steps=0, max_steps_run=None,
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
-        val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32):
-    """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips.  val_every: run the
+        val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
+        frames_root=None):
+    """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
+    frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8]) for
+    frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
+    sizes); each step's samples are drawn by a sampler seeded per rank, its clips come from FolderKinetics.batch.  val_every: run the
     validation phase (`validate`, the reference does it after every 4 training epochs, :195) every that many steps on
     `val_batches` synthetic batches of [val_batch_size, val_crops, 3, T, H, W].
     num_steps_per_update: gradient accumulation over that many micro-batches per optimizer step (train...:119,267-273;
@@ -215,6 +222,22 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
 
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
+    folder_ds = tasks = sampler = None
+    if frames_root is not None:
+        import random
+        import frames as frames_mod
+        if isinstance(frames_root, dict):
+            kw = dict(frames_root)
+            folder_ds = frames_mod.FolderKinetics.from_annotation(
+                kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'train'), sample_duration=frames,
+                gamma_tau=gamma_tau, crop_size=clip_size or crop_size, x3d_version='XL' if x3d_version == 'L' else x3d_version,
+                rng=random.Random(4321 + rank), device=dev, **kw)
+        else:
+            folder_ds = frames_root
+        sampler = random.Random(1234 + rank)
+        # the DataLoader task index of each step (the short-cycle counter): the same state machine as `shapes`
+        sched, _ = lr_schedule_milestones(int(max_epochs * iterations_per_epoch))
+        tasks = cbs.MultigridSchedule(batch_size, sched, steps * num_steps_per_update, LONG_CYCLE).steps()
     tot_loss = tot_corr = tot_dat = 0.0
     t0 = time.time()
     clips = 0
@@ -244,7 +267,13 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
             B = n_global // world
             if clip_size is not None:
                 H = max(8, H * clip_size // {'S': 160, 'M': 224, 'XL': 312, 'L': 312}[x3d_version])
-            inputs, labels = device_batch(B, T, H, 400, dev, gen)
+            if folder_ds is None:
+                inputs, labels = device_batch(B, T, H, 400, dev, gen)
+            else:
+                _, _, task = next(tasks)
+                picks = [sampler.randrange(len(folder_ds)) for _ in range(B)]
+                inputs, labels, _, _ = folder_ds.batch(picks, task, long_ind)
+                T, H = inputs.shape[2], inputs.shape[3]
             loss, logits = optimizer.train_step(
                 inputs, labels, pre_step=lambda: lr_warmup(lr, steps - st_steps, warmup_steps, optimizer))
             clips += n_global
@@ -300,11 +329,20 @@ if __name__ == '__main__':
     parser.add_argument('--no-graph', action='store_true')
     parser.add_argument('--version', default=X3D_VERSION)
     parser.add_argument('--bf16', action='store_true', help='bf16 storage of the wide bottleneck tensors (fp32 arithmetic)')
+    parser.add_argument('--frames-root', default=None, help='root of the folders of frame_%%05d.jpg (with --anno and --labels)')
+    parser.add_argument('--anno', default=None, help='Kinetics annotation json of the reference')
+    parser.add_argument('--labels', default=None, help='class list, one name per line')
+    parser.add_argument('--decode-threads', type=int, default=8, help='host threads of the JPEG entropy stage (1..16)')
     args = parser.parse_args()
+    frames_root = None
+    if args.frames_root is not None:
+        if args.anno is None or args.labels is None:
+            parser.error('--frames-root needs --anno and --labels')
+        frames_root = dict(root=args.frames_root, anno=args.anno, labels=args.labels, threads=args.decode_threads)
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     run(init_lr=(1.6 / 1024) * args.batch, warmup_steps=args.warmup_steps, max_epochs=args.max_epochs,
         batch_size=args.batch, steps=args.start_step, max_steps_run=args.steps,
         iterations_per_epoch=args.iters_per_epoch, load_ckpt=args.load, save_every=args.save_every,
         use_graph=not args.no_graph, x3d_version=args.version,
-        act_dtype=torch.bfloat16 if args.bf16 else torch.float32)
+        act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root)

@@ -1,0 +1,103 @@
+"""ctypes binding of libx3djpeg.so (include/x3djpeg.h): the JPEG decoder (host parse + Huffman stage, IDCT and colour
+kernels).
+
+Same discipline as _datalib.py: the library is mandatory, torch is imported before it is loaded, the ABI version and the
+sizes of the mirrored structs are checked, and a failing entry point raises X3DHipError with the library's message.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from ._lib import X3DHipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libx3djpeg.so")
+ABI_VERSION = 1
+
+OK, EINVAL, ELAUNCH, EUNSUPPORTED, ECORRUPT = 0, -1, -2, -3, -4
+
+_P = ctypes.c_void_p
+_I = ctypes.c_int
+_Z = ctypes.c_size_t
+
+# name -> (restype, argtypes).  Every symbol include/x3djpeg.h declares is listed here; tests/test_jpeg_host.py checks the
+# two against each other and against the library's exports.
+SIGNATURES = {
+    "x3djpeg_abi_version": (_I, []),
+    "x3djpeg_last_error": (ctypes.c_char_p, []),
+    "x3djpeg_info_bytes": (_Z, []),
+    "x3djpeg_frame_job_bytes": (_Z, []),
+    "x3djpeg_parse": (_I, [_P, _Z, _P]),
+    "x3djpeg_entropy_decode": (_I, [_P, _Z, _P, _P, _Z]),
+    "x3djpeg_idct": (_I, [_P, _I, _I, _P]),
+    "x3djpeg_to_rgb": (_I, [_P, _I, _I, _I, _P]),
+    "x3djpeg_decode_batch": (_I, [_P, _I, _I, _I, _I, _P]),
+}
+
+# X3DJpegInfo / X3DJpegFrameJob of include/x3djpeg.h
+INFO_DT = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hmax", "<i4"), ("vmax", "<i4"),
+                    ("mcus_x", "<i4"), ("mcus_y", "<i4"), ("restart_interval", "<i4"),
+                    ("comp_h", "<i4", 3), ("comp_v", "<i4", 3), ("comp_tq", "<i4", 3), ("comp_td", "<i4", 3),
+                    ("comp_ta", "<i4", 3), ("blocks_w", "<i4", 3), ("blocks_h", "<i4", 3), ("cw", "<i4", 3),
+                    ("ch", "<i4", 3), ("block_start", "<i4", 3), ("nblocks", "<i4"),
+                    ("coef_off", "<i8", 3), ("coef_count", "<i8"), ("scan_off", "<i8"),
+                    ("qt", "<u2", (4, 64)), ("huff_bits", "u1", (8, 16)), ("huff_vals", "u1", (8, 256)),
+                    ("qt_set", "u1", 4), ("huff_set", "u1", 8), ("pad", "u1", 4)], align=True)
+FRAME_JOB_DT = np.dtype([("coef", "<u8"), ("planes", "<u8"), ("dst", "<u8"), ("dst_stride", "<i8"),
+                         ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hmax", "<i4"), ("vmax", "<i4"),
+                         ("nblocks", "<i4"), ("blocks_w", "<i4", 3), ("blocks_h", "<i4", 3), ("cw", "<i4", 3),
+                         ("ch", "<i4", 3), ("block_start", "<i4", 3), ("pad", "<i4", 3), ("qt", "<u2", (3, 64))])
+
+_lib = None
+
+
+def lib():
+    """Load (once) and return the ctypes handle; raises X3DHipError when unavailable."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise X3DHipError(
+            "libx3djpeg.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(or `make -C x3d-multigrid_amd/csrc_jpeg`). The JPEG input path has no fallback." % LIB_PATH)
+    import torch  # noqa: F401  (its HIP runtime first: see _lib.lib)
+    h = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(h, name)
+        except AttributeError as e:
+            raise X3DHipError("libx3djpeg.so lacks symbol %s (stale build?)" % name) from e
+        fn.restype = res
+        fn.argtypes = args
+    v = h.x3djpeg_abi_version()
+    if v != ABI_VERSION:
+        raise X3DHipError("libx3djpeg.so ABI %d != expected %d" % (v, ABI_VERSION))
+    if h.x3djpeg_info_bytes() != INFO_DT.itemsize or h.x3djpeg_frame_job_bytes() != FRAME_JOB_DT.itemsize:
+        raise X3DHipError("libx3djpeg.so structs (%d, %d bytes) differ from the binding's (%d, %d)" % (
+            h.x3djpeg_info_bytes(), h.x3djpeg_frame_job_bytes(), INFO_DT.itemsize, FRAME_JOB_DT.itemsize))
+    _lib = h
+    return h
+
+
+def last_error():
+    return lib().x3djpeg_last_error().decode("utf-8", "replace")
+
+
+def check(rc):
+    if rc != 0:
+        raise X3DHipError("libx3djpeg: error %d: %s" % (rc, last_error()))
+
+
+def parse(data, info=None):
+    """x3djpeg_parse on a bytes object.  Returns (rc, info record, message); info is a 1-element INFO_DT array."""
+    if info is None:
+        info = np.zeros(1, dtype=INFO_DT)
+    rc = lib().x3djpeg_parse(data, len(data), info.ctypes.data)
+    return rc, info, (last_error() if rc else "")
+
+
+def entropy_decode(data, info, coef_ptr, coef_bytes):
+    """x3djpeg_entropy_decode into the int16 buffer at coef_ptr.  Returns (rc, message)."""
+    rc = lib().x3djpeg_entropy_decode(data, len(data), info.ctypes.data, coef_ptr, coef_bytes)
+    return rc, (last_error() if rc else "")
