@@ -49,7 +49,7 @@ from x3dhip import engine  # noqa: E402
 for spec in args:
     kv = dict(kv.split("=") for kv in spec.split(","))
     opts = {k: int(v) for k, v in kv.items() if not k.startswith("cfg.")}
-    cfgs = {k[4:]: bool(int(v)) for k, v in kv.items() if k.startswith("cfg.")}       # schedule switches: cfg.wgrad_overlap=1
+    cfgs = {k[4:]: bool(int(v)) for k, v in kv.items() if k.startswith("cfg.")}       # schedule switches: cfg.no_fused_bwd=1
     old = {k: getattr(engine.cfg, k) for k in cfgs}
     for k, v in cfgs.items():
         setattr(engine.cfg, k, v)

@@ -28,21 +28,6 @@ BN_EPS = 1e-5        # nn.BatchNorm3d defaults used by SubBatchNorm3d (x3d.py:23
 BN_MOMENTUM = 0.1
 
 
-class _BNRef:
-    """Pointers to one SubBatchNorm3d's tensors (x3d.py:9-25)."""
-
-    def __init__(self, mod):
-        self.mod = mod
-
-    @property
-    def gamma(self):
-        return self.mod.weight.data
-
-    @property
-    def beta(self):
-        return self.mod.bias.data
-
-
 def _w2d(p):
     return p.data.view(p.shape[0], -1)
 
@@ -53,7 +38,6 @@ class WeightPacks:
 
     def __init__(self, model):
         import numpy as np
-        from . import _lib
         L = _lib.lib()
         convs = []
         for layer in (model.layer1, model.layer2, model.layer3, model.layer4):
@@ -98,7 +82,6 @@ class WeightPacks:
         return any(w.data_ptr() != p for w, p in zip(self.params, self.ptrs[::2]))
 
     def refresh(self):
-        from . import _lib
         _lib.check(_lib.lib().x3d_pw_pack_batch(self.jobs.data_ptr(), self.wg_job.data_ptr(), self.nwg, _lib.stream()))
 
     def get(self, w, transposed=False):
@@ -132,24 +115,17 @@ class _Config:
         self.no_dw_stats = env("X3D_NO_DW_STATS", "0") == "1"        # separate BN1 finalize launch
         self.dw_bwd_stats = env("X3D_DW_BWD_STATS", "1") == "1"      # BN2-backward finalize in the depthwise prologue
         self.no_res_fuse = env("X3D_NO_RES_FUSE", "0") == "1"        # separate bn_add_relu_bwd launch
-        self.no_batch_reduce = env("X3D_NO_BATCH_REDUCE", "0") == "1"
         self.no_fused_bwd = env("X3D_NO_FUSED_BWD", "0") == "1"      # stages 1-2: separate dgrad + batched wgrad
-        # X3D_WGRAD_OVERLAP=1: the postponed weight gradients of layer4 / layer3 are launched on a second stream when their
-        # stage's data-gradient chain is done, beside the NEXT stage's chain.  OFF by default: measured 8.89 vs 8.59 ms per
-        # step in round 2 (two forks per replay; co-running kernels slow the latency-bound chain by more than the overlap
-        # hides -- the same result as round 1's per-conv side stream)
-        self.wgrad_overlap = env("X3D_WGRAD_OVERLAP", "0") == "1"
-        self.side_stream = env("X3D_SIDE_STREAM") == "1" and env("X3D_NO_SIDE_STREAM") != "1"
-        self.exp_skip_wgrad = env("X3D_EXP_SKIP_WGRAD") == "1"       # timing experiment only: gradients are wrong
         self.no_se_merge = env("X3D_NO_SE_MERGE", "0") == "1"        # separate bn2 finalize + SE launches (round 3)
+        # (a plain object on purpose: bench.py still assigns a removed second-stream switch, which nothing reads)
 
 
 cfg = _Config()
 
 
-def _fused_bwd(grads, g, x, mode=0, has_addend=False):
+def _fused_bwd(g, x, mode=0, has_addend=False):
     """Stages 1-2: data gradient and weight gradient of a pointwise conv from one pass (ops.pw_bwd_fused)."""
-    if cfg.no_fused_bwd or grads.side is not None or cfg.exp_skip_wgrad:
+    if cfg.no_fused_bwd:
         return False
     if _lib.get_option("dgrad_f32") or _lib.get_option("wgrad_f32"):      # exact-fp32 A/B switches: separate kernels
         return False
@@ -158,10 +134,13 @@ def _fused_bwd(grads, g, x, mode=0, has_addend=False):
     return ops.pw_bwd_fused_ok(x.shape[1], g.shape[1], g[0, 0].numel(), mode, has_addend, ops.pw_bwd_fused_mx(g, x))
 
 
+def _bn_tensors(bn):
+    """(gamma, beta, running mean, running var) of a SubBatchNorm3d in training: what every BN forward finalize takes."""
+    return bn.weight.data, bn.bias.data, bn.split_bn.running_mean, bn.split_bn.running_var
+
+
 def _bn_train(partial, bn, S, count, want_nsum=False):
-    return ops.bn_fwd_finalize(partial, S, count, bn.weight.data, bn.bias.data,
-                               bn.split_bn.running_mean, bn.split_bn.running_var,
-                               BN_MOMENTUM, BN_EPS, want_nsum=want_nsum)
+    return ops.bn_fwd_finalize(partial, S, count, *_bn_tensors(bn), BN_MOMENTUM, BN_EPS, want_nsum=want_nsum)
 
 
 def _bn_eval(bn, N):
@@ -230,8 +209,7 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
     P1 = a1[0, 0].numel()
     if training and not cfg.no_dw_stats:
         # bn1's finalize runs inside the depthwise kernel's prologue (one launch less per block)
-        a2, p2, c1, s1 = ops.dw333_fwd_stats(a1, blk.conv2.weight.data, p1, S, P1, blk.bn1.weight.data, blk.bn1.bias.data,
-                                             blk.bn1.split_bn.running_mean, blk.bn1.split_bn.running_var,
+        a2, p2, c1, s1 = ops.dw333_fwd_stats(a1, blk.conv2.weight.data, p1, S, P1, *_bn_tensors(blk.bn1),
                                              stride=stride, pre_act=ACT_RELU, momentum=BN_MOMENTUM, eps=BN_EPS)
     else:
         if training:
@@ -245,10 +223,9 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
     se = None
     if training and blk.has_se and not cfg.no_se_merge and blk.bn2.weight.shape[0] <= 1024:
         # bn2's finalize and the SE branch in one launch (round 4)
-        bn2 = blk.bn2
-        c2e, s2, nsum2, se_v, z, pool = ops.se_bn_fwd(p2, S, P2, bn2.weight.data, bn2.bias.data, bn2.split_bn.running_mean,
-                                                      bn2.split_bn.running_var, _w2d(blk.fc1.weight), blk.fc1.bias.data,
-                                                      _w2d(blk.fc2.weight), blk.fc2.bias.data, BN_MOMENTUM, BN_EPS)
+        c2e, s2, nsum2, se_v, z, pool = ops.se_bn_fwd(p2, S, P2, *_bn_tensors(blk.bn2), _w2d(blk.fc1.weight),
+                                                      blk.fc1.bias.data, _w2d(blk.fc2.weight), blk.fc2.bias.data,
+                                                      BN_MOMENTUM, BN_EPS)
         se = dict(se=se_v, z=z, pool=pool, nsum=nsum2)
     else:
         if training:
@@ -282,9 +259,8 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
             raise RuntimeError("identity residual needs a materialised block input")
         res, rcoef = x_raw, None
     if training:
-        bn3 = blk.bn3
-        out, s3 = ops.bn_stats_add_relu_fwd(a3, p3, S, P2, bn3.weight.data, bn3.bias.data, bn3.split_bn.running_mean,
-                                            bn3.split_bn.running_var, res, rcoef, momentum=BN_MOMENTUM, eps=BN_EPS)
+        out, s3 = ops.bn_stats_add_relu_fwd(a3, p3, S, P2, *_bn_tensors(blk.bn3), res, rcoef,
+                                            momentum=BN_MOMENTUM, eps=BN_EPS)
     else:
         out = ops.bn_add_relu_fwd(a3, c3, res, rcoef)
     if ctx is not None:
@@ -303,39 +279,14 @@ class _GradSink:
     zeroed flat gradient buffer): kernels write straight into the existing .grad storage and
     autograd gets None -- 300+ tiny accumulate kernels per step disappear."""
 
-    def __init__(self, direct, side=None):
+    def __init__(self, direct):
         self.direct = direct
         self.written = {}
-        self.side = side          # HIP stream for the weight-gradient kernels (off the critical path)
-        # group sums of the weight-gradient partials, postponed to one launch per backward part (single-stream mode)
-        self.deferred = ops.DeferredGrads() if (side is None and not cfg.no_batch_reduce) else None
+        # group sums of the weight-gradient partials, postponed to one launch per backward part
+        self.deferred = ops.DeferredGrads()
 
     def flush(self):
-        if self.deferred is not None:
-            self.deferred.flush()
-        self.join()
-
-    def flush_async(self, device):
-        """Launch what has been postponed so far on the second stream (fork here, join in flush()).  Every tensor the
-        launches read or write stays referenced until the join."""
-        d = self.deferred
-        if d is None or not cfg.wgrad_overlap or self.side is not None or (not d.wjobs and not d.reduces):
-            return
-        main = torch.cuda.current_stream()
-        st = side_stream(device)
-        st.wait_stream(main)
-        self._async_keep = getattr(self, "_async_keep", [])
-        self._async_keep.append((d.keep, list(d.reduces)))
-        with torch.cuda.stream(st):
-            d.flush()
-        self._async_side = st
-
-    def join(self):
-        st = getattr(self, "_async_side", None)
-        if st is not None:
-            torch.cuda.current_stream().wait_stream(st)
-            self._async_side = None
-            self._async_keep = []
+        self.deferred.flush()
 
     def out(self, p):
         if self.direct and p.grad is not None:
@@ -352,8 +303,9 @@ def trunk_backward(model, ctx, dpooled, grads, part="all", state=None):
 
     part = "all": the whole backward.  "late": head, layer4, layer3 only -- returns the state for
     part = "early" (layer2, layer1, stem), so that the gradient exchange of the late parameters (x3dhip/trainer.py,
-    first bucket) can run while the early layers' backward executes.  Every part ends with the side stream
-    joined: when it returns, all gradients of its parameters are ordered before later work on the current stream."""
+    first bucket) can run while the early layers' backward executes.  Every part ends with its
+    postponed work enqueued: when it returns, all gradients of its parameters are ordered before later work on the
+    current stream."""
     n_late = len(model.layer3) + len(model.layer4)
     blocks = list(reversed(ctx.blocks))
     if part in ("all", "late"):
@@ -362,8 +314,7 @@ def trunk_backward(model, ctx, dpooled, grads, part="all", state=None):
         a5 = hd["a5"]
         P5 = a5[0, 0].numel()
         g5, pp = ops.bn_relu_pool_bwd(a5, hd["c5"], dpooled.contiguous())
-        _bn_bwd(grads, pp, S, P5, model.bn5, hd["save5"], out_cb=True)
-        cb5 = grads.last_cb
+        cb5 = _bn_bwd(grads, pp, S, P5, model.bn5, hd["save5"])
         _wgrad(grads, model.conv5.weight, g5, a5, cb5, hd["x4"])
         if _res_fusable(blocks[0]):
             dcur = ops.pw_bwd_data_res(g5, a5, cb5, _w2d(model.conv5.weight), blocks[0]["out"], blocks[0]["a3"],
@@ -373,15 +324,10 @@ def trunk_backward(model, ctx, dpooled, grads, part="all", state=None):
         del g5
         pstem = None
         last = len(blocks) if part == "all" else n_late
-        n4 = len(model.layer4)
         for i in range(last):
             dcur, pstem = _block_backward(blocks[i], dcur, grads, blocks[i + 1] if i + 1 < len(blocks) else None)
-            if i + 1 == n4 or (i + 1 == n_late and part == "all"):
-                grads.flush_async(dcur[0].device if isinstance(dcur, tuple) else dcur.device)
         if part == "late":
             grads.flush()
-            if grads.side is not None:
-                torch.cuda.current_stream().wait_stream(grads.side)
             return dcur, pstem
     else:
         dcur, pstem = state
@@ -392,82 +338,27 @@ def trunk_backward(model, ctx, dpooled, grads, part="all", state=None):
     st = ctx.stem
     a_t = st["a_t"]
     P = a_t[0, 0].numel()
-    _bn_bwd(grads, pstem, S, P, model.bn1, st["save0"])
-    cb0 = grads.last_cb
+    cb0 = _bn_bwd(grads, pstem, S, P, model.bn1, st["save0"])
     w_t, w_s = model.conv1_t.weight, model.conv1_s.weight
     dx_s, dwt = ops.dw5t_bwd(dcur, a_t, cb0, w_t.data, st["a_s"], dw_out=grads.out(w_t))
     grads.put(w_t, dwt)
     grads.put(w_s, ops.stem133_bwd_weight(st["x"], dx_s, w_s.shape, out=grads.out(w_s)))
     grads.flush()
-    if grads.side is not None:
-        torch.cuda.current_stream().wait_stream(grads.side)
     return None
 
 
-def _bn_bwd(grads, partial, S, count, bn, save, out_cb=True):
+def _bn_bwd(grads, partial, S, count, bn, save):
     cb, dg, db = ops.bn_bwd_finalize(partial, S, count, bn.weight.data, save, dgamma=grads.out(bn.weight),
                                      dbeta=grads.out(bn.bias))
     grads.put(bn.weight, dg)
     grads.put(bn.bias, db)
-    grads.last_cb = cb
     return cb
 
 
-_side_streams = {}
-
-
-def use_side_stream():
-    """Weight-gradient kernels on a second HIP stream: OFF by default.  It paid while the data-gradient chain was slow;
-    since the persistent dgrad / split-bf16 wgrad kernels the forked graph replays 3.8 % slower than the linear one
-    (10.85 vs 10.46 ms at config 2: the overlapped kernels slow each other down by about what the overlap hides, and
-    every fork / join is a cross-queue dependency).  X3D_SIDE_STREAM=1 turns it back on."""
-    return cfg.side_stream
-
-
-def side_stream(device):
-    """One extra HIP stream per device for work that is off the backward critical path."""
-    st = _side_streams.get(device)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _side_streams[device] = st
-    return st
-
-
 def _wgrad(grads, w, g, a, cb, x, **kw):
-    """Pointwise weight gradient.  Nothing downstream in the backward pass consumes it, so it runs
-    on the side stream, concurrently with the data-gradient chain (the small stage-3/4 kernels
-    cannot fill 256 CUs on their own); joined once at the end of trunk_backward."""
-    if cfg.exp_skip_wgrad:      # timing experiment only: gradients are wrong
-        o = grads.out(w)
-        grads.put(w, o if o is not None else torch.zeros_like(w))
-        return
-    side = grads.side
-    if side is None:
-        grads.put(w, ops.pw_bwd_weight(g, a, cb, x, w.shape, out=grads.out(w), defer=grads.deferred, **kw))
-        return
-    main = torch.cuda.current_stream()
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        dw = ops.pw_bwd_weight(g, a, cb, x, w.shape, out=grads.out(w), **kw)
-    for t in (g, a, cb, x, kw.get("pre")):
-        if t is not None:
-            t.record_stream(side)
-    grads.put(w, dw)
-
-
-def _on_side(grads, fn, tensors):
-    """Run fn() on the side stream after everything enqueued so far on the current stream (same
-    protocol as _wgrad); `tensors` are its inputs allocated on the main stream."""
-    side = grads.side
-    if side is None:
-        return fn()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        r = fn()
-    for t in tensors:
-        if t is not None:
-            t.record_stream(side)
-    return r
+    """Pointwise weight gradient.  Nothing downstream in the backward pass consumes it: the kernel and the group sum of
+    its partials are queued in grads.deferred and run in the batched launches that end the backward part (flush)."""
+    grads.put(w, ops.pw_bwd_weight(g, a, cb, x, w.shape, out=grads.out(w), defer=grads.deferred, **kw))
 
 
 def _res_fusable(rec):
@@ -493,7 +384,7 @@ def _block_backward(rec, dout, grads, below=None):
     cb3 = _bn_bwd(grads, p3, S, P2, blk.bn3, rec["s3"])
 
     # conv3: weight gradient, then data gradient fused with the swish backward (one pass at stages 1-2)
-    if _fused_bwd(grads, g3, a2, mode=1):
+    if _fused_bwd(g3, a2, mode=1):
         w3 = blk.conv3.weight
         ds, ps, dw3 = ops.pw_bwd_fused(g3, a3, cb3, w3.shape, rec["w3t"], a2, xpre=rec["c2e"], xact=ACT_SWISH, mode=1,
                                        dw_out=grads.out(w3), defer=grads.deferred)
@@ -511,12 +402,9 @@ def _block_backward(rec, dout, grads, below=None):
         cb2, o = ops.se_bn_bwd_finalize(ps, S, P2, blk.bn2.weight.data, blk.bn2.bias.data, rec["s2"], se["nsum"],
                                         _w2d(blk.fc1.weight), _w2d(blk.fc2.weight), se["se"], se["z"], se["pool"],
                                         outs=outs)
-        grads.put(blk.bn2.weight, o["dgamma"])
-        grads.put(blk.bn2.bias, o["dbeta"])
-        grads.put(blk.fc1.weight, o["dw1"])
-        grads.put(blk.fc1.bias, o["db1"])
-        grads.put(blk.fc2.weight, o["dw2"])
-        grads.put(blk.fc2.bias, o["db2"])
+        for p, k in ((blk.bn2.weight, "dgamma"), (blk.bn2.bias, "dbeta"), (blk.fc1.weight, "dw1"), (blk.fc1.bias, "db1"),
+                     (blk.fc2.weight, "dw2"), (blk.fc2.bias, "db2")):
+            grads.put(p, o[k])
     elif S == 1 and cfg.dw_bwd_stats:
         cb2 = None          # bn2's backward finalize runs in the depthwise kernel's prologue
     else:
@@ -534,15 +422,19 @@ def _block_backward(rec, dout, grads, below=None):
     g1, wpart2, p1 = ops.dw333_bwd(ds, a2, cb2, blk.conv2.weight.data, a1, stride=blk.stride, pre=rec["c1"],
                                    pre_act=ACT_RELU, reduce=False, bn=bn2)
     del ds
-    # the group sum of the 27-tap partials feeds only the optimizer: side stream
+    # the group sum of the 27-tap partials feeds only the optimizer: postponed with the other weight gradients
     w2 = blk.conv2.weight
-    grads.put(w2, _on_side(grads, lambda: ops.dw333_bwd_reduce(wpart2, w2.shape, grads.out(w2), defer=grads.deferred),
-                           (wpart2,)))
+    grads.put(w2, ops.dw333_bwd_reduce(wpart2, w2.shape, grads.out(w2), defer=grads.deferred))
     cb1 = _bn_bwd(grads, p1, S, P1, blk.bn1, rec["s1"])
 
     # conv1 (+ downsample branch)
-    mode1 = 2 if _res_fusable(below) else (1 if x_coef is not None else 0)
-    fuse1 = _fused_bwd(grads, g1, x_raw, mode=mode1, has_addend=True)
+    if _res_fusable(below):            # x_raw IS below["out"]: the mask of the producer's ReLU and the conv's input
+        mode, kw = 2, dict(ex=below["a3"])
+    elif x_coef is not None:           # lazily normalised input (layer1.0: the stem's BN + ReLU)
+        mode, kw = 1, dict(xpre=x_coef, xact=pre_act)
+    else:
+        mode, kw = 0, {}
+    fuse1 = _fused_bwd(g1, x_raw, mode=mode, has_addend=True)
     if not fuse1:
         _wgrad(grads, blk.conv1.weight, g1, a1, cb1, x_raw, pre=x_coef, pre_act=pre_act)
     if blk.downsample is not None:
@@ -555,12 +447,6 @@ def _block_backward(rec, dout, grads, below=None):
         addend, astride = g3, 1
     if fuse1:
         w1 = blk.conv1.weight
-        if _res_fusable(below):            # x_raw IS below["out"]: the mask of the producer's ReLU and the conv's input
-            mode, kw = 2, dict(ex=below["a3"])
-        elif x_coef is not None:           # lazily normalised input (layer1.0: the stem's BN + ReLU)
-            mode, kw = 1, dict(xpre=x_coef, xact=pre_act)
-        else:
-            mode, kw = 0, {}
         dprev, pprev, dw1 = ops.pw_bwd_fused(g1, a1, cb1, w1.shape, rec["w1t"], x_raw, mode=mode, addend=addend,
                                              addend_stride=astride, dw_out=grads.out(w1), defer=grads.deferred, **kw)
         grads.put(w1, dw1)
@@ -598,9 +484,7 @@ class TrunkFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpooled):
-        import os
-        side = side_stream(dpooled.device) if use_side_stream() else None
-        sink = _GradSink(getattr(ctx.model, "_direct_grads", False), side)
+        sink = _GradSink(getattr(ctx.model, "_direct_grads", False))
         trunk_backward(ctx.model, ctx.tctx, dpooled, sink)
         ctx.tctx = None
         out = []

@@ -231,6 +231,17 @@ class Trainer:
         if y.device != x.device:
             raise ValueError("labels on %s, clips on %s" % (y.device, x.device))
 
+    def _fwd_head(self, x, y):
+        """Zero the gradients, trunk forward, head + loss + head backward: everything of a step before the trunk's
+        backward.  Returns (loss, logits) and what engine.trunk_backward takes: the context, dpooled and a fresh sink."""
+        from . import engine
+        self.fp.grad.zero_()
+        tctx = engine.TrunkContext()
+        with torch.no_grad():
+            pooled = engine.trunk_forward(self.model, x.contiguous().float(), True, tctx)
+            loss, logits, dpooled = self._head_loss_bwd(pooled, y)                               # x3d.py:333-339
+        return loss, logits, tctx, dpooled, engine._GradSink(True)
+
     def _fwd_bwd(self, x, y):
         from . import engine
         model = self.model
@@ -240,14 +251,10 @@ class Trainer:
             loss = F.cross_entropy(logits, y)
             loss.backward()
             return loss.detach(), logits.detach()
-        self.fp.grad.zero_()
-        tctx = engine.TrunkContext()
+        loss, logits, tctx, dpooled, sink = self._fwd_head(x, y)
+        model._pending_tracked += 1             # (the split form counts the step in _graphed_split)
         with torch.no_grad():
-            pooled = engine.trunk_forward(model, x.contiguous().float(), True, tctx)
-            model._pending_tracked += 1
-            loss, logits, dpooled = self._head_loss_bwd(pooled, y)
-            side = engine.side_stream(x.device) if engine.use_side_stream() else None
-            engine.trunk_backward(model, tctx, dpooled, engine._GradSink(True, side))
+            engine.trunk_backward(model, tctx, dpooled, sink)
         return loss, logits
 
     def _allreduce(self):
@@ -359,7 +366,7 @@ class Trainer:
         key = (tuple(x.shape), self.model._bn_version, self.model.training) + self._objective_key(y)
         ent = self._lookup(key)
         if ent is None:
-            ent = self._capture(x, y)
+            ent = self._capture(x, y, self._fwd_bwd)
             self._store(key, ent)
         self._feed(ent, x, y)
         ent["fb"].replay()
@@ -382,49 +389,21 @@ class Trainer:
     def _fwd_bwd_late(self, x, y):
         """Graph A: zero grads, forward, loss, head backward, trunk backward of conv5 / layer4 / layer3."""
         from . import engine
-        model = self.model
-        self.fp.grad.zero_()
-        tctx = engine.TrunkContext()
+        loss, logits, tctx, dpooled, sink = self._fwd_head(x, y)
         with torch.no_grad():
-            pooled = engine.trunk_forward(model, x.contiguous().float(), True, tctx)
-            loss, logits, dpooled = self._head_loss_bwd(pooled, y)                               # x3d.py:333-339
-            side = engine.side_stream(x.device) if engine.use_side_stream() else None
-            sink = engine._GradSink(True, side)
-            state = engine.trunk_backward(model, tctx, dpooled, sink, part="late")
+            state = engine.trunk_backward(self.model, tctx, dpooled, sink, part="late")
         return loss, logits, tctx, sink, state
 
-    def _capture_split(self, x, y):
+    def _bwd_early(self, tctx, sink, state):
+        """Graph B: trunk backward of layer2 / layer1 / stem."""
         from . import engine
-        sx, sy = x.clone(), y.clone()
-        bn_state = {k: v.clone() for k, v in self.model.state_dict().items() if "running_" in k}
-        pending = self.model._pending_tracked
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):                                  # allocator / lazy-init warm-up, eager
-                _, _, tctx, sink, state = self._fwd_bwd_late(sx, sy)
-                engine.trunk_backward(self.model, tctx, None, sink, part="early", state=state)
-        torch.cuda.current_stream().wait_stream(s)
-        ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        # thread-local capture: the process group's watchdog thread may touch the HIP runtime while we capture
-        with torch.cuda.graph(ga, capture_error_mode="thread_local"):
-            loss, logits, tctx, sink, state = self._fwd_bwd_late(sx, sy)
-        with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
-            engine.trunk_backward(self.model, tctx, None, sink, part="early", state=state)
-        self.model._pending_tracked = pending
-        sd = self.model.state_dict()
-        for k, v in bn_state.items():
-            sd[k].copy_(v)
-        ent = dict(x=sx, y=sy, ga=ga, gb=gb, loss=loss, logits=logits, keep=(tctx, sink, state))
-        if self.objective == "loc":
-            ent["losses"] = self.last_losses      # written by the captured head: the replays refresh them
-        return ent
+        engine.trunk_backward(self.model, tctx, None, sink, part="early", state=state)
 
     def _graphed_split(self, x, y):
         key = ("split", tuple(x.shape), self.model._bn_version) + self._objective_key(y)
         ent = self._lookup(key)
         if ent is None:
-            ent = self._capture_split(x, y)
+            ent = self._capture(x, y, self._fwd_bwd_late, self._bwd_early)
             self._store(key, ent)
         self._feed(ent, x, y)
         ent["ga"].replay()
@@ -450,26 +429,40 @@ class Trainer:
             # at the same step: the sampler is deterministic in the step counter, cycle_batch_sampler.py:76-93)
             torch.cuda.empty_cache()
 
-    def _capture(self, x, y):
+    def _capture(self, x, y, body, tail=None):
+        """Capture a step on clones of (x, y).  body(x, y) -> (loss, logits, *keep) becomes one graph (entry key "fb").
+        With `tail` (the split form) body becomes graph "ga" and tail(*keep) graph "gb" in the same pool: the caller
+        starts the first gradient bucket between their replays."""
+        split = tail is not None
+        # thread-local capture: the process group's watchdog thread may touch the HIP runtime while we capture
+        mode = "thread_local" if (split or self.world > 1) else "global"
         sx, sy = x.clone(), y.clone()
-        # warm-up on a side stream (allocator + lazy init), restoring state that a real step mutates
+        # the warm-up and the capture run real steps: state that a step mutates is restored afterwards
         bn_state = {k: v.clone() for k, v in self.model.state_dict().items() if "running_" in k}
         pending = self.model._pending_tracked      # (state_dict() above flushed it: 0)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(2):
-                self._fwd_bwd(sx, sy)
+            for _ in range(2):                                  # allocator / lazy-init warm-up, eager
+                keep = body(sx, sy)[2:]
+                if split:
+                    tail(*keep)
         torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local" if self.world > 1 else "global"):
-            loss, logits = self._fwd_bwd(sx, sy)
-        # undo the warm-up's side effects on BN running stats / counters
+        ga = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(ga, capture_error_mode=mode):
+            loss, logits, *keep = body(sx, sy)
+        ent = dict(x=sx, y=sy, loss=loss, logits=logits)
+        if split:
+            gb = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode=mode):
+                tail(*keep)
+            ent.update(ga=ga, gb=gb, keep=tuple(keep))
+        else:
+            ent["fb"] = ga
         self.model._pending_tracked = pending
         sd = self.model.state_dict()
         for k, v in bn_state.items():
             sd[k].copy_(v)
-        ent = dict(x=sx, y=sy, fb=g, loss=loss, logits=logits)
         if self.objective == "loc":
             ent["losses"] = self.last_losses      # written by the captured head: the replays refresh them
         return ent
