@@ -1,7 +1,8 @@
 /*
- * x3ddata.h -- C ABI of libx3ddata.so: HIP kernels (gfx950 / MI355X) of the Charades input path, what the reference's
- * dataset does per sample on CPU workers (charades.py:68-189): the per-frame label windows cut from dense host arrays,
- * the clip transforms, and the zero padding of custom_collate_fn.
+ * x3ddata.h -- C ABI of libx3ddata.so: HIP kernels (gfx950 / MI355X) of the input paths, what the reference's datasets
+ * do per sample on CPU workers: for Charades (charades.py:68-189) the per-frame label windows cut from dense host arrays,
+ * the clip transforms, and the zero padding of custom_collate_fn; for Kinetics (kinetics_multigrid.py:240-253) the clip
+ * transforms.
  *
  * A separate library from libx3dhip.so on purpose: tools/stamp.py and the gradient-hash record hash the training library's
  * sources, and nothing here runs inside a training step.
@@ -83,8 +84,14 @@ int x3ddata_charades_labels(const int32_t* ann_off, const int32_t* ann_cls, cons
  * in `scratch`, then the vertical pass + flip + ToTensor(255) + Normalize(mean, std) + the zero padding.  Replaces
  * load_rgb_frames and the spatial transforms of __getitem__ (charades.py:139,145-148; transforms/spatial_transforms.py
  * :44-83,106-116,214-228,334-346,480-495), the window slicing of the testing split (:150-157) and the clip padding of
- * custom_collate_fn (:179-183).  max_T / max_Tpad / max_crop / max_out: the maxima over the jobs (they size the grid).
- * mean, stdv: 3 floats each on the host. */
+ * custom_collate_fn (:179-183); and, for Kinetics, the per-sample CPU work of kinetics_multigrid.py:240-253 (frame
+ * selection by TemporalRandomCrop, transforms/temporal_transforms.py:94-117, with the indices computed by the host;
+ * MultiScaleRandomCropMultigrid; RandomHorizontalFlip; ToTensor(255) + Normalize; stack / permute to [3][T][S][S]): one
+ * job per sample with dst_cs = T * S * S, dst_ts = S * S, no padding and one window.  Bit-exact with Pillow's 8-bit
+ * bilinear resample given the host-built coefficient table (x3dhip/clip_input.py:resize_coeffs = Resample.c
+ * precompute_coeffs + normalize_coeffs_8bpc).
+ * max_T / max_Tpad / max_crop / max_out: the maxima over the jobs (they size the grid).  mean, stdv: 3 floats each on the
+ * host. */
 int x3ddata_clip_batch(const void* jobs, int njobs, const int32_t* frames, uint8_t* scratch, int max_T, int max_Tpad,
                        int max_crop, int max_out, const float* mean, const float* stdv, void* stream);
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define X3D_ABI_VERSION 7
+#define X3D_ABI_VERSION 8
 
 #define X3D_OK 0
 #define X3D_EINVAL (-1)   /* bad shape / null pointer / unsupported size */
@@ -71,7 +71,12 @@ int x3d_debug_poison_lds(void* sink, void* stream);
  *   no_wgrad4, wg_cpw, wg_cap, stem_wg_cap, dw_tsplit_wgs (channelwise launches of at most this many workgroups cut the T
  *   march into two segments; 0 = never; backward kernel), dw_tsplit_wgs_fwd (the same for the forward kernel), dw_cpb_max (channels per channelwise workgroup, <= 16),
  *   pw6_min_m (smallest output-channel count the whole-K forward kernel takes), pw_two_tiles_k (padded K from which a wave
- *   of the whole-K kernels takes two M tiles of one staged tile).
+ *   of the whole-K kernels takes two M tiles of one staged tile), no_pw8 (the persistent producer / consumer forward
+ *   kernel pw8 off), pw8_grid (its workgroups; 0 = one per CU), pw8_max_k (largest padded K it takes), no_se_bwd_merge
+ *   (separate SE backward launches instead of the merged kernel), pw_waves16 (16-wave workgroups for the whole-K kernels:
+ *   0 never, 1 the K >= 320 layers, 2 also layers with more than 16 M tiles, 3 also from 9 tiles), dw_tquad_wgs
+ *   (channelwise launches whose two-segment form has at most this many workgroups cut the T march into four segments;
+ *   0 = never; backward kernel), dw_tquad_wgs_fwd (the same for the forward kernel).
  * Unknown name or out-of-range value: X3D_EINVAL. */
 int x3d_set_option(const char* name, int value);
 int x3d_get_option(const char* name, int* value);
@@ -406,28 +411,6 @@ int x3d_grad_accumulate(float* acc, const float* g, size_t n, float scale, int f
  * m = first ? g : mu*m + g; w -= lr*m.  grad_scale multiplies g first (1/world_size). */
 int x3d_sgd_fused(float* w, const float* g, float* m, size_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, int first, void* stream);
-
-/* ------------------------------------------------------------------------------------
- * GPU-side clip input pipeline.  Replaces, per sample, the CPU work of
- * kinetics_multigrid.py:240-253 on decoded uint8 frames: frame selection (TemporalRandomCrop,
- * transforms/temporal_transforms.py:94-117 -- indices computed by the host), crop + PIL bilinear
- * resize (MultiScaleRandomCropMultigrid, transforms/spatial_transforms.py:480-495), horizontal flip
- * (:334-346), ToTensor(255) + Normalize (:44-83,106-116), stack/permute to [3][T][S][S].
- * Bit-exact with Pillow's 8-bit bilinear resample given the host-built coefficient table
- * (x3dhip/clip_input.py:resize_coeffs = Resample.c precompute_coeffs + normalize_coeffs_8bpc).
- * `jobs`: device array of X3DClipJob, one per sample; all pointers are device pointers. */
-typedef struct {
-    const unsigned char* src;   /* [Tsrc][Hs][Ws][3] decoded frames */
-    unsigned char* tmp;         /* scratch [T][crop][out][3] */
-    float* dst;                 /* [3][T][out][out]: the sample's slice of the NCTHW batch */
-    const int* kk;              /* [out][ksize] 22-bit fixed-point coefficients */
-    const int* bounds;          /* [out][2] (first input index, tap count) */
-    const int* frames;          /* [T] 0-based source frame per output frame */
-    int Hs, Ws, x1, y1, crop, out, ksize, T, flip, pad;
-} X3DClipJob;
-size_t x3d_clip_job_bytes(void);
-int x3d_clip_preprocess(const void* jobs, int njobs, int max_T, int max_crop, int max_out,
-                        const float* mean3, const float* std3, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,8 @@ def test_library_loads_and_exports_every_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r"\bT (x3d_[a-z0-9_]+)", out))
     assert set(_header_functions()) <= exported
+    # the clip input kernels live in libx3ddata.so alone (ABI 8)
+    assert not {"x3d_clip_preprocess", "x3d_clip_job_bytes"} & exported
     # pure host-side helpers are callable without a GPU
     assert h.x3d_pw_tiles(1, 24, 54, 1000, 1) == 16 and h.x3d_pw_tiles(64, 24, 54, 100000, 1) == 391
     assert h.x3d_pw_tiles(8, 216, 96, 3136, 1) == 49

@@ -1,5 +1,6 @@
-"""GPU clip input pipeline (csrc/clip.hip through the C ABI) against the goldens of the reference's transforms and
-against the oracle on further shapes: bit-exact (uint8 resample) and exact fp32 normalisation."""
+"""GPU clip input pipeline (clip_input.ClipPreprocessor over the clip kernels of libx3ddata.so) against the goldens of
+the reference's transforms and against the oracle on further shapes: bit-exact (uint8 resample) and exact fp32
+normalisation."""
 import glob
 import os
 
@@ -35,8 +36,10 @@ def test_golden_clips(path):
     assert np.array_equal(got, g["clip"]), "max abs diff %g" % np.abs(got - g["clip"]).max()
 
 
-def test_batch_of_mixed_crops_matches_oracle():
-    """one launch, 5 samples with different source sizes / crops / flips (incl. upscaling and a 1-pixel-margin crop)"""
+@pytest.mark.parametrize("preallocated", [False, True], ids=["fresh", "out"])
+def test_batch_of_mixed_crops_matches_oracle(preallocated):
+    """one launch, 5 samples with different source sizes / crops / flips (incl. upscaling and a 1-pixel-margin crop);
+    with out= a NaN-filled [5, 3, 6, 40, 40] tensor as well: every element is written, each sample to its own slice"""
     from x3dhip import clip_input as ci
     dev = _dev()
     rng = np.random.default_rng(5)
@@ -49,8 +52,14 @@ def test_batch_of_mixed_crops_matches_oracle():
         idx = [int(v) for v in rng.integers(0, n, size=T)]
         samples.append((torch.from_numpy(fr).to(dev), dict(frame_idx=idx, x1=x1, y1=y1, crop=crop, out=S, flip=bool(flip))))
         expect.append(io.clip(fr, idx, x1, y1, crop, S, bool(flip)))
-    out = ci.ClipPreprocessor(dev)(samples)
+    if preallocated:
+        given = torch.full((5, 3, T, S, S), float("nan"), dtype=torch.float32, device=dev)
+        out = ci.ClipPreprocessor(dev)(samples, out=given)
+        assert out is given
+    else:
+        out = ci.ClipPreprocessor(dev)(samples)
     torch.cuda.synchronize()
+    assert not torch.isnan(out).any()
     for b, e in enumerate(expect):
         assert np.array_equal(out[b].cpu().numpy(), e), (b, np.abs(out[b].cpu().numpy() - e).max())
 
@@ -64,6 +73,9 @@ def test_rejects_bad_boxes():
         pre([(fr, dict(frame_idx=[0, 1], x1=20, y1=0, crop=20, out=8, flip=False))])
     with pytest.raises(ValueError):
         pre([(fr, dict(frame_idx=[0, 4], x1=0, y1=0, crop=20, out=8, flip=False))])
+    with pytest.raises(ValueError):                 # all samples of a step share T
+        pre([(fr, dict(frame_idx=[0, 1], x1=0, y1=0, crop=20, out=8, flip=False)),
+             (fr, dict(frame_idx=[0, 1, 2], x1=0, y1=0, crop=20, out=8, flip=False))])
 
 
 def test_device_video_dataset_protocol():

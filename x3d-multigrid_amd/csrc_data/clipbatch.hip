@@ -1,11 +1,13 @@
-// Variable-length clip batches of the Charades dataset (charades.py:139,145-157 and custom_collate_fn :167-189) over
-// decoded uint8 frames resident in HBM: crop, Pillow's 8-bit bilinear resample, optional flip, ToTensor(255), Normalize,
-// each sample into its slice of a padded batch (the tail written as +0.0f here, not by a memset) or into the windows of
-// a multi-window testing batch (a frame resized once and stored to every window that holds it).
+// The clip kernels of every input path: the fixed-length batches of the Kinetics dataset (kinetics_multigrid.py:240-253,
+// through clip_input.ClipPreprocessor) and the variable-length ones of the Charades dataset (charades.py:139,145-157 and
+// custom_collate_fn :167-189), over decoded uint8 frames resident in HBM: crop, Pillow's 8-bit bilinear resample,
+// optional flip, ToTensor(255), Normalize, each sample into its slice of a batch, padded where the job asks for it (the
+// tail written as +0.0f here, not by a memset), or into the windows of a multi-window testing batch (a frame resized once
+// and stored to every window that holds it).
 //
-// The resample is a second copy of the arithmetic of csrc/clip.hip (about 60 lines), on purpose: csrc/ is hashed by
-// tools/stamp.csrc_sha16() and the gradient-hash record is keyed on that hash, so nothing may be added to it or shared
-// out of it.  Bit-exact with Pillow (libImaging/Resample.c): separable, horizontal pass first into
+// This is the only copy of the resample.  It lives here and not in csrc/ because nothing that runs outside a training
+// step goes into the sources that tools/stamp.csrc_sha16() hashes and the gradient-hash record is keyed on (DESIGN.md
+// section 7).  Bit-exact with Pillow (libImaging/Resample.c): separable, horizontal pass first into
 // a uint8 intermediate, 22-bit fixed-point coefficient tables built on the host (clip_input.resize_coeffs), round half
 // up, clip to [0, 255].  The intermediate lives in caller-provided HBM scratch: the rounding to uint8 between the passes
 // is what makes the result Pillow's, and the plain two-pass form is the only one.

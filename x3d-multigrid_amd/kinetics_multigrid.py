@@ -48,7 +48,8 @@ class DeviceVideoKinetics:
     """Kinetics.__getitem__'s protocol (kinetics_multigrid.py:214-259) over decoded uint8 videos that are already
     resident in HBM: the per-sample random draws happen on the host in the reference's order
     (x3dhip.clip_input.draw_clip_params), and crop + PIL-bilinear resize + flip + ToTensor + Normalize + the
-    [3,T,H,W] stacking run as two HIP kernels for the whole batch (x3dhip.clip_input.ClipPreprocessor).
+    [3,T,H,W] stacking run as two HIP kernels for the whole batch (x3dhip.clip_input.ClipPreprocessor over the clip
+    kernels of libx3ddata.so).
 
     videos: list of uint8 CUDA tensors [n_frames, H, W, 3]; labels: list of ints.  ``batch(indices, iteration,
     long_cycle_state)`` returns (clips float32 [B,3,T,S,S], labels int64 [B,1], long_cycle_state, stats)."""

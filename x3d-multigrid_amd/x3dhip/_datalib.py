@@ -1,4 +1,5 @@
-"""ctypes binding of libx3ddata.so (include/x3ddata.h): the Charades input kernels (per-frame labels, clip batches).
+"""ctypes binding of libx3ddata.so (include/x3ddata.h): the input kernels (clip batches of both datasets, Charades per-frame
+labels).
 
 Same discipline as _lib.py: the library is mandatory, torch is imported before it is loaded, the ABI version is checked,
 and a failing entry point raises X3DHipError with the library's message.
@@ -48,7 +49,7 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise X3DHipError(
             "libx3ddata.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(or `make -C x3d-multigrid_amd/csrc_data`). The Charades input path has no fallback." % LIB_PATH)
+            "(or `make -C x3d-multigrid_amd/csrc_data`). The input path has no fallback." % LIB_PATH)
     import torch  # noqa: F401  (its HIP runtime first: see _lib.lib)
     h = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libx3dhip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 ACT_NONE, ACT_RELU, ACT_SWISH = 0, 1, 2
 
@@ -25,8 +25,6 @@ SIGNATURES = {
     "x3d_abi_version": (_I, []),
     "x3d_dw333_fwd_stats": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _I, _P, _I, _P]),
     "x3d_bn_stats_add_relu_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "x3d_clip_job_bytes": (_Z, []),
-    "x3d_clip_preprocess": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "x3d_last_error": (ctypes.c_char_p, []),
     "x3d_last_kernel": (ctypes.c_char_p, []),
     "x3d_debug_poison_lds": (_I, [_P, _P]),

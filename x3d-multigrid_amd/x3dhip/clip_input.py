@@ -1,5 +1,6 @@
-"""Host side of the GPU clip input pipeline (csrc/clip.hip): the integer/random logic of the reference's
-per-sample transforms and the job tables for x3d_clip_preprocess.
+"""Host side of the GPU clip input pipeline: the integer/random logic of the reference's per-sample transforms, the
+resample coefficient tables, and ClipPreprocessor, which hands a Kinetics step's samples to dataops.ClipBatcher (the
+clip kernels of csrc_data/clipbatch.hip, libx3ddata.so).
 
 Reference call sites mirrored (random draws in the reference's order, from Python's `random` like the reference):
   kinetics_multigrid.py:240-253 (__getitem__), transforms/temporal_transforms.py:94-117 (TemporalRandomCrop),
@@ -11,8 +12,6 @@ import random as _random
 
 import numpy as np
 import torch
-
-from . import _lib
 
 PRECISION_BITS = 32 - 8 - 2
 KINETICS_MEAN = [110.63666788 / 255, 103.16065604 / 255, 96.29023126 / 255]      # train_x3d_kinetics_multigrid.py:45
@@ -110,62 +109,27 @@ def resize_coeffs(in_size, out_size):
     return out
 
 
-_JOB_DT = np.dtype([("src", "<u8"), ("tmp", "<u8"), ("dst", "<u8"), ("kk", "<u8"), ("bounds", "<u8"), ("frames", "<u8"),
-                    ("Hs", "<i4"), ("Ws", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("crop", "<i4"), ("out", "<i4"),
-                    ("ksize", "<i4"), ("T", "<i4"), ("flip", "<i4"), ("pad", "<i4")])
-
-
 class ClipPreprocessor:
-    """Turns decoded uint8 videos resident on the GPU into the normalised float NCTHW batch of one training step.
+    """Turns decoded uint8 videos resident on the GPU into the normalised float NCTHW batch of one training step: an
+    adapter that lays the samples out for dataops.ClipBatcher (one job table, one scratch buffer, two launches).
 
     samples: list of (frames uint8 CUDA tensor [Tsrc, H, W, 3], params dict from draw_clip_params); all samples of
     a step share T and the output size (the multigrid schedule fixes both per step)."""
 
     def __init__(self, device, mean=KINETICS_MEAN, std=KINETICS_STD):
+        from .dataops import ClipBatcher          # dataops imports resize_coeffs from this module
         self.device = torch.device(device)
-        self.mean = np.asarray(mean, dtype=np.float32)
-        self.std = np.asarray(std, dtype=np.float32)
-        self._tables = {}
-        assert _lib.lib().x3d_clip_job_bytes() == _JOB_DT.itemsize
-
-    def _table(self, crop, out):
-        key = (crop, out)
-        hit = self._tables.get(key)
-        if hit is None:
-            kk, bounds, ksize = resize_coeffs(crop, out)
-            hit = (torch.from_numpy(kk).to(self.device), torch.from_numpy(bounds).to(self.device), ksize)
-            self._tables[key] = hit
-        return hit
+        self._batcher = ClipBatcher(self.device, mean, std)
 
     def __call__(self, samples, out=None):
-        L = _lib.lib()
         B = len(samples)
         T = len(samples[0][1]["frame_idx"])
         S = samples[0][1]["out"]
         batch = out if out is not None else torch.empty((B, 3, T, S, S), dtype=torch.float32, device=self.device)
-        jobs = np.zeros(B, dtype=_JOB_DT)
-        keep = []
-        max_crop = 0
+        jobs = []
         for b, (frames, p) in enumerate(samples):
-            if frames.device != self.device or frames.dtype != torch.uint8 or not frames.is_contiguous():
-                raise ValueError("frames must be contiguous uint8 tensors on %s" % self.device)
             if len(p["frame_idx"]) != T or p["out"] != S:
                 raise ValueError("all samples of a step share T and the output size")
-            Tsrc, Hs, Ws, C = frames.shape
-            if C != 3 or p["crop"] <= 0 or p["x1"] < 0 or p["y1"] < 0 or p["x1"] + p["crop"] > Ws or p["y1"] + p["crop"] > Hs:
-                raise ValueError("crop box outside the frame")
-            if min(p["frame_idx"]) < 0 or max(p["frame_idx"]) >= Tsrc:
-                raise ValueError("frame index outside the video")
-            kk, bounds, ksize = self._table(p["crop"], S)
-            fidx = torch.tensor(p["frame_idx"], dtype=torch.int32, device=self.device)
-            tmp = torch.empty((T, p["crop"], S, 3), dtype=torch.uint8, device=self.device)
-            keep += [fidx, tmp]
-            jobs[b] = (frames.data_ptr(), tmp.data_ptr(), batch[b].data_ptr(), kk.data_ptr(), bounds.data_ptr(),
-                       fidx.data_ptr(), Hs, Ws, p["x1"], p["y1"], p["crop"], S, ksize, T, 1 if p["flip"] else 0, 0)
-            max_crop = max(max_crop, p["crop"])
-        jd = torch.from_numpy(jobs.view(np.uint8).copy()).to(self.device)
-        _lib.check(L.x3d_clip_preprocess(jd.data_ptr(), B, T, max_crop, S, self.mean.ctypes.data, self.std.ctypes.data,
-                                         _lib.stream()))
-        for t in keep + [jd]:
-            t.record_stream(torch.cuda.current_stream())
-        return batch
+            jobs.append(dict(frames=frames, frame_idx=p["frame_idx"], x1=p["x1"], y1=p["y1"], crop=p["crop"],
+                             flip=p["flip"], dst_off=b * 3 * T * S * S, dst_cs=T * S * S, dst_ts=S * S))
+        return self._batcher(batch, jobs, S)

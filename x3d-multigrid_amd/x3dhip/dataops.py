@@ -1,4 +1,4 @@
-"""Tensor-level wrappers over the Charades input C ABI (include/x3ddata.h), in the style of evalops.py.
+"""Tensor-level wrappers over the input C ABI (include/x3ddata.h), in the style of evalops.py.
 
 Shapes, dtypes, devices, crop boxes and frame indices are checked here, on the host, before anything is launched (the
 messages follow clip_input.py).  Every launch goes to the current stream.  There is no fallback: a CPU tensor raises.
