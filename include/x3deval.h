@@ -1,7 +1,8 @@
 /*
  * x3deval.h -- C ABI of libx3deval.so: HIP kernels (gfx950 / MI355X) of the evaluation path, a device-resident
- * average-precision meter (the reference's apmeter.APMeter, apmeter.py:98-136) and the appends of the two Charades scripts
- * (train_x3d_charades.py:150-183, train_x3d_charades_loc.py:152-186).
+ * average-precision meter (the reference's apmeter.APMeter, apmeter.py:98-136), the appends of the two Charades scripts
+ * (train_x3d_charades.py:150-183, train_x3d_charades_loc.py:152-186) and a top-k classification meter (the Kinetics
+ * validation, train_x3d_kinetics_multigrid.py:253-265).
  *
  * A separate library from libx3dhip.so on purpose: tools/stamp.py and the gradient-hash record hash the training library's
  * sources, and the meter never runs inside a training step.
@@ -31,7 +32,7 @@
 extern "C" {
 #endif
 
-#define X3DEVAL_ABI_VERSION 1
+#define X3DEVAL_ABI_VERSION 2
 
 #define X3DEVAL_OK 0
 #define X3DEVAL_EINVAL (-1)   /* bad shape / null pointer / unsupported size */
@@ -44,10 +45,13 @@ extern "C" {
 #define X3DEVAL_S_BAD 3       /* sticky: a non-binary target or a negative / NaN weight */
 #define X3DEVAL_S_BASE 4      /* first row of the append in flight */
 #define X3DEVAL_S_GO 5        /* 1 when the append in flight fits */
+#define X3DEVAL_S_BATCHES 6   /* classification meter: append calls that fitted */
 #define X3DEVAL_STATE_INTS 8
 
 #define X3DEVAL_MAX_CAPACITY 0x7fffffc0   /* row indices are 31-bit in the sort payload */
 #define X3DEVAL_MAX_FRAMES_B 1024         /* samples per x3deval_ap_append_frames call */
+#define X3DEVAL_CLS_MAX_K 4096            /* classes of the classification meter */
+#define X3DEVAL_CLS_MAX_CROPS 32          /* crops per video of x3deval_cls_append_crops */
 
 int x3deval_abi_version(void);
 const char* x3deval_last_error(void);
@@ -83,6 +87,37 @@ size_t x3deval_ap_workspace_bytes(int K, int capacity);
  * tp_i = positives up to i, or their weighted sums.  workspace: x3deval_ap_workspace_bytes(K, capacity) bytes. */
 int x3deval_ap_value(const int* state, const float* scores, const uint8_t* targets, const float* weights, int K,
                      int capacity, void* workspace, size_t workspace_bytes, float* ap, void* stream);
+
+/*
+ * The classification (top-k) meter: the validation arithmetic of train_x3d_kinetics_multigrid.py:253-265, 293-295.
+ * The state is the AP meter's (x3deval_ap_reset / x3deval_ap_set_capacity operate on it; X3DEVAL_S_BATCHES counts the
+ * append calls that fitted).  One row per video, in five caller-owned arrays of `capacity` elements:
+ *   loss fp32, rank int32, pred int32, label int32, batch_rows int32
+ *
+ * x3deval_cls_append_crops: logits fp32 [b * n_crops, K] (crops of a video adjacent), labels int64 [b].  Per video, in
+ * fp64 from the fp32 logits:
+ *   s[k] = mean over crops of softmax_k(logits[crop]);  m[k] = mean over crops of logits[crop][k]
+ *   loss = logsumexp(m) - m[label], rounded to fp32 once
+ *   pred = index of the largest s, the lowest index among equals
+ *   rank = #{k : s[k] > s[label]} + #{k < label : s[k] == s[label]}      (top-k correct iff rank < k)
+ *   s[label] NaN (s is then NaN in every class): rank = K, pred = -1; loss is what the arithmetic gives
+ *   label outside [0, K): rank = K, loss = NaN, X3DEVAL_S_BAD is set
+ *   batch_rows = b for every row of the call
+ * An append that would pass the device capacity writes nothing and sets X3DEVAL_S_OVERFLOW.
+ * K <= X3DEVAL_CLS_MAX_K and n_crops <= X3DEVAL_CLS_MAX_CROPS, X3DEVAL_EINVAL beyond.
+ */
+int x3deval_cls_append_crops(int* state, float* loss, int* rank, int* pred, int* label, int* batch_rows, int K,
+                             const float* logits, const int64_t* labels, int b, int n_crops, void* stream);
+
+/* Totals over the rows, the same bits run to run (one workgroup, sums in a fixed order; integer atomics for the
+ * histograms only).  capacity: elements of the row arrays.
+ *   totals         int64 [4]  rows, top-1 correct (rank == 0), top-kmax correct (rank < kmax), batches
+ *   loss_sums      fp64  [2]  sum_i loss_i, sum_i loss_i / batch_rows_i   (the latter / batches = the mean of batch means)
+ *   class_correct  int32 [K]  top-1 correct rows per label;  class_count int32 [K] rows per label
+ * While a sticky flag is set: totals = -1, loss_sums = NaN, histograms 0.  pred is not read (it may be NULL). */
+int x3deval_cls_value(const int* state, const float* loss, const int* rank, const int* pred, const int* label,
+                      const int* batch_rows, int K, int capacity, int kmax, int64_t* totals, double* loss_sums,
+                      int* class_correct, int* class_count, void* stream);
 
 #ifdef __cplusplus
 }

@@ -34,18 +34,6 @@ __device__ __forceinline__ unsigned desc_key(float f) {
     return ~asc;
 }
 
-__device__ __forceinline__ void reserve_rows(int* state, long long n) {
-    const long long c = state[X3DEVAL_S_COUNT], cap = state[X3DEVAL_S_CAPACITY];
-    if (c + n > cap) {
-        state[X3DEVAL_S_OVERFLOW] = 1;
-        state[X3DEVAL_S_GO] = 0;
-    } else {
-        state[X3DEVAL_S_BASE] = (int)c;
-        state[X3DEVAL_S_COUNT] = (int)(c + n);
-        state[X3DEVAL_S_GO] = 1;
-    }
-}
-
 __global__ void ap_state_kernel(int* state, int capacity, int reset) {
     if (threadIdx.x != 0) return;
     if (reset)

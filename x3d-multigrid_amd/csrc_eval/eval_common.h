@@ -26,3 +26,16 @@ void x3deval_set_error(const char* fmt, ...);
     } while (0)
 
 __host__ __device__ static inline int eval_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// The reservation of an append (one thread): publishes the base row and advances the count, or sets the overflow flag.
+__device__ static inline void reserve_rows(int* state, long long n) {
+    const long long c = state[X3DEVAL_S_COUNT], cap = state[X3DEVAL_S_CAPACITY];
+    if (c + n > cap) {
+        state[X3DEVAL_S_OVERFLOW] = 1;
+        state[X3DEVAL_S_GO] = 0;
+    } else {
+        state[X3DEVAL_S_BASE] = (int)c;
+        state[X3DEVAL_S_COUNT] = (int)(c + n);
+        state[X3DEVAL_S_GO] = 1;
+    }
+}

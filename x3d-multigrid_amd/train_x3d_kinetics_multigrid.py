@@ -144,6 +144,32 @@ def validate(model, batches):
     return tot_cls_loss / max(num_iter, 1), tot_corr / max(tot_dat, 1), tot_dat
 
 
+def validate_topk(model, batches, meter=None, process_group=None):
+    """The same validation phase scored by the device-resident topkmeter.TopKMeter: eval mode,
+    `aggregate_sub_bn_stats()` first, no gradients, one `add_logits` per batch and no host synchronisation inside the
+    loop.  Returns the meter's value() dict ("videos", "top1", "top5", "cls_loss", "loss_per_video", "class_acc",
+    "mean_class_acc"); with a process_group every rank scores its own batches and the raw totals are summed over the
+    ranks (topkmeter.reduce_totals), so every rank returns the figures of the whole set.  The model is left in eval
+    mode."""
+    import topkmeter
+    meter = topkmeter.TopKMeter() if meter is None else meter
+    model.train(False)
+    model.aggregate_sub_bn_stats()
+    with torch.no_grad():
+        for inputs, labels in batches:
+            b, n, c, t, h, w = inputs.shape
+            meter.add_logits(model(inputs.view(b * n, c, t, h, w)), labels, n_crops=n)
+    if process_group is not None:
+        return topkmeter.reduce_totals(meter.totals(check=False), process_group)     # a failed meter: all ranks raise
+    return meter.value()
+
+
+def val_line(res):
+    """The reference's validation line (train_x3d_kinetics_multigrid.py:294) extended with top-5."""
+    return 'Cls Loss: {:.4f} Acc: {:.4f} Top5: {:.4f} ({} videos)'.format(res['cls_loss'], res['top1'], res['top5'],
+                                                                          res['videos'])
+
+
 def _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps):
     """The reference's checkpoint record (train_x3d_kinetics_multigrid.py:286-291)."""
     ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
@@ -156,13 +182,16 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
-        frames_root=None):
+        frames_root=None, val_frames=None):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8]) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
     sizes); each step's samples are drawn by a sampler seeded per rank, its clips come from FolderKinetics.batch.  val_every: run the
     validation phase (`validate`, the reference does it after every 4 training epochs, :195) every that many steps on
-    `val_batches` synthetic batches of [val_batch_size, val_crops, 3, T, H, W].
+    `val_batches` synthetic batches of [val_batch_size, val_crops, 3, T, H, W]; or, with val_frames -- a
+    dict(root=, anno=, labels=[, subset='validate', threads=8]) for kinetics.Kinetics, or a ready instance -- on the
+    frame folders of the validation set: every video once, val_crops temporal windows each, in batches of val_batch_size,
+    sharded over the ranks and scored by `validate_topk` (top-1, top-5 and the loss, reduced over the ranks).
     num_steps_per_update: gradient accumulation over that many micro-batches per optimizer step (train...:119,267-273;
     the schedule then counts iterations and lr_schedule is divided by it, :130).  clip_size overrides the crop size of
     the shape table (tests: the default batch arithmetic at a tiny resolution)."""
@@ -238,6 +267,16 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         # the DataLoader task index of each step (the short-cycle counter): the same state machine as `shapes`
         sched, _ = lr_schedule_milestones(int(max_epochs * iterations_per_epoch))
         tasks = cbs.MultigridSchedule(batch_size, sched, steps * num_steps_per_update, LONG_CYCLE).steps()
+    val_ds = None
+    if val_frames is not None:
+        import kinetics
+        if isinstance(val_frames, dict):
+            kw = dict(val_frames)
+            val_ds = kinetics.Kinetics(kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'validate'),
+                                       sample_duration=frames, gamma_tau=gamma_tau, crops=val_crops,
+                                       crop_size=clip_size or crop_size, device=dev, **kw)
+        else:
+            val_ds = val_frames
     tot_loss = tot_corr = tot_dat = 0.0
     t0 = time.time()
     clips = 0
@@ -290,7 +329,12 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                     dt = time.time() - t0
                     print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s'.format(
                         steps, long_ind, B, T, H, tot_loss, acc, optimizer.param_groups[0]['lr'], clips / dt), flush=True)
-            if val_every and done % val_every == 0:
+            if val_every and done % val_every == 0 and val_ds is not None:
+                res = validate_topk(model, val_ds.batches(val_batch_size, rank, world), process_group=pg)
+                model.train(True)                                   # train...:199-200
+                if rank == 0:
+                    print(' val after step {}: {}'.format(steps, val_line(res)), flush=True)
+            elif val_every and done % val_every == 0:
                 Tv, Hv = frames // gamma_tau, crop_size
                 vb = []
                 for _ in range(val_batches):
@@ -332,6 +376,12 @@ if __name__ == '__main__':
     parser.add_argument('--frames-root', default=None, help='root of the folders of frame_%%05d.jpg (with --anno and --labels)')
     parser.add_argument('--anno', default=None, help='Kinetics annotation json of the reference')
     parser.add_argument('--labels', default=None, help='class list, one name per line')
+    parser.add_argument('--val-frames-root', default=None, help='frame folders of the validation set (with --val-anno and '
+                        '--labels): the validation phase scores them instead of synthetic clips')
+    parser.add_argument('--val-anno', default=None, help='annotation json of the validation set')
+    parser.add_argument('--val-every', type=int, default=None, help='validate every that many steps')
+    parser.add_argument('--val-batch', type=int, default=2, help='videos per validation batch and rank')
+    parser.add_argument('--val-crops', type=int, default=3, help='temporal windows per validation video')
     parser.add_argument('--decode-threads', type=int, default=8, help='host threads of the JPEG entropy stage (1..16)')
     args = parser.parse_args()
     frames_root = None
@@ -339,10 +389,16 @@ if __name__ == '__main__':
         if args.anno is None or args.labels is None:
             parser.error('--frames-root needs --anno and --labels')
         frames_root = dict(root=args.frames_root, anno=args.anno, labels=args.labels, threads=args.decode_threads)
+    val_frames = None
+    if args.val_frames_root is not None:
+        if args.val_anno is None or args.labels is None:
+            parser.error('--val-frames-root needs --val-anno and --labels')
+        val_frames = dict(root=args.val_frames_root, anno=args.val_anno, labels=args.labels, threads=args.decode_threads)
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     run(init_lr=(1.6 / 1024) * args.batch, warmup_steps=args.warmup_steps, max_epochs=args.max_epochs,
         batch_size=args.batch, steps=args.start_step, max_steps_run=args.steps,
         iterations_per_epoch=args.iters_per_epoch, load_ckpt=args.load, save_every=args.save_every,
         use_graph=not args.no_graph, x3d_version=args.version,
-        act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root)
+        act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root, val_every=args.val_every,
+        val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames)

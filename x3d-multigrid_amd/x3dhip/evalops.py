@@ -139,3 +139,57 @@ def ap_value(state, scores, targets, weights=None, workspace=None):
     check(_evallib.lib().x3deval_ap_value(ptr(state), ptr(scores), ptr(targets), ptr(weights), K, cap, ptr(workspace),
                                           workspace.numel(), ptr(ap), stream()))
     return ap
+
+
+def cls_rows(dev, capacity):
+    """The row arrays of a classification meter: (loss fp32, rank, pred, label, batch_rows int32), each [capacity]."""
+    return (torch.zeros(capacity, dtype=torch.float32, device=dev),) + \
+        tuple(torch.zeros(capacity, dtype=torch.int32, device=dev) for _ in range(4))
+
+
+def _rows(state, rows):
+    _need("state", state, torch.int32, 1)
+    if len(rows) != 5:
+        raise X3DHipError("a classification meter has five row arrays (loss, rank, pred, label, batch_rows)")
+    for name, t, dtype in zip(("loss", "rank", "pred", "label", "batch_rows"), rows, (torch.float32,) + (torch.int32,) * 4):
+        _need(name + " rows", t, dtype, 1)
+        if t.shape[0] != rows[0].shape[0]:
+            raise X3DHipError("row arrays of different lengths")
+    _same_device(state, *rows)
+    return rows[0].shape[0]
+
+
+def cls_append_crops(state, rows, logits, labels, n_crops):
+    """One batch of the Kinetics validation (include/x3deval.h): logits [b * n_crops, K] float32 (a video's crops adjacent),
+    labels [b] int64.  Appends one row per video to `rows` (cls_rows)."""
+    _rows(state, rows)
+    _need("logits", logits, torch.float32, 2)
+    _need("labels", labels, torch.int64, 1)
+    n_crops = int(n_crops)
+    K = logits.shape[1]
+    if n_crops < 1 or n_crops > _evallib.CLS_MAX_CROPS or logits.shape[0] % n_crops != 0 or logits.shape[0] == 0:
+        raise X3DHipError("cls_append_crops: logits must be [b * n_crops, K] with 1 <= n_crops <= %d (got %s, n_crops %d)"
+                          % (_evallib.CLS_MAX_CROPS, tuple(logits.shape), n_crops))
+    if K < 1 or K > _evallib.CLS_MAX_K:
+        raise X3DHipError("cls_append_crops: %d classes, the meter takes 1..%d" % (K, _evallib.CLS_MAX_K))
+    b = logits.shape[0] // n_crops
+    if labels.shape[0] != b:
+        raise X3DHipError("cls_append_crops: labels must be [%d] (got %s)" % (b, tuple(labels.shape)))
+    _same_device(state, logits, labels)
+    check(_evallib.lib().x3deval_cls_append_crops(ptr(state), *[ptr(r) for r in rows], K, ptr(logits), ptr(labels), b,
+                                                  n_crops, stream()))
+
+
+def cls_value(state, rows, K, kmax):
+    """(totals int64 [4], loss_sums float64 [2], class_correct int32 [K], class_count int32 [K]) on the device, without a
+    synchronisation: rows / top-1 correct / top-kmax correct / batches, sum of the losses / sum of loss_i / batch_rows_i,
+    the per-class top-1 histograms.  totals = -1 and loss_sums = NaN while a sticky flag is set."""
+    cap = _rows(state, rows)
+    dev = state.device
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    loss_sums = torch.empty(2, dtype=torch.float64, device=dev)
+    correct = torch.empty(int(K), dtype=torch.int32, device=dev)
+    count = torch.empty(int(K), dtype=torch.int32, device=dev)
+    check(_evallib.lib().x3deval_cls_value(ptr(state), *[ptr(r) for r in rows], int(K), cap, int(kmax), ptr(totals),
+                                           ptr(loss_sums), ptr(correct), ptr(count), stream()))
+    return totals, loss_sums, correct, count
