@@ -24,6 +24,14 @@
  * padded to whole MCUs, the components one after the other (coef_off).  Planes: uint8, per component
  * [blocks_h * 8][blocks_w * 8], the components one after the other: block b of a frame has its coefficients at element
  * 64 * b and its component's plane starts at byte 64 * block_start.
+ *
+ * Huffman decoding has two paths that fill the same coefficient buffer bit for bit.  x3djpeg_entropy_decode is the serial
+ * host decoder.  The device path: x3djpeg_scan_prepare (host, one pass over the file) removes the byte stuffing and the
+ * restart markers and cuts the scan into one segment per restart interval; x3djpeg_entropy_decode_batch decodes a batch,
+ * one workgroup per frame, by many decoders that start at fixed bit offsets (every sub_bits bits of a segment) and are
+ * relaxed until each starts in the state its predecessor ended in (JPEG Huffman streams self-synchronise; Weissenberger
+ * & Schmidt, "Accelerating JPEG decompression on GPUs").  x3djpeg_entropy_decode_parallel_host runs the same scheme
+ * through the same code (csrc_jpeg/entropy_core.h) serially on the CPU.
  */
 #ifndef X3DJPEG_H
 #define X3DJPEG_H
@@ -35,7 +43,7 @@
 extern "C" {
 #endif
 
-#define X3DJPEG_ABI_VERSION 1
+#define X3DJPEG_ABI_VERSION 2
 
 #define X3DJPEG_OK 0
 #define X3DJPEG_EINVAL (-1)        /* bad shape / null pointer / buffer too small */
@@ -77,10 +85,38 @@ typedef struct X3DJpegFrameJob {
     uint16_t qt[3][64];    /* per component, natural order */
 } X3DJpegFrameJob;
 
+/* One restart interval of a prepared scan (a file without DRI has one).  Its bit length is 8 * byte_len: the decoder
+ * ignores the pad bits of the last byte. */
+typedef struct X3DJpegScanSeg {
+    uint32_t byte_off, byte_len;   /* in the frame's unstuffed scan bytes */
+    int32_t first_mcu, mcu_count;
+} X3DJpegScanSeg;
+
+#define X3DJPEG_SCAN_PAD 16               /* zero bytes x3djpeg_scan_prepare appends to the unstuffed scan */
+#define X3DJPEG_SCAN_MAX_BYTES (1 << 27)  /* largest scan the parallel path takes: bit positions stay below 2^30 */
+#define X3DJPEG_SUB_BITS_DEFAULT 1024     /* profiles/jpeg_entropy/README.md */
+
+/* One frame of a batch of x3djpeg_entropy_decode_batch, on the device (host pointers for ..._parallel_host). */
+typedef struct X3DJpegScanJob {
+    const uint8_t* scan;           /* what x3djpeg_scan_prepare wrote: scan_bytes bytes and X3DJPEG_SCAN_PAD zeros */
+    const X3DJpegScanSeg* segs;    /* nseg entries */
+    int16_t* coef;                 /* the frame's coefficients (coef_count elements), written in full */
+    int64_t coef_count;
+    int64_t ws_off, ws_bytes;      /* the frame's part of the workspace: ws_off a multiple of 16, ws_bytes at least
+                                      x3djpeg_entropy_workspace_bytes(scan_bytes, nseg, sub_bits) */
+    int32_t scan_bytes, nseg;
+    int32_t ncomp, mcus_x, mcus_y, restart_interval;
+    int32_t comp_h[3], comp_v[3], comp_td[3], comp_ta[3], blocks_w[3], block_start[3];
+    uint8_t huff_bits[8][16];      /* as in X3DJpegInfo */
+    uint8_t huff_vals[8][256];
+} X3DJpegScanJob;
+
 int x3djpeg_abi_version(void);
 const char* x3djpeg_last_error(void);
 size_t x3djpeg_info_bytes(void);
 size_t x3djpeg_frame_job_bytes(void);
+size_t x3djpeg_scan_seg_bytes(void);
+size_t x3djpeg_scan_job_bytes(void);
 
 /* Host stage. */
 int x3djpeg_parse(const uint8_t* bytes, size_t len, X3DJpegInfo* info);
@@ -88,7 +124,31 @@ int x3djpeg_parse(const uint8_t* bytes, size_t len, X3DJpegInfo* info);
  * (info->coef_count int16, zero-filled first).  coef_bytes < 2 * coef_count is X3DJPEG_EINVAL. */
 int x3djpeg_entropy_decode(const uint8_t* bytes, size_t len, const X3DJpegInfo* info, int16_t* coef, size_t coef_bytes);
 
-/* Device stage.  jobs: X3DJpegFrameJob [njobs] on the device; max_blocks, max_w, max_h: the maxima of nblocks, width and
+/* The host's part of the device path: copies the entropy-coded data of the scan `info` describes into scan[0, scan_cap)
+ * with the byte stuffing (FF 00 -> FF) and the restart markers removed, X3DJPEG_SCAN_PAD zero bytes after it, and writes
+ * one X3DJpegScanSeg per restart interval into segs[0, seg_cap).  Markers are handled as x3djpeg_entropy_decode does:
+ * fill FFs before a marker are skipped, RSTn must be the expected one at the end of its interval, anything else ends
+ * the data; fewer segments than ceil(mcus / restart_interval), or an over-subscribed Huffman table, is X3DJPEG_ECORRUPT.
+ * scan_cap >= len - info->scan_off + X3DJPEG_SCAN_PAD and seg_cap >= the number of restart intervals always suffice;
+ * too small a buffer is X3DJPEG_EINVAL.  *scan_bytes (without the padding) and *nseg receive what was written. */
+int x3djpeg_scan_prepare(const uint8_t* bytes, size_t len, const X3DJpegInfo* info, uint8_t* scan, size_t scan_cap,
+                         X3DJpegScanSeg* segs, size_t seg_cap, size_t* scan_bytes, size_t* nseg);
+/* Workspace one frame needs, a multiple of 16.  sub_bits: a multiple of 32 (0 if not). */
+size_t x3djpeg_entropy_workspace_bytes(size_t scan_bytes, size_t nseg, int sub_bits);
+/* The scheme of x3djpeg_entropy_decode_batch, serially on the CPU through the same code; every pointer (in the jobs too)
+ * is a host pointer.  rounds (may be null): relaxation rounds used per frame. */
+int x3djpeg_entropy_decode_parallel_host(const X3DJpegScanJob* jobs, int njobs, int sub_bits, void* workspace,
+                                         size_t workspace_bytes, int32_t* status, int32_t* rounds);
+
+/* Device stage.  Huffman decoding of njobs prepared scans into their coefficient ranges: one workgroup per frame, one
+ * launch.  jobs: X3DJpegScanJob [njobs] on the device; workspace: device memory, 16-byte aligned; status: int32 [njobs] on
+ * the device, per frame 0, X3DJPEG_ECORRUPT (a stream the host decoder refuses too) or X3DJPEG_EINVAL (a job that does not
+ * fit its own sizes or the workspace).  A failed frame's coefficients are unspecified but stay inside its own range, and
+ * the other frames are not affected.  The first int32 of a frame's workspace receives the relaxation rounds it used. */
+int x3djpeg_entropy_decode_batch(const void* jobs, int njobs, int sub_bits, void* workspace, size_t workspace_bytes,
+                                 void* status, void* stream);
+
+/* jobs: X3DJpegFrameJob [njobs] on the device; max_blocks, max_w, max_h: the maxima of nblocks, width and
  * height over the jobs (they size the grids).  Frames of a batch may differ in size and subsampling. */
 /* dequantisation + IDCT + 128, clamped: coef -> planes */
 int x3djpeg_idct(const void* jobs, int njobs, int max_blocks, void* stream);

@@ -2,6 +2,7 @@
 size of the reference's Kinetics frame folders.  One JSON line, also written to profiles/jpeg_decode/bench.json.
 
     python tools/bench_jpeg_decode.py [--out FILE] [--rounds N] [--batch N]
+    python tools/bench_jpeg_decode.py --entropy        (the rows below "--entropy", to profiles/jpeg_entropy/bench.json)
 
   host_stage   x3djpeg_parse + x3djpeg_entropy_decode of a batch into the pinned buffer, frames/s at 1, 4, 8, 16 threads
   kernels      x3djpeg_idct and x3djpeg_to_rgb alone on a resident batch, between two device events: us per frame and
@@ -10,6 +11,13 @@ size of the reference's Kinetics frame folders.  One JSON line, also written to 
   end_to_end   JpegDecoder.decode_into (host stage, copy, job table, two launches) + synchronise, 16 threads, frames/s
   pillow       Image.open(...).convert('RGB') in a pool of 16 threads into a pinned [n, H, W, 3] buffer + one upload +
                synchronise, on the same frames; null when Pillow is not importable where this runs
+--entropy: the device Huffman decoder (JpegDecoder(entropy="device")) against the host one, same frames, same protocol:
+  scan_prepare     x3djpeg_parse + x3djpeg_scan_prepare of a batch into the pinned buffer, frames/s at 1, 2, 16 threads
+  entropy_kernel   x3djpeg_entropy_decode_batch alone on a resident batch between two device events, us per frame, with the
+                   relaxation rounds the frames used; once per sub_bits of 256 .. 4096
+  end_to_end       decode_into + synchronise for both paths at 2 and at 16 threads, the four alternating window by window;
+                   and the device path at 2 threads once per sub_bits
+  bytes_copied     host-to-device bytes per batch of either path (coefficients; scans and segment tables)
 Every figure: warm-up first, then `--rounds` windows of at least `--window` seconds (end_to_end and pillow alternate);
 median, minimum and maximum.
 
@@ -157,12 +165,16 @@ def _stats(v, key):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_decode", "bench.json"))
+    ap.add_argument("--entropy", action="store_true", help="the device Huffman decoder against the host one")
+    ap.add_argument("--out", default=None, help="default: profiles/jpeg_decode/bench.json, profiles/jpeg_entropy/bench.json "
+                                                "with --entropy")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=16)
     ap.add_argument("--window", type=float, default=0.5, help="seconds per timed window of the host-side figures")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_entropy" if args.entropy else "jpeg_decode", "bench.json")
     import torch
     from tests import jpeg_ref as jr
     from tools import stamp
@@ -193,6 +205,10 @@ def main():
            "frame": [H, W], "subsampling": "4:2:0", "quality": 75, "encoder": encoder,
            "mean_file_bytes": sum(len(d) for d in distinct) / len(distinct),
            "checked_against": "tests/jpeg_ref.py" + (" and Pillow" if Image is not None else "")}
+
+    if args.entropy:
+        entropy_rows(args, res, frames, distinct, got, dev)
+        return finish(args, res)
 
     # host stage alone
     res["host_stage"] = {}
@@ -288,6 +304,115 @@ def main():
         spread = max(e["frames_per_s_max"] - e["frames_per_s_min"], p["frames_per_s_max"] - p["frames_per_s_min"])
         res["spread_frames_per_s"] = spread
         res["end_to_end_not_below_pillow_beyond_spread"] = e["frames_per_s"] >= p["frames_per_s"] - spread
+    finish(args, res)
+
+
+def entropy_rows(args, res, frames, distinct, got, dev):
+    """The rows of --entropy into res.  got: the host path's decode of `distinct`."""
+    import torch
+    from x3dhip import _jpeglib, jpegops
+    n = len(frames)
+    res["metric"] = "jpeg_entropy"
+    sweep = (256, 512, 1024, 2048, 4096)
+    default = _jpeglib.SUB_BITS_DEFAULT
+    res["sub_bits_default"] = default
+    # the same bits first: every sub_bits of the sweep, frame by frame against the host path
+    for sb in sweep:
+        d = jpegops.JpegDecoder(dev, threads=16, entropy="device", sub_bits=sb)
+        for g, o in zip(got, d.decode(distinct)):
+            assert torch.equal(g, o), sb
+    res["checked_against"] += ", device path equal to the host path at every sub_bits"
+
+    res["scan_prepare"] = {}
+    for th in (1, 2, 16):
+        d = jpegops.JpegDecoder(dev, threads=th, entropy="device")
+        d._prepare_stage(frames)
+        v = [_rate(lambda: d._prepare_stage(frames), n, args.window) for _ in range(args.rounds)]
+        res["scan_prepare"]["threads_%d" % th] = _stats(v, "frames_per_s")
+
+    # the entropy kernel alone
+    dst = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+    targets = [(dst.data_ptr() + i * H * W * 3, 3 * W) for i in range(n)]
+    L = _jpeglib.lib()
+    from x3dhip._lib import stream
+    res["entropy_kernel"] = {}
+    for sb in sweep:
+        d = jpegops.JpegDecoder(dev, threads=16, entropy="device", sub_bits=sb)
+        b = d._stage_device(frames, lambda infos: targets)
+
+        def kern():
+            _jpeglib.check(L.x3djpeg_entropy_decode_batch(b["scan_jobs"], n, sb, b["workspace"].data_ptr(),
+                                                          b["workspace"].numel(), b["status"].data_ptr(), stream()))
+        for _ in range(5):
+            kern()
+        v = []
+        for _ in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                kern()
+            e1.record()
+            torch.cuda.synchronize()
+            v.append(e0.elapsed_time(e1) * 1e3 / 20 / n)
+        assert not b["status"].any()
+        r = _stats(v, "us_per_frame")
+        r["us_per_batch"] = r["us_per_frame"] * n
+        head = b["workspace"].cpu().numpy().view(np.int32)
+        # the first int32 of each frame's workspace: its rounds; the second: its subsequences
+        ws_off = b["ws_off"] // 4
+        r["rounds_max"], r["rounds_mean"] = int(head[ws_off].max()), float(head[ws_off].mean())
+        r["subsequences_mean"] = float(head[ws_off + 1].mean())
+        res["entropy_kernel"]["sub_bits_%d" % sb] = r
+
+    # end to end, both paths at 2 and at 16 threads, alternating
+    versions = {}
+    for th in (2, 16):
+        for ent in ("host", "device"):
+            d = jpegops.JpegDecoder(dev, threads=th, entropy=ent)
+
+            def fn(d=d):
+                d.decode_into(frames, dst)
+                torch.cuda.synchronize()
+            versions["%s_threads_%d" % (ent, th)] = (fn, d)
+    for fn, _ in versions.values():
+        for _ in range(3):
+            fn()
+    rates = {k: [] for k in versions}
+    for _ in range(args.rounds):
+        for k, (fn, _) in versions.items():
+            rates[k].append(_rate(fn, n, args.window))
+    res["end_to_end"] = {k: _stats(v, "frames_per_s") for k, v in rates.items()}
+    res["bytes_copied_per_batch"] = {ent: versions["%s_threads_2" % ent][1].last_bytes_copied for ent in ("host", "device")}
+    assert torch.equal(dst[:len(distinct)], torch.stack(got))
+
+    # the device path at 2 threads once per sub_bits, alternating
+    sw = {}
+    for sb in sweep:
+        d = jpegops.JpegDecoder(dev, threads=2, entropy="device", sub_bits=sb)
+
+        def fn(d=d):
+            d.decode_into(frames, dst)
+            torch.cuda.synchronize()
+        fn()
+        sw[sb] = fn
+    rates = {sb: [] for sb in sweep}
+    for _ in range(args.rounds):
+        for sb, fn in sw.items():
+            rates[sb].append(_rate(fn, n, args.window))
+    res["end_to_end_device_2_threads_by_sub_bits"] = {"sub_bits_%d" % sb: _stats(v, "frames_per_s") for sb, v in rates.items()}
+
+    e = res["end_to_end"]
+    res["step_consumes_frames_per_s"] = STEP_FRAMES_PER_S
+    for th in (2, 16):
+        h, d = e["host_threads_%d" % th], e["device_threads_%d" % th]
+        spread = max(h["frames_per_s_max"] - h["frames_per_s_min"], d["frames_per_s_max"] - d["frames_per_s_min"])
+        res["threads_%d" % th] = {"spread_frames_per_s": spread, "device_over_host": d["frames_per_s"] / h["frames_per_s"],
+                                  "device_not_below_host_beyond_spread": d["frames_per_s"] >= h["frames_per_s"] - spread,
+                                  "device_over_step_rate": d["frames_per_s"] / STEP_FRAMES_PER_S,
+                                  "host_over_step_rate": h["frames_per_s"] / STEP_FRAMES_PER_S}
+
+
+def finish(args, res):
     out = json.dumps(res, sort_keys=True)
     print(out)
     if args.out:

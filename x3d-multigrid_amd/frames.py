@@ -24,11 +24,14 @@ class FrameFolder:
     """One video as the reference stores it: files frame_00001.jpg, frame_00002.jpg, ... without a gap (video_loader stops
     at the first missing file, kinetics.py:43-51).  n_frames and (W, H) come from the listing and the first file's header;
     nothing is decoded.  name: the file name format (the reference's Charades loader has '<video id>-{:06d}.jpg',
-    charades.py:47)."""
+    charades.py:47).  entropy: where this video's frames are Huffman decoded ('host' or 'device'), for decode_folder to
+    pass on to its decoder; None leaves it to the caller."""
 
-    def __init__(self, path, name=FRAME_NAME):
+    def __init__(self, path, name=FRAME_NAME, entropy=None):
         from x3dhip.jpegops import read_header
-        self.path, self.name = path, name
+        if entropy not in (None, 'host', 'device'):
+            raise ValueError("entropy must be 'host' or 'device' (got %r)" % (entropy,))
+        self.path, self.name, self.entropy = path, name, entropy
         names = set(os.listdir(path))
         n = 0
         while name.format(n + 1) in names:
@@ -102,7 +105,7 @@ class FolderKinetics(DeviceVideoKinetics):
             self.shape = (folder.n_frames, folder.height, folder.width, 3)
 
     def __init__(self, folders, labels, sample_duration=80, gamma_tau=5, crop_size=224, x3d_version='M', rng=None,
-                 device='cuda:0', threads=8):
+                 device='cuda:0', threads=8, entropy='host'):
         from x3dhip.clip_input import ClipPreprocessor
         from x3dhip.jpegops import JpegDecoder
         if len(folders) != len(labels) or not folders:
@@ -115,7 +118,7 @@ class FolderKinetics(DeviceVideoKinetics):
         self.scales = [crop_size / i for i in self.RESIZE[x3d_version]]
         self.rng = rng if rng is not None else random
         self.device = torch.device(device)
-        self.decoder = JpegDecoder(self.device, threads=threads)
+        self.decoder = JpegDecoder(self.device, threads=threads, entropy=entropy)
         self._pre = ClipPreprocessor(self.device)
 
     def pre(self, samples, out=None):
@@ -159,11 +162,13 @@ class FolderKinetics(DeviceVideoKinetics):
         return cls([e[0] for e in entries], [e[1] for e in entries], **kw)
 
 
-def decode_folder(path, device, threads=8, decoder=None, chunk=256, name=FRAME_NAME):
-    """A whole video as uint8 [n_frames, H, W, 3] on `device`."""
+def decode_folder(path, device, threads=8, decoder=None, chunk=256, name=FRAME_NAME, entropy=None):
+    """A whole video as uint8 [n_frames, H, W, 3] on `device`.  entropy: 'host' or 'device' Huffman decoding (None: what
+    the FrameFolder says, else 'host'); a ready `decoder` keeps its own."""
     from x3dhip.jpegops import JpegDecoder
-    folder = path if isinstance(path, FrameFolder) else FrameFolder(path, name)
-    dec = decoder if decoder is not None else JpegDecoder(device, threads=threads)
+    folder = path if isinstance(path, FrameFolder) else FrameFolder(path, name, entropy=entropy)
+    dec = decoder if decoder is not None else JpegDecoder(device, threads=threads,
+                                                          entropy=entropy or folder.entropy or 'host')
     out = torch.empty((folder.n_frames, folder.height, folder.width, 3), dtype=torch.uint8, device=dec.device)
     for s in range(0, folder.n_frames, chunk):
         e = min(folder.n_frames, s + chunk)
@@ -171,12 +176,12 @@ def decode_folder(path, device, threads=8, decoder=None, chunk=256, name=FRAME_N
     return out
 
 
-def charades_videos(root, anno, device, threads=8):
+def charades_videos(root, anno, device, threads=8, entropy='host'):
     """{video id: uint8 [n, H, W, 3]} for every video of the annotation dict that has a folder under root, decoded whole:
     the `videos` argument of charades.Charades and the Charades training scripts.  Frames are named frame_%05d.jpg or, as
     in the reference's Charades loader (charades.py:47), <video id>-%06d.jpg."""
     from x3dhip.jpegops import JpegDecoder
-    dec = JpegDecoder(device, threads=threads)
+    dec = JpegDecoder(device, threads=threads, entropy=entropy)
     videos = {}
     for vid in anno:
         path = os.path.join(root, vid)

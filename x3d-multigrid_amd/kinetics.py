@@ -23,10 +23,11 @@ class Kinetics:
     annotation json (or its dict)."""
 
     def __init__(self, root_path, annotation_path, class_labels, subset, sample_duration=16, gamma_tau=5, crops=10,
-                 crop_size=224, device='cuda:0', threads=8):
+                 crop_size=224, device='cuda:0', threads=8, entropy='host'):
+        decode = {} if entropy == 'host' else dict(entropy=entropy)      # 'host' is FolderKinetics' own default
         self._init(FolderKinetics.from_annotation(root_path, annotation_path, class_labels, subset,
                                                   sample_duration=sample_duration, gamma_tau=gamma_tau,
-                                                  crop_size=crop_size, device=device, threads=threads), crops)
+                                                  crop_size=crop_size, device=device, threads=threads, **decode), crops)
 
     def _init(self, dataset, crops):
         if int(crops) < 2:

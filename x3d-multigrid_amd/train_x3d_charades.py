@@ -63,6 +63,8 @@ def main(run_fn, default_save):
     parser.add_argument('--no-graph', action='store_true')
     parser.add_argument('--version', default=X3D_VERSION)
     parser.add_argument('--frames-root', default=None, help='root of the per-video folders of JPEG frames')
+    parser.add_argument('--jpeg-entropy', choices=('host', 'device'), default='host',
+                        help='where the JPEG frames are Huffman decoded: host threads, or the GPU (x3djpeg_entropy_decode_batch)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -71,7 +73,7 @@ def main(run_fn, default_save):
         import frames
         with open(args.anno, 'r') as f:
             anno = json.load(f)
-        size['videos'] = frames.charades_videos(args.frames_root, anno, 'cuda:0')
+        size['videos'] = frames.charades_videos(args.frames_root, anno, 'cuda:0', entropy=args.jpeg_entropy)
     run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version, load_ckpt=args.load,
            resume=args.resume, save_model=args.save, save_every=args.save_every, use_graph=not args.no_graph,
            num_steps_per_update=args.accumulate, **size)

@@ -184,12 +184,12 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
         frames_root=None, val_frames=None):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
-    frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8]) for
+    frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
     sizes); each step's samples are drawn by a sampler seeded per rank, its clips come from FolderKinetics.batch.  val_every: run the
     validation phase (`validate`, the reference does it after every 4 training epochs, :195) every that many steps on
     `val_batches` synthetic batches of [val_batch_size, val_crops, 3, T, H, W]; or, with val_frames -- a
-    dict(root=, anno=, labels=[, subset='validate', threads=8]) for kinetics.Kinetics, or a ready instance -- on the
+    dict(root=, anno=, labels=[, subset='validate', threads=8, entropy='host']) for kinetics.Kinetics, or a ready instance -- on the
     frame folders of the validation set: every video once, val_crops temporal windows each, in batches of val_batch_size,
     sharded over the ranks and scored by `validate_topk` (top-1, top-5 and the loss, reduced over the ranks).
     num_steps_per_update: gradient accumulation over that many micro-batches per optimizer step (train...:119,267-273;
@@ -383,17 +383,21 @@ if __name__ == '__main__':
     parser.add_argument('--val-batch', type=int, default=2, help='videos per validation batch and rank')
     parser.add_argument('--val-crops', type=int, default=3, help='temporal windows per validation video')
     parser.add_argument('--decode-threads', type=int, default=8, help='host threads of the JPEG entropy stage (1..16)')
+    parser.add_argument('--jpeg-entropy', choices=('host', 'device'), default='host',
+                        help='where the JPEG frames are Huffman decoded: host threads, or the GPU (x3djpeg_entropy_decode_batch)')
     args = parser.parse_args()
     frames_root = None
     if args.frames_root is not None:
         if args.anno is None or args.labels is None:
             parser.error('--frames-root needs --anno and --labels')
-        frames_root = dict(root=args.frames_root, anno=args.anno, labels=args.labels, threads=args.decode_threads)
+        frames_root = dict(root=args.frames_root, anno=args.anno, labels=args.labels, threads=args.decode_threads,
+                           entropy=args.jpeg_entropy)
     val_frames = None
     if args.val_frames_root is not None:
         if args.val_anno is None or args.labels is None:
             parser.error('--val-frames-root needs --val-anno and --labels')
-        val_frames = dict(root=args.val_frames_root, anno=args.val_anno, labels=args.labels, threads=args.decode_threads)
+        val_frames = dict(root=args.val_frames_root, anno=args.val_anno, labels=args.labels, threads=args.decode_threads,
+                          entropy=args.jpeg_entropy)
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     run(init_lr=(1.6 / 1024) * args.batch, warmup_steps=args.warmup_steps, max_epochs=args.max_epochs,

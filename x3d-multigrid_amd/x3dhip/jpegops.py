@@ -4,6 +4,13 @@ The serial stage (headers, Huffman decoding) runs on the host in a thread pool (
 pinned coefficient buffer; one asynchronous copy, one job table and two kernel launches per batch go on the current
 stream, whatever the number of frames and however they differ in size or subsampling.  There is no fallback: a frame the
 library does not take raises X3DHipError and nothing is launched for its batch.
+
+entropy="device" moves the Huffman decoding to the GPU as well: the thread pool only parses the headers and strips the
+byte stuffing and restart markers (x3djpeg_scan_prepare) into a reused pinned byte buffer, the copy carries the
+entropy-coded bytes instead of the coefficients (about 1/18 of them), and one more launch
+(x3djpeg_entropy_decode_batch, one workgroup per frame) fills the coefficient buffer the two kernels read, bit for bit
+what the host decoder writes.  A damaged scan is then found on the device: the per-frame status is read back once per
+batch, after the launches.
 """
 from concurrent.futures import ThreadPoolExecutor
 
@@ -11,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _jpeglib
-from ._jpeglib import FRAME_JOB_DT, INFO_DT
+from ._jpeglib import FRAME_JOB_DT, INFO_DT, SCAN_JOB_DT, SCAN_PAD, SCAN_SEG_DT, SUB_BITS_DEFAULT
 from ._lib import X3DHipError, stream
 
 _JOB_FIELDS = ("width", "height", "ncomp", "hmax", "vmax", "nblocks", "blocks_w", "blocks_h", "cw", "ch", "block_start")
@@ -34,14 +41,28 @@ def read_header(data):
 
 
 class JpegDecoder:
-    def __init__(self, device, threads=8):
+    """entropy: "host" (Huffman decoding in the thread pool) or "device" (on the GPU).  For "device": sub_bits is the
+    length of a subsequence in bits, a multiple of 32 (None: the library's default); check=False skips the read of the
+    per-frame status after a batch and leaves it, an int32 tensor on the device, in last_status."""
+
+    def __init__(self, device, threads=8, entropy="host", sub_bits=None, check=True):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("JpegDecoder needs a GPU device (got %s)" % self.device)
+        if entropy not in ("host", "device"):
+            raise ValueError("entropy must be 'host' or 'device' (got %r)" % (entropy,))
+        self.entropy = entropy
+        self.sub_bits = SUB_BITS_DEFAULT if sub_bits is None else int(sub_bits)
+        if self.sub_bits < 32 or self.sub_bits % 32 or self.sub_bits > 1 << 20:
+            raise ValueError("sub_bits must be a multiple of 32 in 32 .. 2^20 (got %r)" % (sub_bits,))
+        self.check = bool(check)
+        self.last_status = None
+        self.last_bytes_copied = 0  # of the last batch's host-to-device copy of coefficients or scan bytes
         self.threads = max(1, min(16, int(threads)))       # never sized from the machine's core count
         _jpeglib.lib()
         self._pool = ThreadPoolExecutor(max_workers=self.threads) if self.threads > 1 else None
         self._pinned = None
+        self._pinned_bytes = None   # entropy="device": scans and segment tables
         self._copied = None         # event after the last H2D copy out of the pinned buffer
 
     def _chunks(self, fn, n):
@@ -53,16 +74,17 @@ class JpegDecoder:
             return fn(0, n)
         return [r for part in self._pool.map(fn, cuts[:-1], cuts[1:]) for r in part]
 
-    def _host_stage(self, frames):
-        """Headers and Huffman decoding of all frames.  Returns (infos, pinned int16 tensor holding the coefficients of
-        the frames back to back, element offsets).  Raises X3DHipError naming the first frame that fails."""
+    @staticmethod
+    def _fail(i, rc):                                       # on the thread that made the call: the message is thread-local
+        return "JPEG frame %d of the batch: libx3djpeg error %d: %s" % (i, rc, _jpeglib.last_error())
+
+    def _parse_stage(self, frames):
+        """Headers of all frames -> infos.  Raises X3DHipError naming the first frame that fails."""
         n = len(frames)
         L = _jpeglib.lib()
         infos = np.zeros(n, dtype=INFO_DT)
         info_ptr, info_size = infos.ctypes.data, INFO_DT.itemsize
-
-        def fail(i, rc):                                    # on the thread that made the call: the message is thread-local
-            return "JPEG frame %d of the batch: libx3djpeg error %d: %s" % (i, rc, _jpeglib.last_error())
+        fail = self._fail
 
         def parse(lo, hi):
             out = []
@@ -74,6 +96,16 @@ class JpegDecoder:
         for msg in self._chunks(parse, n):
             if msg:
                 raise X3DHipError(msg)
+        return infos
+
+    def _host_stage(self, frames):
+        """Headers and Huffman decoding of all frames.  Returns (infos, pinned int16 tensor holding the coefficients of
+        the frames back to back, element offsets).  Raises X3DHipError naming the first frame that fails."""
+        n = len(frames)
+        L = _jpeglib.lib()
+        infos = self._parse_stage(frames)
+        info_ptr, info_size = infos.ctypes.data, INFO_DT.itemsize
+        fail = self._fail
         counts = infos["coef_count"].astype(np.int64)
         offs = np.concatenate([[0], np.cumsum(counts)])
         total = int(offs[-1])
@@ -96,6 +128,114 @@ class JpegDecoder:
                 raise X3DHipError(msg)
         return infos, self._pinned[:total], offs
 
+    def _prepare_stage(self, frames):
+        """Headers and scan preparation of all frames for the device decoder.  Returns (infos, pinned uint8 tensor: per
+        frame its unstuffed scan with padding, then per frame its segment table; byte offsets of the scans, of the tables;
+        scan bytes, segments and workspace bytes per frame).  Raises X3DHipError naming the first frame that fails."""
+        n = len(frames)
+        L = _jpeglib.lib()
+        infos = self._parse_stage(frames)
+        info_ptr, info_size = infos.ctypes.data, INFO_DT.itemsize
+        fail, sub_bits = self._fail, self.sub_bits
+        lens = np.array([len(f) for f in frames], dtype=np.int64)
+        cap = (lens - infos["scan_off"] + SCAN_PAD + 15) & ~15
+        mcus, ri = infos["mcus_x"].astype(np.int64) * infos["mcus_y"], infos["restart_interval"].astype(np.int64)
+        nseg = np.where(ri > 0, -(-mcus // np.maximum(ri, 1)), 1)
+        scan_at = np.concatenate([[0], np.cumsum(cap)])
+        seg_at = scan_at[-1] + np.concatenate([[0], np.cumsum(nseg * SCAN_SEG_DT.itemsize)])
+        total = int(seg_at[-1])
+        if self._copied is not None:
+            self._copied.synchronize()                      # the previous batch's copy has left the pinned buffer
+        if self._pinned_bytes is None or self._pinned_bytes.numel() < total:
+            self._pinned_bytes = torch.empty(max(total, 1 << 16), dtype=torch.uint8).pin_memory()
+        base = self._pinned_bytes.data_ptr()
+        written = np.zeros((n, 2), dtype=np.uint64)         # scan bytes, segments
+        ws = np.zeros(n, dtype=np.int64)
+        out_ptr = written.ctypes.data
+        scan_p, seg_p = (base + scan_at[:-1]).tolist(), (base + seg_at[:-1]).tolist()
+        cap_l, nseg_l = cap.tolist(), nseg.tolist()
+
+        def prepare(lo, hi):
+            out = []
+            for i in range(lo, hi):
+                rc = L.x3djpeg_scan_prepare(frames[i], len(frames[i]), info_ptr + i * info_size, scan_p[i], cap_l[i],
+                                            seg_p[i], nseg_l[i], out_ptr + 16 * i, out_ptr + 16 * i + 8)
+                if rc == 0:
+                    ws[i] = L.x3djpeg_entropy_workspace_bytes(int(written[i, 0]), nseg_l[i], sub_bits)
+                out.append(fail(i, rc) if rc else None)
+            return out
+
+        for msg in self._chunks(prepare, n):
+            if msg:
+                raise X3DHipError(msg)
+        return infos, self._pinned_bytes[:total], scan_at, seg_at, written[:, 0].astype(np.int64), nseg, ws
+
+    def _stage_device(self, frames, dsts):
+        """Everything of a device-path batch short of the launches: the host work, the copy of the scan bytes, the
+        buffers and both job tables.  Returns a dict: n, sub_bits, scan_jobs / frame_jobs (device pointers), workspace,
+        status, coef (tensors), ws_off (each frame's byte offset in the workspace), max_blocks, max_w, max_h, keep (tensors
+        the launches read)."""
+        n = len(frames)
+        infos, host_bytes, scan_at, seg_at, scan_bytes, nseg, ws_need = self._prepare_stage(frames)
+        targets = dsts(infos)
+        counts = infos["coef_count"].astype(np.int64)
+        offs = np.concatenate([[0], np.cumsum(counts)])
+        total = int(offs[-1])
+        ws_off = np.concatenate([[0], np.cumsum(ws_need)])
+        with torch.cuda.device(self.device):
+            dev_bytes = torch.empty(host_bytes.numel(), dtype=torch.uint8, device=self.device)
+            dev_bytes.copy_(host_bytes, non_blocking=True)
+            self._copied = torch.cuda.Event()
+            self._copied.record()
+            self.last_bytes_copied = int(host_bytes.numel())
+            coef = torch.empty(total, dtype=torch.int16, device=self.device)
+            planes = torch.empty(total, dtype=torch.uint8, device=self.device)
+            workspace = torch.empty(int(ws_off[-1]), dtype=torch.uint8, device=self.device)
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+            jobs = np.zeros(n, dtype=FRAME_JOB_DT)
+            fill_jobs(jobs, infos)
+            jobs["coef"] = coef.data_ptr() + 2 * offs[:-1]
+            jobs["planes"] = planes.data_ptr() + offs[:-1]
+            jobs["dst"] = [t[0] for t in targets]
+            jobs["dst_stride"] = [t[1] for t in targets]
+            sj = np.zeros(n, dtype=SCAN_JOB_DT)
+            _jpeglib.fill_scan_jobs(sj, infos)
+            sj["scan"] = dev_bytes.data_ptr() + scan_at[:-1]
+            sj["segs"] = dev_bytes.data_ptr() + seg_at[:-1]
+            sj["coef"] = jobs["coef"]
+            sj["ws_off"], sj["ws_bytes"] = ws_off[:-1], ws_need
+            sj["scan_bytes"], sj["nseg"] = scan_bytes, nseg
+            jd = torch.from_numpy(np.concatenate([jobs.view(np.uint8), sj.view(np.uint8)])).to(self.device)
+        return dict(n=n, sub_bits=self.sub_bits, frame_jobs=jd.data_ptr(), scan_jobs=jd.data_ptr() + jobs.nbytes,
+                    workspace=workspace, ws_off=ws_off[:-1], status=status, coef=coef, max_blocks=int(infos["nblocks"].max()),
+                    max_w=int(infos["width"].max()), max_h=int(infos["height"].max()),
+                    keep=(dev_bytes, coef, planes, workspace, status, jd))
+
+    @staticmethod
+    def launch_device(b):
+        """The three launches of a staged device-path batch on the current stream (capturable: nothing else happens)."""
+        L = _jpeglib.lib()
+        _jpeglib.check(L.x3djpeg_entropy_decode_batch(b["scan_jobs"], b["n"], b["sub_bits"], b["workspace"].data_ptr(),
+                                                      b["workspace"].numel(), b["status"].data_ptr(), stream()))
+        _jpeglib.check(L.x3djpeg_decode_batch(b["frame_jobs"], b["n"], b["max_blocks"], b["max_w"], b["max_h"], stream()))
+
+    def _run_device(self, frames, dsts):
+        b = self._stage_device(frames, dsts)
+        with torch.cuda.device(self.device):
+            self.launch_device(b)
+            cur = torch.cuda.current_stream()
+            for t in b["keep"]:
+                t.record_stream(cur)
+            self.last_status = b["status"]
+            if self.check:
+                st = b["status"].cpu().numpy()              # the one synchronisation of the batch
+                bad = np.flatnonzero(st)
+                if bad.size:
+                    i = int(bad[0])
+                    raise X3DHipError("JPEG frame %d of the batch: libx3djpeg error %d: %s" % (
+                        i, int(st[i]), "corrupt JPEG: the device Huffman decoder refused the scan" if st[i] == _jpeglib.ECORRUPT
+                        else "the scan job does not fit its sizes or its workspace"))
+
     def _run(self, frames, dsts):
         """dsts(infos) -> per frame (data_ptr, row stride in bytes, tensor to keep alive), called after the host stage
         succeeded for every frame."""
@@ -103,12 +243,15 @@ class JpegDecoder:
         n = len(frames)
         if n < 1 or n > 65535:
             raise ValueError("a batch holds 1 .. 65535 frames (got %d)" % n)
+        if self.entropy == "device":
+            return self._run_device(frames, dsts)
         infos, coef_host, offs = self._host_stage(frames)
         targets = dsts(infos)
         total = int(offs[-1])
         with torch.cuda.device(self.device):
             coef = torch.empty(total, dtype=torch.int16, device=self.device)
             coef.copy_(coef_host, non_blocking=True)
+            self.last_bytes_copied = 2 * total
             self._copied = torch.cuda.Event()
             self._copied.record()
             planes = torch.empty(total, dtype=torch.uint8, device=self.device)
