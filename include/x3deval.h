@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define X3DEVAL_ABI_VERSION 2
+#define X3DEVAL_ABI_VERSION 3
 
 #define X3DEVAL_OK 0
 #define X3DEVAL_EINVAL (-1)   /* bad shape / null pointer / unsupported size */
@@ -52,6 +52,8 @@ extern "C" {
 #define X3DEVAL_MAX_FRAMES_B 1024         /* samples per x3deval_ap_append_frames call */
 #define X3DEVAL_CLS_MAX_K 4096            /* classes of the classification meter */
 #define X3DEVAL_CLS_MAX_CROPS 32          /* crops per video of x3deval_cls_append_crops */
+#define X3DEVAL_MERGE_MAX_SHARDS 64       /* meters per x3deval_ap_merge call (one lane of a wave each) */
+#define X3DEVAL_MERGE_MAX_MARKS (1 << 20) /* segment marks per meter */
 
 int x3deval_abi_version(void);
 const char* x3deval_last_error(void);
@@ -87,6 +89,45 @@ size_t x3deval_ap_workspace_bytes(int K, int capacity);
  * tp_i = positives up to i, or their weighted sums.  workspace: x3deval_ap_workspace_bytes(K, capacity) bytes. */
 int x3deval_ap_value(const int* state, const float* scores, const uint8_t* targets, const float* weights, int K,
                      int capacity, void* workspace, size_t workspace_bytes, float* ap, void* stream);
+
+/*
+ * Segment marks and the merge of several meters (data-parallel evaluation: one meter per rank, one AP over all rows).
+ *
+ * AP is not a sum over ranks: the rows of every rank go through one stable sort, so the merged rows need a defined ORDER.
+ * A meter that is to be merged records where each add ended:
+ *   marks    int32 [1 + max_marks] on the device: marks[0] = segments so far, marks[1 + j] = X3DEVAL_S_COUNT after
+ *            segment j (the ends are non-decreasing; an add that was dropped for capacity ends a segment of length 0)
+ *
+ * x3deval_ap_mark: call it after every append (same stream; capturable, one thread).  A mark that does not fit
+ * (marks[0] >= max_marks) sets X3DEVAL_S_OVERFLOW in `state` and writes nothing else.  marks[0] = 0 starts over.
+ * max_marks <= X3DEVAL_MERGE_MAX_MARKS.
+ */
+int x3deval_ap_mark(int* state, int* marks, int max_marks, void* stream);
+
+/* Bytes of the workspace x3deval_ap_merge needs (host only): the destination offset of every segment and a header.
+ * 0 beyond the limits (nshards <= X3DEVAL_MERGE_MAX_SHARDS, max_marks <= X3DEVAL_MERGE_MAX_MARKS). */
+size_t x3deval_ap_merge_workspace_bytes(int nshards, int max_marks);
+
+/* Merges W = nshards meters, stacked as an all-gather leaves them, into one:
+ *   states int32 [W, X3DEVAL_STATE_INTS], marks int32 [W, 1 + max_marks], scores fp32 [W, K, capacity],
+ *   targets uint8 [W, K, capacity], weights fp32 [W, capacity] or NULL (dst_weights is NULL exactly when weights is)
+ *   -> dst_state, dst_scores [K, dst_capacity], dst_targets [K, dst_capacity], dst_weights [dst_capacity]
+ * With n_r the count of shard r, s_r = marks[r][0], e_{r,j} = marks[r][1 + j] and e_{r,-1} = 0, row i of segment j of
+ * shard r lands at destination row off(r, j) + (i - e_{r,j-1}); off(r, j) is the total length of the segments that
+ * precede (j, r) in the order SEGMENT INDEX FIRST, SHARD SECOND: (0,0), (0,1), .., (0,W-1), (1,0), ..  A shard with fewer
+ * segments is absent from the later rounds.  That is the row order of one process that visits global batch j * W + r, and
+ * of DataParallel's per-step chunks.  Destination count = sum of the n_r, capacity word = dst_capacity; the shards'
+ * sticky flags are OR-ed into the destination's.
+ * A shard whose marks are inconsistent (s_r outside [0, max_marks], ends that are not non-decreasing, a last end != n_r,
+ * n_r > capacity) sets X3DEVAL_S_BAD; a total above dst_capacity sets X3DEVAL_S_OVERFLOW; in either case no row is
+ * written and the count is 0.
+ * Two launches whatever the counts are (a one-workgroup plan, a copy whose grid is sized by `capacity`), no allocation,
+ * no synchronisation (capturable); every destination element is stored once, so the result is the same bits run to run.
+ * workspace: x3deval_ap_merge_workspace_bytes(nshards, max_marks) bytes.  X3DEVAL_EINVAL beyond the limits above. */
+int x3deval_ap_merge(const int* states, const int* marks, const float* scores, const uint8_t* targets,
+                     const float* weights, int nshards, int max_marks, int K, int capacity, int* dst_state,
+                     float* dst_scores, uint8_t* dst_targets, float* dst_weights, int dst_capacity, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /*
  * The classification (top-k) meter: the validation arithmetic of train_x3d_kinetics_multigrid.py:253-265, 293-295.

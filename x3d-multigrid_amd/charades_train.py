@@ -5,7 +5,19 @@ tot_loss, the reference's checkpoint record and print lines.
 
 What differs (MI355X-first): batches are made on the device by charades.Charades (no DataLoader, no workers), the losses
 are summed on the device and read where the reference prints them, the meters never leave the GPU, and one process drives
-one GPU (the reference wraps the model in nn.DataParallel).
+one GPU.
+
+Several GPUs (the reference wraps the model in nn.DataParallel, GPUS = 2): one rank per GPU, run(process_group=, rank=,
+world=).  Every rank shuffles with the shared seed and forms the same global batches; rank r takes the r-th contiguous
+chunk of each (DataParallel's scatter) and the Trainer averages the gradients over the ranks.  Every rank draws the
+augmentation parameters of the WHOLE global batch in order and uses its own slice, so the shared `rng` is consumed exactly
+as by one process.  A global batch is cut to a multiple of `world`: at most world - 1 samples at the tail of an epoch are
+dropped (none for world = 1, whose loop is untouched).  The training mAP is one mAP over every rank's rows in the
+reference's row order (apmeter.gather), the printed losses are the mean over the ranks.  Validation: the model's buffers
+are broadcast from rank 0 first -- the reference's semantics, where replica 0's BatchNorm statistics are the module's --
+then rank r scores the whole batches r, r + world, ... and every rank gets the metric of the whole set
+(charades_eval.validate_*(process_group=)), so ReduceLROnPlateau takes the same step everywhere.  Rank 0 alone prints and
+saves.
 """
 import math
 import os
@@ -14,6 +26,7 @@ import random
 import torch
 
 import x3d as resnet_x3d
+import apmeter
 import charades_eval
 from apmeter import APMeter
 from charades import Charades, CHARADES_MEAN, CHARADES_STD
@@ -118,6 +131,59 @@ def _batches(n, batch_size, order=None):
     return [order[i:i + batch_size] for i in range(0, n, batch_size)]
 
 
+def _global_batches(n, batch_size, order, world):
+    """The global batches of an epoch, each cut to a multiple of `world` (an empty remainder is no batch)."""
+    out = []
+    for idx in _batches(n, batch_size, order):
+        idx = idx[:len(idx) // world * world]
+        if idx:
+            out.append(idx)
+    return out
+
+
+def _rank_chunk(idx, rank, world):
+    """The rank's contiguous chunk of a global batch (DataParallel's scatter); len(idx) is a multiple of world."""
+    per = len(idx) // world
+    return idx[rank * per:(rank + 1) * per]
+
+
+def _rank_share(draw, idx, rank, world):
+    """(indices, params) of the rank's chunk of a global batch: draw(i) is called for EVERY sample of the global batch, in
+    order, as one process does (the draws consume a shared random.Random), and the rank keeps its own slice."""
+    params = [draw(i) for i in idx]
+    return _rank_chunk(idx, rank, world), _rank_chunk(params, rank, world)
+
+
+def _broadcast(tensors, process_group):
+    """In-place broadcast of `tensors` from the group's rank 0, one collective per dtype (staged through the host when
+    the backend is not RCCL)."""
+    import torch.distributed as dist
+    src = dist.get_global_rank(process_group, 0)
+    nccl = dist.get_backend(process_group) == "nccl"
+    by_dtype = {}
+    for t in tensors:
+        by_dtype.setdefault(t.dtype, []).append(t)
+    for group in by_dtype.values():
+        flat = torch.cat([t.detach().reshape(-1) for t in group])
+        wire = flat if nccl else flat.cpu()
+        dist.broadcast(wire, src, group=process_group)
+        flat = wire.to(flat.device)
+        o = 0
+        with torch.no_grad():
+            for t in group:
+                t.copy_(flat[o:o + t.numel()].view_as(t))
+                o += t.numel()
+
+
+def _rank_mean(values, process_group, world):
+    """The mean over the ranks of a list of device scalars, as floats (one all-reduce; one synchronisation)."""
+    import torch.distributed as dist
+    v = torch.stack([x.reshape(()) for x in values])
+    wire = v if dist.get_backend(process_group) == "nccl" else v.cpu()
+    dist.all_reduce(wire, op=dist.ReduceOp.SUM, group=process_group)
+    return [float(x) / world for x in wire.cpu()]
+
+
 def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
     """The reference's checkpoint record (train_x3d_charades.py:203-207)."""
     ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
@@ -130,15 +196,21 @@ def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
 
 def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
-        device=None):
+        device=None, process_group=None, rank=0, world=1, base_bn_splits=1):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
     optimizer and scheduler state).  crop_size / c_size: the testing and training output sizes (default: the version's
     table and the reference's hard-coded 224).  Returns a dict: 'steps', 'epochs', 'phases' (one record per phase),
-    'checkpoints', 'lr'."""
+    'checkpoints', 'lr'.  process_group / rank / world: data parallel over that group, one rank per GPU (see the
+    module docstring; batch_size is the GLOBAL batch and must be a multiple of world).  base_bn_splits: the BatchNorm
+    splits of a training batch (a single process with `world` splits normalises as `world` ranks do)."""
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
+    ddp = process_group is not None and world > 1
+    if ddp and batch_size % world != 0:
+        raise ValueError("global batch %d is not divisible by the world size %d" % (batch_size, world))
+    say = print if rank == 0 else (lambda *a, **k: None)
     frames = 80                                                                  # DOUBLED INSIDE DATASET
     table_crop = {'S': 160, 'M': 224, 'XL': 312}[x3d_version]
     resize_size = {'S': [180., 225.], 'M': [256., 256.], 'XL': [360., 450.]}[x3d_version]
@@ -157,13 +229,13 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     torch.cuda.set_device(dev)
     iterations_per_epoch = max(1, len(dataset) // batch_size)
     max_steps = iterations_per_epoch * max_epochs
-    print('train', len(dataset), 'val', len(val_dataset))
-    print('Total iterations:', max_steps, 'Total epochs:', max_epochs)
-    print('datasets created')
+    say('train', len(dataset), 'val', len(val_dataset))
+    say('Total iterations:', max_steps, 'Total epochs:', max_epochs)
+    say('datasets created')
 
     kw = dict(task='loc') if loc else {}
     x3d = resnet_x3d.generate_model(x3d_version=x3d_version, n_classes=400, n_input_channels=3, dropout=dropout,
-                                    base_bn_splits=1, **kw)
+                                    base_bn_splits=base_bn_splits, **kw)
     if load_ckpt is not None:
         x3d.load_state_dict(torch.load(load_ckpt, map_location='cpu')['model_state_dict'])
     x3d.replace_logits(157)                      # before the Trainer: FlatParams flattens the head it finds
@@ -172,28 +244,32 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
         ck = torch.load(resume, map_location='cpu')
         x3d.load_state_dict(ck['model_state_dict'])
     x3d.to(dev)
-    print('model loaded')
+    if ddp:                                      # one model on every rank, the random 157-way head included
+        x3d._flush_tracked()
+        _broadcast(list(x3d.parameters()) + list(x3d.buffers()), process_group)
+    say('model loaded')
 
     lr = init_lr
-    print('INIT LR: %f' % lr)
+    say('INIT LR: %f' % lr)
     optimizer = Trainer(x3d, lr=lr, momentum=0.9, weight_decay=1e-5, objective='loc' if loc else 'bce',
-                        use_graph=use_graph, num_steps_per_update=num_steps_per_update)
+                        use_graph=use_graph, num_steps_per_update=num_steps_per_update,
+                        **(dict(process_group=process_group, world_size=world) if ddp else {}))
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
     if ck is not None:
         optimizer.load_state_dict(ck['optimizer_state_dict'])
         lr_sched.load_state_dict(ck['scheduler_state_dict'])
 
-    val_apm = APMeter()
-    tr_apm = APMeter()
+    val_apm = APMeter(track_segments=ddp)
+    tr_apm = APMeter(track_segments=ddp)
     phases, checkpoints = [], []
     s_times = max(1, iterations_per_epoch // 2)
     zero = torch.zeros((), device=dev)
     try:
         while epochs < max_epochs:
-            print('Step {} Epoch {}'.format(steps, epochs))
-            print('-' * 10)
+            say('Step {} Epoch {}'.format(steps, epochs))
+            say('-' * 10)
             for phase in 2 * ['train'] + ['val']:
-                print(phase)
+                say(phase)
                 if phase == 'train':
                     x3d.train(True)
                     epochs += 1
@@ -201,8 +277,12 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                     order = list(range(len(dataset)))
                     rng.shuffle(order)
                     rec = dict(phase=phase, epoch=epochs, maps=[], losses=[])
-                    for idx in _batches(len(dataset), batch_size, order):
-                        data = dataset.batch(idx)
+                    for idx in _global_batches(len(dataset), batch_size, order, world if ddp else 1):
+                        if ddp:
+                            own, params = _rank_share(dataset.draw, idx, rank, world)
+                            data = dataset.batch(own, params=params)
+                        else:
+                            data = dataset.batch(idx)
                         loss, logits = optimizer.train_step(data[0], data[1])
                         if loc:
                             tr_apm.add_frames(logits, data[1], data[2])
@@ -216,38 +296,47 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                             continue
                         steps += 1
                         if steps % s_times == 0:
-                            tr_map = float(tr_apm.value().mean())
+                            if ddp:
+                                tr_map = float(apmeter.gather(tr_apm, process_group).value().mean())
+                                tot_loss, tot_loc_loss, tot_cls_loss = _rank_mean(
+                                    [tot_loss, tot_loc_loss, tot_cls_loss], process_group, world)
+                            else:
+                                tr_map = float(tr_apm.value().mean())
                             tr_apm.reset()
                             n = s_times * num_steps_per_update
                             if loc:
-                                print(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'
+                                say(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'
                                       .format(epochs, phase, steps, float(tot_loc_loss) / n, float(tot_cls_loss) / n,
                                               float(tot_loss) / s_times, tr_map))
                             else:
-                                print(' Epoch:{} {} steps: {} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                                say(' Epoch:{} {} steps: {} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
                                     epochs, phase, steps, float(tot_cls_loss) / n, float(tot_loss) / s_times, tr_map))
                             rec['maps'].append(tr_map)
                             rec['losses'].append(float(tot_loss) / s_times)
                             tot_loss, tot_loc_loss, tot_cls_loss = zero.clone(), zero.clone(), zero.clone()
-                        if save_every and steps % save_every == 0:
+                        if save_every and steps % save_every == 0 and rank == 0:
                             checkpoints.append(_save_ckpt(x3d, optimizer, lr_sched, save_model, steps))
                     rec['steps'] = steps
                     phases.append(rec)
                 else:
                     vb = _batches(len(val_dataset), max(1, batch_size // 2))
-                    gen = (val_dataset.test_batch(idx) for idx in vb)
-                    res = (charades_eval.validate_loc if loc else charades_eval.validate_cls)(x3d, gen, val_apm)
+                    if ddp:                          # replica 0's running statistics are the module's
+                        x3d._flush_tracked()         # num_batches_tracked is advanced lazily: bring every rank's
+                        _broadcast(list(x3d.buffers()), process_group)      # buffers up to date before they are replaced
+                    gen = (val_dataset.test_batch(idx) for idx in (vb[rank::world] if ddp else vb))
+                    res = (charades_eval.validate_loc if loc else charades_eval.validate_cls)(
+                        x3d, gen, val_apm, **(dict(process_group=process_group) if ddp else {}))
                     num_iter = len(vb)
                     tot_loss = res['loss'] * num_iter / num_steps_per_update
                     val_map = res['map']
                     lr_sched.step(tot_loss)
                     val_apm.reset()
                     if loc:
-                        print(' Epoch:{} {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                        say(' Epoch:{} {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
                             epochs, phase, res['loc_loss'], res['cls_loss'], (tot_loss * num_steps_per_update) / num_iter,
                             val_map))
                     else:
-                        print(' Epoch:{} {} Loc Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                        say(' Epoch:{} {} Loc Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
                             epochs, phase, res['cls_loss'], (tot_loss * num_steps_per_update) / num_iter, val_map))
                     phases.append(dict(phase=phase, epoch=epochs, map=val_map, loss=tot_loss, rows=res['rows'],
                                        lr=optimizer.param_groups[0]['lr'], steps=steps))

@@ -6,6 +6,10 @@ scored by the max over the windows.  The loop itself is charades_train.run, shar
 runs on synthetic videos of the annotation file's lengths; with --frames-root DIR every video of the annotation file that
 has a folder DIR/<video id> of JPEG frames is decoded on the GPU into HBM first (frames.charades_videos), and
 run(videos=...) takes decoded videos from Python.
+
+    python -m torch.distributed.run --nproc-per-node 8 train_x3d_charades.py --anno data/charades.json
+fine-tunes on every GPU of the node: one rank per GPU over RCCL, --batch is the global batch, one mAP over all ranks' rows
+(charades_train.run, process_group=).
 """
 import argparse
 import json
@@ -32,11 +36,13 @@ SAVE_MODEL = 'models/x3d_charades_rgb_sgd_'
 
 def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_UPSCALE, videos=None,
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
-        num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48)):
+        num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
+        process_group=None, rank=0, world=1, base_bn_splits=1):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3]}; None: synthetic videos of round(24 * duration) frames of video_hw noise for every video of
     the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the device of
-    the videos given.  See charades_train.run for the rest."""
+    the videos given.  process_group / rank / world: data parallel, one rank per GPU (init_distributed).  See
+    charades_train.run for the rest."""
     if not isinstance(anno, dict):
         with open(anno, 'r') as f:
             anno = json.load(f)
@@ -45,7 +51,30 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
     return charades_train.run(TASK, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version=x3d_version,
                               load_ckpt=load_ckpt, resume=resume, save_every=save_every, use_graph=use_graph,
                               num_steps_per_update=num_steps_per_update, crop_size=crop_size, c_size=c_size,
-                              dropout=dropout, seed=seed, device=device)
+                              dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
+                              world=world, base_bn_splits=base_bn_splits)
+
+
+def init_distributed():
+    """(process_group, rank, world, device) of a launch under torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK): one
+    rank per GPU over RCCL (backend "nccl"), as train_x3d_kinetics_multigrid.run; (None, 0, 1, cuda:0) otherwise.  The
+    caller destroys the group.  Test hook: X3D_CHARADES_SINGLE_DEVICE=1 puts every rank on cuda:0 and
+    X3D_CHARADES_BACKEND names another backend (gloo), to drive the multi-rank control flow on a one-GPU box."""
+    import torch
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = 0 if os.environ.get("X3D_CHARADES_SINGLE_DEVICE") == "1" else int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if world == 1:
+        return None, 0, 1, dev
+    import torch.distributed as dist
+    backend = os.environ.get("X3D_CHARADES_BACKEND", "nccl")
+    if backend == "nccl":
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    else:
+        dist.init_process_group(backend, rank=rank, world_size=world)
+    return dist.group.WORLD, rank, world, dev
 
 
 def main(run_fn, default_save):
@@ -69,14 +98,21 @@ def main(run_fn, default_save):
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     size = {} if args.size is None else dict(crop_size=args.size, c_size=args.size)
-    if args.frames_root is not None:
-        import frames
-        with open(args.anno, 'r') as f:
-            anno = json.load(f)
-        size['videos'] = frames.charades_videos(args.frames_root, anno, 'cuda:0', entropy=args.jpeg_entropy)
-    run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version, load_ckpt=args.load,
-           resume=args.resume, save_model=args.save, save_every=args.save_every, use_graph=not args.no_graph,
-           num_steps_per_update=args.accumulate, **size)
+    pg, rank, world, dev = init_distributed()
+    try:
+        if args.frames_root is not None:
+            import frames
+            with open(args.anno, 'r') as f:
+                anno = json.load(f)
+            size['videos'] = frames.charades_videos(args.frames_root, anno, str(dev), entropy=args.jpeg_entropy)
+        run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version,
+               load_ckpt=args.load, resume=args.resume, save_model=args.save, save_every=args.save_every,
+               use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,
+               rank=rank, world=world, **size)
+    finally:
+        if pg is not None:
+            import torch.distributed as dist
+            dist.destroy_process_group()
 
 
 if __name__ == '__main__':

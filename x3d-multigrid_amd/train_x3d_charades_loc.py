@@ -30,7 +30,8 @@ SAVE_MODEL = 'models/x3d_charades_loc_rgb_sgd_'
 
 def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_UPSCALE, videos=None,
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
-        num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48)):
+        num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
+        process_group=None, rank=0, world=1, base_bn_splits=1):
     """The reference's run() (train_x3d_charades_loc.py:54-221) over a charades.Charades dataset with task='loc'.
     Arguments as train_x3d_charades.run."""
     if not isinstance(anno, dict):
@@ -41,7 +42,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
     return charades_train.run(TASK, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version=x3d_version,
                               load_ckpt=load_ckpt, resume=resume, save_every=save_every, use_graph=use_graph,
                               num_steps_per_update=num_steps_per_update, crop_size=crop_size, c_size=c_size,
-                              dropout=dropout, seed=seed, device=device)
+                              dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
+                              world=world, base_bn_splits=base_bn_splits)
 
 
 if __name__ == '__main__':

@@ -10,7 +10,7 @@ from ._lib import X3DHipError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libx3deval.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # include/x3deval.h state words
 S_COUNT, S_CAPACITY, S_OVERFLOW, S_BAD, S_BASE, S_GO, S_BATCHES = 0, 1, 2, 3, 4, 5, 6
@@ -19,6 +19,8 @@ MAX_CAPACITY = 0x7fffffc0
 MAX_FRAMES_B = 1024
 CLS_MAX_K = 4096
 CLS_MAX_CROPS = 32
+MERGE_MAX_SHARDS = 64
+MERGE_MAX_MARKS = 1 << 20
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -36,6 +38,9 @@ SIGNATURES = {
     "x3deval_ap_append_frames": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "x3deval_ap_workspace_bytes": (_Z, [_I, _I]),
     "x3deval_ap_value": (_I, [_P, _P, _P, _P, _I, _I, _P, _Z, _P, _P]),
+    "x3deval_ap_mark": (_I, [_P, _P, _I, _P]),
+    "x3deval_ap_merge_workspace_bytes": (_Z, [_I, _I]),
+    "x3deval_ap_merge": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "x3deval_cls_append_crops": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "x3deval_cls_value": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }

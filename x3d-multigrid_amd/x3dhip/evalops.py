@@ -141,6 +141,64 @@ def ap_value(state, scores, targets, weights=None, workspace=None):
     return ap
 
 
+def ap_marks(dev, max_marks):
+    """A fresh marks buffer (int32 [1 + max_marks], no segment yet) on `dev` (include/x3deval.h)."""
+    max_marks = int(max_marks)
+    if max_marks < 0 or max_marks > _evallib.MERGE_MAX_MARKS:
+        raise X3DHipError("ap_marks: %d marks, the meter takes up to %d" % (max_marks, _evallib.MERGE_MAX_MARKS))
+    return torch.zeros(1 + max_marks, dtype=torch.int32, device=dev)
+
+
+def ap_mark(state, marks):
+    """Ends a segment: records the state's row count in `marks` (int32 [1 + max_marks]); capturable."""
+    _need("state", state, torch.int32, 1)
+    _need("marks", marks, torch.int32, 1)
+    if marks.numel() < 1:
+        raise X3DHipError("ap_mark: marks must be [1 + max_marks]")
+    _same_device(state, marks)
+    check(_evallib.lib().x3deval_ap_mark(ptr(state), ptr(marks), marks.numel() - 1, stream()))
+
+
+def ap_merge_workspace_bytes(nshards, max_marks):
+    return int(_evallib.lib().x3deval_ap_merge_workspace_bytes(int(nshards), int(max_marks)))
+
+
+def ap_merge(states, marks, scores, targets, weights, dst_state, dst_scores, dst_targets, dst_weights=None,
+             workspace=None):
+    """Merges W stacked meters -- states [W, STATE_INTS], marks [W, 1 + M], scores [W, K, C], targets [W, K, C] (uint8),
+    weights [W, C] or None -- into the meter (dst_state, dst_scores [K, Cd], dst_targets [K, Cd], dst_weights [Cd] or
+    None) in the order segment index first, shard second (include/x3deval.h).  No synchronisation; flags are left in
+    dst_state.  workspace: uint8 scratch, by default ap_merge_workspace_bytes(W, M)."""
+    _need("states", states, torch.int32, 2)
+    _need("marks", marks, torch.int32, 2)
+    _need("scores", scores, torch.float32, 3)
+    _need("targets", targets, torch.uint8, 3)
+    W, K, C = scores.shape
+    M = marks.shape[1] - 1
+    if W < 1 or W > _evallib.MERGE_MAX_SHARDS or M < 0 or M > _evallib.MERGE_MAX_MARKS:
+        raise X3DHipError("ap_merge: %d shards of %d marks; the merge takes up to %d shards and %d marks"
+                          % (W, M, _evallib.MERGE_MAX_SHARDS, _evallib.MERGE_MAX_MARKS))
+    if tuple(states.shape) != (W, _evallib.STATE_INTS) or marks.shape[0] != W or tuple(targets.shape) != (W, K, C) \
+            or K < 1 or C < 1:
+        raise X3DHipError("ap_merge: states %s, marks %s, scores %s and targets %s do not stack %d meters"
+                          % (tuple(states.shape), tuple(marks.shape), tuple(scores.shape), tuple(targets.shape), W))
+    if weights is not None:
+        _need("weights", weights, torch.float32, 2)
+        if tuple(weights.shape) != (W, C):
+            raise X3DHipError("ap_merge: weights must be [%d, %d] (got %s)" % (W, C, tuple(weights.shape)))
+    if (weights is None) != (dst_weights is None):
+        raise X3DHipError("ap_merge: the destination is weighted exactly when the shards are")
+    if _store(dst_state, dst_scores, dst_targets, dst_weights) != K or dst_scores.shape[1] < 1:
+        raise X3DHipError("ap_merge: the destination stores must be [%d, capacity] (got %s)" % (K, tuple(dst_scores.shape)))
+    if workspace is None:
+        workspace = torch.empty(ap_merge_workspace_bytes(W, M), dtype=torch.uint8, device=scores.device)
+    _need("workspace", workspace, torch.uint8, 1)
+    _same_device(states, marks, scores, targets, weights, dst_state, workspace)
+    check(_evallib.lib().x3deval_ap_merge(ptr(states), ptr(marks), ptr(scores), ptr(targets), ptr(weights), W, M, K, C,
+                                          ptr(dst_state), ptr(dst_scores), ptr(dst_targets), ptr(dst_weights),
+                                          dst_scores.shape[1], ptr(workspace), workspace.numel(), stream()))
+
+
 def cls_rows(dev, capacity):
     """The row arrays of a classification meter: (loss fp32, rank, pred, label, batch_rows int32), each [capacity]."""
     return (torch.zeros(capacity, dtype=torch.float32, device=dev),) + \
