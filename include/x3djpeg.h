@@ -111,6 +111,43 @@ typedef struct X3DJpegScanJob {
     uint8_t huff_vals[8][256];
 } X3DJpegScanJob;
 
+/* Frame store: frames kept on the device in the form the device path decodes from -- the output of x3djpeg_scan_prepare
+ * and its segment table, in arena chunks that are never moved -- so that a batch's two job tables can be built on the
+ * device from a list of frame ids (x3djpeg_store_build_jobs).  The caller fills all three tables with plain copies. */
+
+/* What a frame's jobs take from its headers, laid out as the jobs themselves: `frame` and `scan` are the two job structs
+ * with every pointer, dst_stride, ws_off, ws_bytes, scan_bytes and nseg zero (scan.coef_count is set).  Frames with equal
+ * headers share one entry.  16-byte aligned, a multiple of 16 bytes. */
+typedef struct X3DJpegStoreHeader {
+    X3DJpegFrameJob frame;
+    X3DJpegScanJob scan;
+} X3DJpegStoreHeader;
+
+/* One stored frame: device addresses (16-byte aligned) of its prepared scan and segment table. */
+typedef struct X3DJpegStoreRec {
+    const uint8_t* scan;           /* scan_bytes bytes and X3DJPEG_SCAN_PAD zeros */
+    const X3DJpegScanSeg* segs;    /* nseg entries */
+    int32_t scan_bytes, nseg;
+    int32_t header;                /* index into the header table */
+    int32_t pad;
+} X3DJpegStoreRec;
+
+/* Where one request of a batch is decoded to. */
+typedef struct X3DJpegStoreDst {
+    uint8_t* dst;                  /* as X3DJpegFrameJob.dst */
+    int64_t dst_stride;
+    int32_t width, height;         /* the size the caller expects; a frame of another size is refused */
+} X3DJpegStoreDst;
+
+/* Bits of the build status, and of a request's flags in the plan. */
+#define X3DJPEG_STORE_BAD_ID 1     /* id outside [0, nrecs), or a record whose header index is outside the header table */
+#define X3DJPEG_STORE_BAD_SIZE 2   /* the frame is not width x height of its destination */
+#define X3DJPEG_STORE_NO_COEF 4    /* its coefficients or planes do not fit the capacities given */
+#define X3DJPEG_STORE_NO_WS 8      /* its workspace does not fit */
+
+#define X3DJPEG_STORE_PLAN_THREADS 256   /* the plan kernel's one workgroup */
+#define X3DJPEG_STORE_PLAN_CHUNK 1024    /* requests it sums per pass; a carry joins the passes */
+
 int x3djpeg_abi_version(void);
 const char* x3djpeg_last_error(void);
 size_t x3djpeg_info_bytes(void);
@@ -156,6 +193,37 @@ int x3djpeg_idct(const void* jobs, int njobs, int max_blocks, void* stream);
 int x3djpeg_to_rgb(const void* jobs, int njobs, int max_w, int max_h, void* stream);
 /* both, in two launches whatever njobs is */
 int x3djpeg_decode_batch(const void* jobs, int njobs, int max_blocks, int max_w, int max_h, void* stream);
+
+/* Frame store. */
+size_t x3djpeg_store_header_bytes(void);
+size_t x3djpeg_store_rec_bytes(void);
+size_t x3djpeg_store_dst_bytes(void);
+/* bytes of the plan of n requests: int64 [3 * n + 2] -- coefficient offsets (int16 elements) [n], workspace offsets
+ * (bytes) [n], flags [n], then the two totals */
+size_t x3djpeg_store_plan_bytes(int n);
+
+/* Builds the job tables of a batch from frame ids, on the device: two launches whatever n is, no synchronisation, no
+ * allocation.  recs: X3DJpegStoreRec [nrecs]; headers: X3DJpegStoreHeader [nheaders]; ids: int32 [n], n in 1 .. 65535;
+ * dsts: X3DJpegStoreDst [n]; coef: int16 [coef_cap]; planes: uint8 [planes_cap]; workspace_bytes: the capacity of the
+ * workspace x3djpeg_entropy_decode_batch will be given.  All on the device, the tables 16-byte aligned.
+ *
+ * Request i gets the coefficient range [off_i, off_i + coef_count_i) of coef, the same range of planes in bytes, and
+ * workspace [ws_i, ws_i + x3djpeg_entropy_workspace_bytes(...)_i), where off and ws are the exclusive sums over the
+ * requests before it (a request with a bad id counts as zero, every other one in full whether it is served or not: a
+ * refused request does not move anybody else's range).  The sums, each request's flags and the totals go to `plan`
+ * (x3djpeg_store_plan_bytes(n) bytes).  scan_jobs: X3DJpegScanJob [n], frame_jobs: X3DJpegFrameJob [n]: every byte of both
+ * is written exactly once.  A request that cannot be served (X3DJPEG_STORE_* says why) gets a refused pair -- every byte
+ * of both jobs zero -- for which x3djpeg_entropy_decode_batch reports X3DJPEG_EINVAL and the kernels of
+ * x3djpeg_decode_batch leave at once; *build_status (int32) receives the OR of all requests' flags, 0 if all are served. */
+int x3djpeg_store_build_jobs(const void* recs, int nrecs, const void* headers, int nheaders, const void* ids, int n,
+                             int sub_bits, void* coef, size_t coef_cap, void* planes, size_t planes_cap,
+                             size_t workspace_bytes, const void* dsts, void* plan, void* scan_jobs, void* frame_jobs,
+                             void* build_status, void* stream);
+/* The same through the same code (csrc_jpeg/store_core.h) serially on the CPU; every pointer is a host pointer. */
+int x3djpeg_store_build_jobs_host(const void* recs, int nrecs, const void* headers, int nheaders, const void* ids, int n,
+                                  int sub_bits, void* coef, size_t coef_cap, void* planes, size_t planes_cap,
+                                  size_t workspace_bytes, const void* dsts, void* plan, void* scan_jobs, void* frame_jobs,
+                                  void* build_status);
 
 #ifdef __cplusplus
 }

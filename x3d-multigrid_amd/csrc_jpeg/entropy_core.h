@@ -154,6 +154,15 @@ X3DJ_HD static inline int64_t workspace_need(int64_t nsub, int64_t nseg) {
     return 16 + align16(4 * nseg) + align16(4 * nsub) + 2 * align16(8 * nsub) + align16(4 * nsub);
 }
 
+// What x3djpeg_entropy_workspace_bytes answers, for the host and for the job builder of store_core.h: 0 for a sub_bits or a
+// scan the decoder does not take.  A segment has at most floor(bits / sub_bits) + 1 subsequences.
+X3DJ_HD static inline int64_t frame_workspace_bytes(int64_t scan_bytes, int64_t nseg, int sub_bits) {
+    if (sub_bits < 32 || sub_bits % 32 != 0 || scan_bytes < 0 || scan_bytes > (int64_t)X3DJPEG_SCAN_MAX_BYTES || nseg < 0 ||
+        nseg > ((int64_t)1 << 26))
+        return 0;
+    return workspace_need(scan_bytes * 8 / sub_bits + nseg, nseg);
+}
+
 X3DJ_HD static inline int32_t seg_nsub(uint32_t byte_len, int32_t sub_bits) {
     const int64_t n = ((int64_t)byte_len * 8 + sub_bits - 1) / sub_bits;
     return n < 1 ? 1 : (int32_t)n;

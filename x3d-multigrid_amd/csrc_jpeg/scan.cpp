@@ -104,10 +104,8 @@ extern "C" int x3djpeg_scan_prepare(const uint8_t* d, size_t len, const X3DJpegI
 }
 
 extern "C" size_t x3djpeg_entropy_workspace_bytes(size_t scan_bytes, size_t nseg, int sub_bits) {
-    if (sub_bits < 32 || sub_bits % 32 != 0 || scan_bytes > (size_t)X3DJPEG_SCAN_MAX_BYTES || nseg > (size_t)1 << 26) return 0;
-    // a segment has at most floor(bits / sub_bits) + 1 subsequences
-    const int64_t nsub = (int64_t)scan_bytes * 8 / sub_bits + (int64_t)nseg;
-    return (size_t)x3dj::workspace_need(nsub, (int64_t)nseg);
+    if (scan_bytes > (size_t)X3DJPEG_SCAN_MAX_BYTES || nseg > (size_t)1 << 26) return 0;
+    return (size_t)x3dj::frame_workspace_bytes((int64_t)scan_bytes, (int64_t)nseg, sub_bits);
 }
 
 namespace {

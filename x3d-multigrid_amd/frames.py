@@ -6,6 +6,9 @@ FrameFolder      one video: frame count and size from the listing and the first 
 FolderKinetics   DeviceVideoKinetics' batch / val_batch protocol over frame folders: only the frames a sample draws are
                  decoded, straight into the [T, H, W, 3] tensor ClipPreprocessor consumes
 decode_folder    a whole video as uint8 [n, H, W, 3] in HBM (what charades.Charades(videos=...) takes)
+StoredVideo      a whole video in HBM as the prepared scans of its JPEG files (x3dhip.jpegstore.FrameStore), about the size
+                 of the files: charades.Charades takes it wherever it takes a decoded video and decodes, per batch, the
+                 frames the batch draws
 """
 import json
 import os
@@ -176,17 +179,83 @@ def decode_folder(path, device, threads=8, decoder=None, chunk=256, name=FRAME_N
     return out
 
 
-def charades_videos(root, anno, device, threads=8, entropy='host'):
-    """{video id: uint8 [n, H, W, 3]} for every video of the annotation dict that has a folder under root, decoded whole:
-    the `videos` argument of charades.Charades and the Charades training scripts.  Frames are named frame_%05d.jpg or, as
-    in the reference's Charades loader (charades.py:47), <video id>-%06d.jpg."""
-    from x3dhip.jpegops import JpegDecoder
-    dec = JpegDecoder(device, threads=threads, entropy=entropy)
+class StoredVideo:
+    """One video in a FrameStore: frames ids[0], ids[1], ... of the store, all of one size.  .shape is what the decoded
+    video's would be; .frames(idx) decodes the 0-based frames idx now."""
+
+    def __init__(self, store, ids):
+        ids = range(ids.start, ids.stop) if isinstance(ids, range) and ids.step == 1 else ids
+        if not isinstance(ids, range) or len(ids) < 1 or ids.start < 0 or ids.stop > len(store):
+            raise ValueError("ids must be a non-empty range of frame ids of the store")
+        w, h = store.width[ids.start:ids.stop], store.height[ids.start:ids.stop]
+        if (w != w[0]).any() or (h != h[0]).any():
+            raise ValueError("the frames of a video are of one size")
+        self.store, self.ids, self.device = store, ids, store.device
+        self.shape = (len(ids), int(h[0]), int(w[0]), 3)
+
+    def frames(self, idx):
+        """uint8 [len(idx), H, W, 3] on the store's device."""
+        idx = list(idx)
+        n = self.shape[0]
+        for i in idx:
+            if not 0 <= i < n:
+                raise ValueError("frame %d outside the %d frames of the video" % (i, n))
+        out = torch.empty((len(idx),) + self.shape[1:], dtype=torch.uint8, device=self.device)
+        return self.store.decode_into([self.ids.start + i for i in idx], out)
+
+
+def decode_stored(samples):
+    """samples: dicts with 'frames' and 'frame_idx' (as dataops.ClipBatcher takes them).  Every sample whose 'frames' is a
+    StoredVideo gets, in place, the uint8 tensor of exactly its frame_idx and frame_idx = range(len): one decode_into per
+    store and frame size over all samples (what FolderKinetics.pre does for folders)."""
+    groups = {}
+    for s in samples:
+        v = s["frames"]
+        if isinstance(v, StoredVideo):
+            groups.setdefault((id(v.store),) + v.shape[1:3], []).append(s)
+    for group in groups.values():
+        v = group[0]["frames"]
+        ids = [s["frames"].ids.start + i for s in group for i in s["frame_idx"]]
+        for s in group:
+            n = s["frames"].shape[0]
+            if any(not 0 <= i < n for i in s["frame_idx"]):
+                raise ValueError("frame index outside the video")
+        buf = torch.empty((len(ids),) + v.shape[1:], dtype=torch.uint8, device=v.device)
+        v.store.decode_into(ids, buf)
+        at = 0
+        for s in group:
+            T = len(s["frame_idx"])
+            s["frames"], s["frame_idx"] = buf[at:at + T], range(T)
+            at += T
+
+
+def charades_videos(root, anno, device, threads=8, entropy='host', resident='decoded', chunk_bytes=None):
+    """{video id: video} for every video of the annotation dict that has a folder under root: the `videos` argument of
+    charades.Charades and the Charades training scripts.  resident='decoded': uint8 [n, H, W, 3], decoded whole.
+    resident='compressed': StoredVideo over one FrameStore shared by all videos (chunk_bytes: its arena chunk size),
+    decoded batch by batch on the GPU, Huffman decoding included; `entropy` is not used then.  Frames are named
+    frame_%05d.jpg or, as in the reference's Charades loader (charades.py:47), <video id>-%06d.jpg."""
+    if resident not in ('decoded', 'compressed'):
+        raise ValueError("resident must be 'decoded' or 'compressed' (got %r)" % (resident,))
+    if resident == 'compressed':
+        from x3dhip.jpegstore import FrameStore
+        store = FrameStore(device, threads=threads, **({} if chunk_bytes is None else dict(chunk_bytes=chunk_bytes)))
+    else:
+        from x3dhip.jpegops import JpegDecoder
+        dec = JpegDecoder(device, threads=threads, entropy=entropy)
     videos = {}
     for vid in anno:
         path = os.path.join(root, vid)
         if not os.path.isdir(path):
             continue
         name = FRAME_NAME if os.path.exists(os.path.join(path, FRAME_NAME.format(1))) else vid + '-{:06d}.jpg'
-        videos[vid] = decode_folder(path, device, decoder=dec, name=name)
+        if resident == 'compressed':
+            folder = FrameFolder(path, name)
+            ids = None
+            for s in range(0, folder.n_frames, 256):
+                r = store.add(folder.read(range(s, min(folder.n_frames, s + 256))))
+                ids = r if ids is None else range(ids.start, r.stop)
+            videos[vid] = StoredVideo(store, ids)
+        else:
+            videos[vid] = decode_folder(path, device, decoder=dec, name=name)
     return videos

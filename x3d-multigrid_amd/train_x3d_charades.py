@@ -5,7 +5,9 @@ scored by the max over the windows.  The loop itself is charades_train.run, shar
     python train_x3d_charades.py -gpu 0 --anno data/charades.json --epochs 2 --batch 8 --size 64
 runs on synthetic videos of the annotation file's lengths; with --frames-root DIR every video of the annotation file that
 has a folder DIR/<video id> of JPEG frames is decoded on the GPU into HBM first (frames.charades_videos), and
-run(videos=...) takes decoded videos from Python.
+run(videos=...) takes decoded videos from Python.  --resident compressed keeps the videos in HBM as prepared JPEG scans
+instead (x3dhip.jpegstore.FrameStore, about the size of the files: the real dataset fits one GPU that way) and decodes,
+per batch, the frames the batch draws.
 
     python -m torch.distributed.run --nproc-per-node 8 train_x3d_charades.py --anno data/charades.json
 fine-tunes on every GPU of the node: one rank per GPU over RCCL, --batch is the global batch, one mAP over all ranks' rows
@@ -39,9 +41,9 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
-    tensor [n, H, W, 3]}; None: synthetic videos of round(24 * duration) frames of video_hw noise for every video of
-    the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the device of
-    the videos given.  process_group / rank / world: data parallel, one rank per GPU (init_distributed).  See
+    tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
+    every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
+    device of the videos given.  process_group / rank / world: data parallel, one rank per GPU (init_distributed).  See
     charades_train.run for the rest."""
     if not isinstance(anno, dict):
         with open(anno, 'r') as f:
@@ -94,6 +96,9 @@ def main(run_fn, default_save):
     parser.add_argument('--frames-root', default=None, help='root of the per-video folders of JPEG frames')
     parser.add_argument('--jpeg-entropy', choices=('host', 'device'), default='host',
                         help='where the JPEG frames are Huffman decoded: host threads, or the GPU (x3djpeg_entropy_decode_batch)')
+    parser.add_argument('--resident', choices=('decoded', 'compressed'), default='decoded',
+                        help='how the videos of --frames-root stay in HBM: decoded whole, or as prepared JPEG scans in a frame '
+                             'store, decoded batch by batch (implies the GPU Huffman decoder)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -104,7 +109,8 @@ def main(run_fn, default_save):
             import frames
             with open(args.anno, 'r') as f:
                 anno = json.load(f)
-            size['videos'] = frames.charades_videos(args.frames_root, anno, str(dev), entropy=args.jpeg_entropy)
+            size['videos'] = frames.charades_videos(args.frames_root, anno, str(dev), entropy=args.jpeg_entropy,
+                                                       resident=args.resident)
         run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version,
                load_ckpt=args.load, resume=args.resume, save_model=args.save, save_every=args.save_every,
                use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,

@@ -1,5 +1,6 @@
 """ctypes binding of libx3djpeg.so (include/x3djpeg.h): the JPEG decoder (host parse + Huffman stage, the parallel
-Huffman decoder on the device with its host-side scan preparation and CPU twin, IDCT and colour kernels).
+Huffman decoder on the device with its host-side scan preparation and CPU twin, IDCT and colour kernels, the frame store's
+job builder and its CPU twin).
 
 Same discipline as _datalib.py: the library is mandatory, torch is imported before it is loaded, the ABI version and the
 sizes of the mirrored structs are checked, and a failing entry point raises X3DHipError with the library's message.
@@ -41,6 +42,12 @@ SIGNATURES = {
     "x3djpeg_idct": (_I, [_P, _I, _I, _P]),
     "x3djpeg_to_rgb": (_I, [_P, _I, _I, _I, _P]),
     "x3djpeg_decode_batch": (_I, [_P, _I, _I, _I, _I, _P]),
+    "x3djpeg_store_header_bytes": (_Z, []),
+    "x3djpeg_store_rec_bytes": (_Z, []),
+    "x3djpeg_store_dst_bytes": (_Z, []),
+    "x3djpeg_store_plan_bytes": (_Z, [_I]),
+    "x3djpeg_store_build_jobs": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _Z, _P, _P, _P, _P, _P, _P]),
+    "x3djpeg_store_build_jobs_host": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _Z, _P, _P, _P, _P, _P]),
 }
 
 # X3DJpegInfo / X3DJpegFrameJob / X3DJpegScanSeg / X3DJpegScanJob of include/x3djpeg.h
@@ -62,6 +69,13 @@ SCAN_JOB_DT = np.dtype([("scan", "<u8"), ("segs", "<u8"), ("coef", "<u8"), ("coe
                         ("mcus_y", "<i4"), ("restart_interval", "<i4"), ("comp_h", "<i4", 3), ("comp_v", "<i4", 3),
                         ("comp_td", "<i4", 3), ("comp_ta", "<i4", 3), ("blocks_w", "<i4", 3), ("block_start", "<i4", 3),
                         ("huff_bits", "u1", (8, 16)), ("huff_vals", "u1", (8, 256))])
+# X3DJpegStoreHeader / X3DJpegStoreRec / X3DJpegStoreDst of the frame store, and its constants
+STORE_HEADER_DT = np.dtype([("frame", FRAME_JOB_DT), ("scan", SCAN_JOB_DT)])
+STORE_REC_DT = np.dtype([("scan", "<u8"), ("segs", "<u8"), ("scan_bytes", "<i4"), ("nseg", "<i4"), ("header", "<i4"),
+                         ("pad", "<i4")])
+STORE_DST_DT = np.dtype([("dst", "<u8"), ("dst_stride", "<i8"), ("width", "<i4"), ("height", "<i4")])
+STORE_BAD_ID, STORE_BAD_SIZE, STORE_NO_COEF, STORE_NO_WS = 1, 2, 4, 8
+STORE_PLAN_THREADS, STORE_PLAN_CHUNK = 256, 1024
 
 _lib = None
 
@@ -93,6 +107,11 @@ def lib():
     if h.x3djpeg_scan_seg_bytes() != SCAN_SEG_DT.itemsize or h.x3djpeg_scan_job_bytes() != SCAN_JOB_DT.itemsize:
         raise X3DHipError("libx3djpeg.so scan structs (%d, %d bytes) differ from the binding's (%d, %d)" % (
             h.x3djpeg_scan_seg_bytes(), h.x3djpeg_scan_job_bytes(), SCAN_SEG_DT.itemsize, SCAN_JOB_DT.itemsize))
+    if (h.x3djpeg_store_header_bytes() != STORE_HEADER_DT.itemsize or h.x3djpeg_store_rec_bytes() != STORE_REC_DT.itemsize
+            or h.x3djpeg_store_dst_bytes() != STORE_DST_DT.itemsize):
+        raise X3DHipError("libx3djpeg.so store structs (%d, %d, %d bytes) differ from the binding's (%d, %d, %d)" % (
+            h.x3djpeg_store_header_bytes(), h.x3djpeg_store_rec_bytes(), h.x3djpeg_store_dst_bytes(),
+            STORE_HEADER_DT.itemsize, STORE_REC_DT.itemsize, STORE_DST_DT.itemsize))
     _lib = h
     return h
 

@@ -128,6 +128,14 @@ class JpegDecoder:
                 raise X3DHipError(msg)
         return infos, self._pinned[:total], offs
 
+    def _staging(self, total):
+        """The reused pinned byte buffer of _prepare_stage, at least `total` bytes, once nothing reads it any more."""
+        if self._copied is not None:
+            self._copied.synchronize()                      # the previous batch's copy has left the pinned buffer
+        if self._pinned_bytes is None or self._pinned_bytes.numel() < total:
+            self._pinned_bytes = torch.empty(max(total, 1 << 16), dtype=torch.uint8).pin_memory()
+        return self._pinned_bytes
+
     def _prepare_stage(self, frames):
         """Headers and scan preparation of all frames for the device decoder.  Returns (infos, pinned uint8 tensor: per
         frame its unstuffed scan with padding, then per frame its segment table; byte offsets of the scans, of the tables;
@@ -144,11 +152,7 @@ class JpegDecoder:
         scan_at = np.concatenate([[0], np.cumsum(cap)])
         seg_at = scan_at[-1] + np.concatenate([[0], np.cumsum(nseg * SCAN_SEG_DT.itemsize)])
         total = int(seg_at[-1])
-        if self._copied is not None:
-            self._copied.synchronize()                      # the previous batch's copy has left the pinned buffer
-        if self._pinned_bytes is None or self._pinned_bytes.numel() < total:
-            self._pinned_bytes = torch.empty(max(total, 1 << 16), dtype=torch.uint8).pin_memory()
-        base = self._pinned_bytes.data_ptr()
+        base = self._staging(total).data_ptr()
         written = np.zeros((n, 2), dtype=np.uint64)         # scan bytes, segments
         ws = np.zeros(n, dtype=np.int64)
         out_ptr = written.ctypes.data
