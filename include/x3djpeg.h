@@ -148,6 +148,10 @@ typedef struct X3DJpegStoreDst {
 #define X3DJPEG_STORE_PLAN_THREADS 256   /* the plan kernel's one workgroup */
 #define X3DJPEG_STORE_PLAN_CHUNK 1024    /* requests it sums per pass; a carry joins the passes */
 
+/* Bits of the stage status (x3djpeg_stage): why a request was not copied into the staging buffer. */
+#define X3DJPEG_STAGE_BAD_ID 1     /* id outside [0, nrecs), or a record without addresses or with sizes below zero */
+#define X3DJPEG_STAGE_NO_ROOM 2    /* the frame does not fit what is left of the staging buffer, or max_frame_bytes */
+
 int x3djpeg_abi_version(void);
 const char* x3djpeg_last_error(void);
 size_t x3djpeg_info_bytes(void);
@@ -224,6 +228,47 @@ int x3djpeg_store_build_jobs_host(const void* recs, int nrecs, const void* heade
                                   int sub_bits, void* coef, size_t coef_cap, void* planes, size_t planes_cap,
                                   size_t workspace_bytes, const void* dsts, void* plan, void* scan_jobs, void* frame_jobs,
                                   void* build_status);
+
+/* Second tier of the frame store: the arena may lie in host memory the device can read (x3djpeg_pinned_alloc), with the
+ * record and header tables still on the device.  A batch then first gathers the frames it draws into a small staging
+ * buffer on the device (x3djpeg_stage), and the builder and the decoders run on the staged copy:
+ *     x3djpeg_stage(recs, nrecs, ids, n, ..., staged_recs, staged_ids, ...)
+ *     x3djpeg_store_build_jobs(staged_recs, n, headers, nheaders, staged_ids, n, ...)
+ *     x3djpeg_entropy_decode_batch, x3djpeg_decode_batch as ever.
+ * (These entry points are not named x3djpeg_store_*: that family is closed at the six above.) */
+
+/* bytes one frame takes in a staging buffer: its scan + X3DJPEG_SCAN_PAD rounded up to 16, then its segment table (16
+ * bytes per segment); 0 for sizes below zero */
+size_t x3djpeg_stage_bytes(int scan_bytes, int nseg);
+
+/* Copies the frames `ids` name into `staging` and writes the tables that make the staged copies a store of n frames: two
+ * launches whatever n (1 .. 65535) is, no synchronisation, no allocation.  recs: X3DJpegStoreRec [nrecs], ids: int32 [n],
+ * staging (16-byte aligned, staging_cap bytes) and the four outputs are on the device; only the addresses inside the
+ * records may point into host memory the device can read.  A scan is read in whole 16-byte pieces: scan_bytes +
+ * X3DJPEG_SCAN_PAD rounded up to 16 is readable at rec.scan.  max_frame_bytes: the largest x3djpeg_stage_bytes among the
+ * frames the caller can be asked for (it sizes the copy kernel's grid; n * max_frame_bytes < 2^44).
+ *
+ * Request i is served at offsets[i], the exclusive sum of x3djpeg_stage_bytes over the requests before it (a bad id and a
+ * frame beyond max_frame_bytes count as zero), if it ends at or before staging_cap.  Since a request that does not fit
+ * leaves no room for any after it either, the served requests take staging[0, total) without a gap: a refused request
+ * takes no staging bytes, offsets[i] of a request refused for lack of room is total, and offsets[n] is total.  A served
+ * request gets staged_ids[i] = i and staged_recs[i] = its record with scan and segs rebased into staging; a refused one
+ * staged_ids[i] = -1 and a record of zeros, which x3djpeg_store_build_jobs answers with X3DJPEG_STORE_BAD_ID.  Repeated ids
+ * are staged once per request.  Every byte of staging[0, total) is written exactly once by a plain store, the round-up
+ * tail of each scan as zeros; no byte at or after total is written.  *stage_status (int32) receives the OR of the
+ * X3DJPEG_STAGE_* bits of the refused requests. */
+int x3djpeg_stage(const void* recs, int nrecs, const void* ids, int n, size_t max_frame_bytes, void* staging,
+                  size_t staging_cap, void* staged_recs, void* staged_ids, void* offsets, void* stage_status, void* stream);
+/* The same through the same code (csrc_jpeg/stage_core.h) serially on the CPU; every pointer is a host pointer. */
+int x3djpeg_stage_host(const void* recs, int nrecs, const void* ids, int n, size_t max_frame_bytes, void* staging,
+                       size_t staging_cap, void* staged_recs, void* staged_ids, void* offsets, void* stage_status);
+
+/* Pinned host memory the device can read, for the arena of a host-tier store: mapped and portable.  *host is the address
+ * the CPU writes through, *dev the one the runtime reports for the device: kernels are given *dev, never *host.  These two
+ * are the only entry points that allocate, and they are not for a step's path.  A failure (no device, a limit reached)
+ * is X3DJPEG_ELAUNCH with the byte count in the message. */
+int x3djpeg_pinned_alloc(size_t bytes, void** host, void** dev);
+int x3djpeg_pinned_free(void* host);
 
 #ifdef __cplusplus
 }

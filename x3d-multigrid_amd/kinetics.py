@@ -1,6 +1,8 @@
 """Drop-in for the reference's `kinetics.py` (the validation dataset, kinetics.py:161-242): the videos of a subset of the
 annotation file, every video as `crops` temporal windows of `sample_duration // gamma_tau` frames, centre crop scaled to
-`crop_size`, read from folders of JPEG frames and decoded on the GPU (frames.FolderKinetics.val_batch).
+`crop_size`, read from folders of JPEG frames and decoded on the GPU (frames.FolderKinetics.val_batch), or held as prepared scans
+in a frame store in HBM or pinned host memory and decoded by frame id (Kinetics.from_dataset over
+frames.StoredKinetics: no file is opened during a validation pass).
 
     from kinetics import Kinetics
     val = Kinetics('data/kinetics/frames_val', 'kinetics_val.json', 'labels.txt', 'validate', sample_duration=80,
@@ -33,15 +35,20 @@ class Kinetics:
         if int(crops) < 2:
             raise ValueError("Kinetics: the window step divides by crops - 1 (kinetics.py:220), so crops >= 2")
         self.dataset, self.crops = dataset, int(crops)
+        self.sharded = None
         self.sample_duration, self.gamma_tau = dataset.sample_duration, dataset.gamma_tau
         self.frames = self.sample_duration // self.gamma_tau
 
     @classmethod
-    def from_dataset(cls, dataset, crops=10):
-        """Over a ready frames.FolderKinetics (or kinetics_multigrid.DeviceVideoKinetics): anything with __len__ and
-        val_batch(indices, crops=)."""
+    def from_dataset(cls, dataset, crops=10, sharded=None):
+        """Over a ready frames.FolderKinetics, frames.StoredKinetics (or kinetics_multigrid.DeviceVideoKinetics): anything
+        with __len__ and val_batch(indices, crops=).  sharded=(rank, world): the dataset already holds only the videos rank,
+        rank + world, ... of the listing (frames.StoredKinetics.from_pack(..., rank=, world=)); shard() and batches() then
+        take that rank and world only, and give all of it."""
         self = cls.__new__(cls)
         self._init(dataset, crops)
+        if sharded is not None:
+            self.sharded = (int(sharded[0]), int(sharded[1]))
         return self
 
     def __len__(self):
@@ -51,6 +58,10 @@ class Kinetics:
         """The videos of one rank: rank, rank + world, ... in listing order."""
         if not 0 <= rank < world:
             raise ValueError("rank %d outside a world of %d" % (rank, world))
+        if self.sharded is not None:
+            if (rank, world) != self.sharded:
+                raise ValueError("this dataset holds the shard of rank %d of %d, not of rank %d of %d" % (self.sharded + (rank, world)))
+            return list(range(len(self)))
         return list(range(rank, len(self), world))
 
     def batches(self, batch_size, rank=0, world=1):

@@ -178,6 +178,24 @@ def _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps):
     torch.save(ckpt, save_model + str(steps).zfill(6) + '.pt')
 
 
+TIERS = {'hbm': 'device', 'host': 'host'}       # --resident -> the tier of x3dhip.jpegstore.FrameStore
+
+
+def stored_dataset(frames_mod, resident, pack, kw, subset, rank, world, common):
+    """frames.StoredKinetics for --resident hbm / host: from a pack file (each rank its own shard, videos rank, rank +
+    world, ...), or filled from the frame folders."""
+    if resident not in TIERS:
+        raise ValueError("resident must be 'files', 'hbm' or 'host' (got %r)" % (resident,))
+    kw = dict(kw)
+    kw.pop('entropy', None)                      # a store decodes on the GPU, Huffman stage included
+    threads = kw.pop('threads', 8)
+    if pack is not None:
+        return frames_mod.StoredKinetics.from_pack(pack, tier=TIERS[resident], rank=rank, world=world, **common)
+    return frames_mod.StoredKinetics.from_annotation(kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', subset),
+                                                     tier=TIERS[resident], threads=threads, rank=rank, world=world,
+                                                     **common, **kw)
+
+
 def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_UPSCALE, steps=0, max_steps_run=None,
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
@@ -257,10 +275,14 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         import frames as frames_mod
         if isinstance(frames_root, dict):
             kw = dict(frames_root)
-            folder_ds = frames_mod.FolderKinetics.from_annotation(
-                kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'train'), sample_duration=frames,
-                gamma_tau=gamma_tau, crop_size=clip_size or crop_size, x3d_version='XL' if x3d_version == 'L' else x3d_version,
-                rng=random.Random(4321 + rank), device=dev, **kw)
+            common = dict(sample_duration=frames, gamma_tau=gamma_tau, crop_size=clip_size or crop_size,
+                          x3d_version='XL' if x3d_version == 'L' else x3d_version, rng=random.Random(4321 + rank), device=dev)
+            resident, pack = kw.pop('resident', 'files'), kw.pop('pack', None)
+            if resident == 'files':
+                folder_ds = frames_mod.FolderKinetics.from_annotation(
+                    kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'train'), **common, **kw)
+            else:
+                folder_ds = stored_dataset(frames_mod, resident, pack, kw, 'train', rank, world, common)
         else:
             folder_ds = frames_root
         sampler = random.Random(1234 + rank)
@@ -272,9 +294,18 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         import kinetics
         if isinstance(val_frames, dict):
             kw = dict(val_frames)
-            val_ds = kinetics.Kinetics(kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'validate'),
-                                       sample_duration=frames, gamma_tau=gamma_tau, crops=val_crops,
-                                       crop_size=clip_size or crop_size, device=dev, **kw)
+            resident, pack = kw.pop('resident', 'files'), kw.pop('pack', None)
+            if resident == 'files':
+                val_ds = kinetics.Kinetics(kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'validate'),
+                                           sample_duration=frames, gamma_tau=gamma_tau, crops=val_crops,
+                                           crop_size=clip_size or crop_size, device=dev, **kw)
+            else:
+                import frames as frames_mod
+                # each rank holds its own shard, the videos rank, rank + world, ... that Kinetics.batches gives it
+                val_ds = kinetics.Kinetics.from_dataset(stored_dataset(
+                    frames_mod, resident, pack, kw, 'validate', rank, world,
+                    dict(sample_duration=frames, gamma_tau=gamma_tau, crop_size=clip_size or crop_size, device=dev)),
+                    val_crops, sharded=(rank, world))
         else:
             val_ds = val_frames
     tot_loss = tot_corr = tot_dat = 0.0
@@ -383,21 +414,36 @@ if __name__ == '__main__':
     parser.add_argument('--val-batch', type=int, default=2, help='videos per validation batch and rank')
     parser.add_argument('--val-crops', type=int, default=3, help='temporal windows per validation video')
     parser.add_argument('--decode-threads', type=int, default=8, help='host threads of the JPEG entropy stage (1..16)')
+    parser.add_argument('--resident', choices=('files', 'hbm', 'host'), default='files',
+                        help='where the training frames live: files read every step; or a frame store of prepared scans in '
+                             'HBM (hbm) or in pinned host memory (host, for a set larger than HBM), decoded by frame id')
+    parser.add_argument('--pack', default=None, help='pack file of the training set (tools/pack_frames.py) to load the store '
+                                                     'from, each rank its own shard, instead of --frames-root')
+    parser.add_argument('--val-resident', choices=('files', 'hbm', 'host'), default='files',
+                        help='the same for the validation set')
+    parser.add_argument('--val-pack', default=None, help='pack file of the validation set (tools/pack_frames.py '
+                                                         '--val-windows) instead of --val-frames-root')
     parser.add_argument('--jpeg-entropy', choices=('host', 'device'), default='host',
                         help='where the JPEG frames are Huffman decoded: host threads, or the GPU (x3djpeg_entropy_decode_batch)')
     args = parser.parse_args()
+    if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
+        parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
     frames_root = None
-    if args.frames_root is not None:
+    if args.pack is not None:
+        frames_root = dict(resident=args.resident, pack=args.pack)
+    elif args.frames_root is not None:
         if args.anno is None or args.labels is None:
             parser.error('--frames-root needs --anno and --labels')
         frames_root = dict(root=args.frames_root, anno=args.anno, labels=args.labels, threads=args.decode_threads,
-                           entropy=args.jpeg_entropy)
+                           entropy=args.jpeg_entropy, resident=args.resident)
     val_frames = None
-    if args.val_frames_root is not None:
+    if args.val_pack is not None:
+        val_frames = dict(resident=args.val_resident, pack=args.val_pack)
+    elif args.val_frames_root is not None:
         if args.val_anno is None or args.labels is None:
             parser.error('--val-frames-root needs --val-anno and --labels')
         val_frames = dict(root=args.val_frames_root, anno=args.val_anno, labels=args.labels, threads=args.decode_threads,
-                          entropy=args.jpeg_entropy)
+                          entropy=args.jpeg_entropy, resident=args.val_resident)
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     run(init_lr=(1.6 / 1024) * args.batch, warmup_steps=args.warmup_steps, max_epochs=args.max_epochs,

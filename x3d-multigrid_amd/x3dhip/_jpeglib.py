@@ -1,6 +1,6 @@
 """ctypes binding of libx3djpeg.so (include/x3djpeg.h): the JPEG decoder (host parse + Huffman stage, the parallel
 Huffman decoder on the device with its host-side scan preparation and CPU twin, IDCT and colour kernels, the frame store's
-job builder and its CPU twin).
+job builder and its CPU twin, the stage step of the store's host tier with its CPU twin, pinned memory).
 
 Same discipline as _datalib.py: the library is mandatory, torch is imported before it is loaded, the ABI version and the
 sizes of the mirrored structs are checked, and a failing entry point raises X3DHipError with the library's message.
@@ -48,6 +48,11 @@ SIGNATURES = {
     "x3djpeg_store_plan_bytes": (_Z, [_I]),
     "x3djpeg_store_build_jobs": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _Z, _P, _P, _P, _P, _P, _P]),
     "x3djpeg_store_build_jobs_host": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _Z, _P, _P, _P, _P, _P]),
+    "x3djpeg_stage_bytes": (_Z, [_I, _I]),
+    "x3djpeg_stage": (_I, [_P, _I, _P, _I, _Z, _P, _Z, _P, _P, _P, _P, _P]),
+    "x3djpeg_stage_host": (_I, [_P, _I, _P, _I, _Z, _P, _Z, _P, _P, _P, _P]),
+    "x3djpeg_pinned_alloc": (_I, [_Z, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    "x3djpeg_pinned_free": (_I, [_P]),
 }
 
 # X3DJpegInfo / X3DJpegFrameJob / X3DJpegScanSeg / X3DJpegScanJob of include/x3djpeg.h
@@ -76,6 +81,12 @@ STORE_REC_DT = np.dtype([("scan", "<u8"), ("segs", "<u8"), ("scan_bytes", "<i4")
 STORE_DST_DT = np.dtype([("dst", "<u8"), ("dst_stride", "<i8"), ("width", "<i4"), ("height", "<i4")])
 STORE_BAD_ID, STORE_BAD_SIZE, STORE_NO_COEF, STORE_NO_WS = 1, 2, 4, 8
 STORE_PLAN_THREADS, STORE_PLAN_CHUNK = 256, 1024
+STAGE_BAD_ID, STAGE_NO_ROOM = 1, 2
+
+
+def stage_bytes(scan_bytes, nseg):
+    """x3djpeg_stage_bytes over numpy arrays: what a frame takes in a staging buffer."""
+    return ((np.asarray(scan_bytes, np.int64) + SCAN_PAD + 15) & ~15) + np.asarray(nseg, np.int64) * SCAN_SEG_DT.itemsize
 
 _lib = None
 

@@ -17,13 +17,27 @@ ids, a whole batch (plan) can be captured in a graph and replayed on other frame
     batch = store.plan(64, 340, 256)             # static buffers: batch.ids, batch.dst; batch.launch() is capturable
 
 There is no fallback: a file the decoder does not take raises X3DHipError in add() and the store is left as it was.
+
+Two tiers.  tier="device" (the default) is the above.  With tier="host" the arena chunks lie in pinned host memory the GPU
+reads over the host link (PinnedMemory), for a dataset larger than HBM; the record and header tables stay on the device.
+A batch of such a store owns a small staging buffer in HBM: x3djpeg_stage gathers the frames the batch draws into it (two
+more launches, ids still read on the device, still capturable), and the builder and the decoders run on the staged copy.
+
+Pack files.  store.save(path, meta) writes the whole store -- header table, per-frame fields, arena bytes, a JSON blob the
+caller owns -- as one file of data, without addresses; FrameStore.load(path, device, tier=...) reads it back with bulk
+reads (all of it or ranges of its frames) instead of opening, parsing and un-stuffing every JPEG file again.
 """
+import ctypes
+import json
+import os
+import struct
+
 import numpy as np
 import torch
 
 from . import _jpeglib
 from ._jpeglib import (FRAME_JOB_DT, SCAN_JOB_DT, SCAN_PAD, SCAN_SEG_DT, STORE_DST_DT, STORE_HEADER_DT, STORE_REC_DT,
-                       SUB_BITS_DEFAULT)
+                       SUB_BITS_DEFAULT, stage_bytes)
 from ._lib import X3DHipError, stream
 from .jpegops import JpegDecoder, fill_jobs
 
@@ -32,6 +46,18 @@ MIRROR_DT = np.dtype([("width", "<i4"), ("height", "<i4"), ("nblocks", "<i4"), (
 _REASONS = ((_jpeglib.STORE_BAD_ID, "a frame id outside the store"),
             (_jpeglib.STORE_BAD_SIZE, "a frame of another size than its destination"),
             (_jpeglib.STORE_NO_COEF, "coefficients beyond the buffer"), (_jpeglib.STORE_NO_WS, "workspace beyond the buffer"))
+_STAGE_REASONS = ((_jpeglib.STAGE_BAD_ID, "a frame id outside the store"),
+                  (_jpeglib.STAGE_NO_ROOM, "a frame beyond the staging buffer"))
+TIERS = ("device", "host")
+
+# A pack file, little-endian: PACK_HEAD, the header table (STORE_HEADER_DT [nheaders]), the frame table (PACK_FRAME_DT
+# [nframes]), zeros up to a multiple of 16, the arena bytes (per frame its scan, padded to 16, then its segment table: what
+# x3djpeg_stage_bytes counts), the JSON meta blob.  `offset` is a file offset.
+PACK_MAGIC, PACK_VERSION = b"X3DJPACK", 1
+PACK_HEAD = struct.Struct("<8sIIIIQQQQQ")       # magic, version, header entry bytes, frame entry bytes, sub_bits at save,
+#                                                 nframes, nheaders, arena offset, arena bytes, meta bytes
+PACK_FRAME_DT = np.dtype([("offset", "<u8"), ("length", "<u8"), ("scan_bytes", "<i4"), ("nseg", "<i4"), ("header", "<i4"),
+                          ("width", "<i4"), ("height", "<i4"), ("nblocks", "<i4"), ("coef_count", "<i8")])
 
 
 def store_headers(infos):
@@ -61,6 +87,79 @@ class TorchMemory:
 
     def ptr(self, buf):
         return buf.data_ptr()
+
+    def read(self, buf, off, nbytes):
+        return buf[off:off + nbytes].cpu().numpy()
+
+
+class _PinnedBuffer:
+    """One x3djpeg_pinned_alloc: `view` is the host's numpy view of it, `dev` the address the runtime gives the device."""
+
+    def __init__(self, nbytes):
+        host, dev = ctypes.c_void_p(), ctypes.c_void_p()
+        self._host = None
+        _jpeglib.check(_jpeglib.lib().x3djpeg_pinned_alloc(int(nbytes), ctypes.byref(host), ctypes.byref(dev)))
+        self._host, self.dev, self.nbytes = host.value, dev.value, int(nbytes)
+        self.view = np.ctypeslib.as_array((ctypes.c_uint8 * self.nbytes).from_address(self._host))
+
+    def __del__(self):
+        host, self._host = getattr(self, "_host", None), None
+        if host is not None:
+            self.view = None
+            try:
+                _jpeglib.lib().x3djpeg_pinned_free(host)
+            except Exception:                               # the interpreter is shutting down: the process frees it
+                pass
+
+
+class PinnedMemory:
+    """Where a host-tier store keeps its arena: mapped, portable pinned host memory.  The same three methods as
+    TorchMemory; ptr is the device-visible address, write a plain host copy.  host_view lets load() read a file straight
+    into a chunk."""
+
+    def alloc(self, nbytes):
+        return _PinnedBuffer(nbytes)
+
+    def write(self, buf, off, host):
+        buf.view[off:off + host.size] = host
+
+    def ptr(self, buf):
+        return buf.dev
+
+    def read(self, buf, off, nbytes):
+        return buf.view[off:off + nbytes]
+
+    def host_view(self, buf):
+        return buf.view
+
+
+def _read(memory, buf, off, nbytes):
+    """nbytes of a chunk as numpy uint8 (a memory object without read keeps numpy arrays)."""
+    if hasattr(memory, "read"):
+        return memory.read(buf, off, nbytes)
+    return np.asarray(buf[off:off + nbytes])
+
+
+class NumpyMemory:
+    """The same three methods over plain host memory: a store that is only filled and saved (tools/pack_frames.py), or
+    read by the CPU twins, needs no GPU."""
+
+    def alloc(self, nbytes):
+        whole = np.zeros(int(nbytes) + 64, np.uint8)
+        at = -whole.ctypes.data % 64
+        return whole[at:at + int(nbytes)]
+
+    def write(self, buf, off, host):
+        buf[off:off + host.size] = host
+
+    def ptr(self, buf):
+        return buf.ctypes.data
+
+    def read(self, buf, off, nbytes):
+        return buf[off:off + nbytes]
+
+    def host_view(self, buf):
+        return buf
 
 
 class _HostStages(JpegDecoder):
@@ -114,7 +213,8 @@ class Batch:
     status: int32 [n], per frame 0 or a negative X3DJPEG_E*; build_status: int32 [1], the OR of the X3DJPEG_STORE_* bits
     of the requests the builder refused (a refused frame reports X3DJPEG_EINVAL and its destination is not written)."""
 
-    def __init__(self, store, n, coef_cap, ws_cap, max_blocks, max_w, max_h, ids, dsts, dst=None):
+    def __init__(self, store, n, coef_cap, ws_cap, max_blocks, max_w, max_h, ids, dsts, dst=None, stage_cap=None,
+                 max_frame_bytes=0):
         mem, self.n, self.sub_bits = store.memory, int(n), store.sub_bits
         self.max_blocks, self.max_w, self.max_h = int(max_blocks), int(max_w), int(max_h)
         self.coef_cap, self.ws_cap = int(coef_cap), int(ws_cap)
@@ -126,20 +226,39 @@ class Batch:
         self.scan_jobs = torch.empty(self.n * SCAN_JOB_DT.itemsize, dtype=torch.uint8, device=dev)
         self.frame_jobs = torch.empty(self.n * FRAME_JOB_DT.itemsize, dtype=torch.uint8, device=dev)
         self.plan = torch.empty(3 * self.n + 2, dtype=torch.int64, device=dev)
-        self._status = torch.empty(self.n + 1, dtype=torch.int32, device=dev)
-        self.status, self.build_status = self._status[:self.n], self._status[self.n:]
+        self.staged = stage_cap is not None
+        self._status = torch.empty(self.n + (2 if self.staged else 1), dtype=torch.int32, device=dev)
+        self.status, self.build_status = self._status[:self.n], self._status[self.n:self.n + 1]
         # the tables as they are now: a later add() may move them, and leaves these to this batch
         self._recs, self._headers = store._recs.dev, store._headers.dev
         self.nrecs, self.nheaders = store._recs.n, store._headers.n
-        self._args = (mem.ptr(self._recs), self.nrecs, mem.ptr(self._headers), self.nheaders, ids.data_ptr(), self.n,
+        recs_ptr, nrecs, ids_ptr = mem.ptr(self._recs), self.nrecs, ids.data_ptr()
+        self._stage_args = None
+        if self.staged:
+            # the host tier: the frames are gathered into `staging` first, and the builder is given the staged tables
+            self._chunks = list(store._chunks)              # the arena this batch reads lives as long as the batch
+            self.stage_cap, self.max_frame_bytes = int(stage_cap), int(max_frame_bytes)
+            self.staging = torch.empty(max(self.stage_cap, 16), dtype=torch.uint8, device=dev)
+            self.staged_recs = torch.empty(self.n * STORE_REC_DT.itemsize, dtype=torch.uint8, device=dev)
+            self.staged_ids = torch.empty(self.n, dtype=torch.int32, device=dev)
+            self.offsets = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+            self.stage_status = self._status[self.n + 1:]
+            self._stage_args = (recs_ptr, nrecs, ids_ptr, self.n, self.max_frame_bytes, self.staging.data_ptr(),
+                                self.stage_cap, self.staged_recs.data_ptr(), self.staged_ids.data_ptr(),
+                                self.offsets.data_ptr(), self.stage_status.data_ptr())
+            recs_ptr, nrecs, ids_ptr = self.staged_recs.data_ptr(), self.n, self.staged_ids.data_ptr()
+        self._args = (recs_ptr, nrecs, mem.ptr(self._headers), self.nheaders, ids_ptr, self.n,
                       self.sub_bits, self.coef.data_ptr(), self.coef_cap, self.planes.data_ptr(), self.coef_cap, self.ws_cap,
                       dsts.data_ptr(), self.plan.data_ptr(), self.scan_jobs.data_ptr(), self.frame_jobs.data_ptr(),
                       self.build_status.data_ptr())
 
     def launch(self):
         """x3djpeg_store_build_jobs (two launches), x3djpeg_entropy_decode_batch, x3djpeg_decode_batch (two) on the current
-        stream, and nothing else: no allocation, no copy, no synchronisation."""
+        stream, after x3djpeg_stage (two) for a host-tier store, and nothing else: no allocation, no copy, no
+        synchronisation."""
         L, s = _jpeglib.lib(), stream()
+        if self._stage_args is not None:
+            _jpeglib.check(L.x3djpeg_stage(*self._stage_args, s))
         _jpeglib.check(L.x3djpeg_store_build_jobs(*self._args, s))
         _jpeglib.check(L.x3djpeg_entropy_decode_batch(self.scan_jobs.data_ptr(), self.n, self.sub_bits,
                                                       self.workspace.data_ptr(), self.ws_cap, self.status.data_ptr(), s))
@@ -149,12 +268,15 @@ class Batch:
         """One read of the status words (a synchronisation); X3DHipError naming the first frame that failed."""
         st = self._status.cpu().numpy()
         bad = np.flatnonzero(st[:self.n])
-        if st[self.n] or bad.size:
-            why = [text for bit, text in _REASONS if st[self.n] & bit]
+        staged = int(st[self.n + 1]) if self.staged else 0
+        what = "the stage refused the request (%s)" if staged else "the job builder refused the request (%s)"
+        if st[self.n] or staged or bad.size:
+            why = [text for bit, text in _STAGE_REASONS if staged & bit]
+            why = why or [text for bit, text in _REASONS if st[self.n] & bit]   # a request the stage refused reads as a bad id
             i = int(bad[0]) if bad.size else -1
             raise X3DHipError("JPEG frame %d of the batch: libx3djpeg error %d: %s" % (
                 i, int(st[i]) if bad.size else _jpeglib.EINVAL,
-                "the job builder refused the request (%s)" % ", ".join(why) if why else
+                what % ", ".join(why) if why else
                 "corrupt JPEG: the device Huffman decoder refused the scan" if st[i] == _jpeglib.ECORRUPT else
                 "the scan job does not fit its sizes or its workspace"))
 
@@ -163,10 +285,16 @@ class FrameStore:
     """device: where the frames live.  chunk_bytes: the size of an arena chunk (a frame larger than that gets a chunk of
     its own).  sub_bits: the subsequence length of the device Huffman decoder (None: the library's default), fixed for the
     store since the workspace a frame needs depends on it.  threads: host threads of add().  check=False skips the read of
-    the status words after decode / decode_into and leaves the batch in last_batch.  memory: see TorchMemory."""
+    the status words after decode / decode_into and leaves the batch in last_batch.  memory: see TorchMemory.  tier:
+    "device" keeps the arena chunks where the tables are; "host" keeps them in pinned host memory (PinnedMemory) and
+    decodes through a staging buffer per batch.  A `memory` given by the caller holds tables and chunks alike."""
 
-    def __init__(self, device, chunk_bytes=64 << 20, sub_bits=None, threads=2, check=True, memory=None):
+    def __init__(self, device, chunk_bytes=64 << 20, sub_bits=None, threads=2, check=True, memory=None, tier="device"):
+        if tier not in TIERS:
+            raise ValueError("tier must be one of %s (got %r)" % (", ".join(TIERS), tier))
+        self.tier = tier
         self.memory = memory if memory is not None else TorchMemory(device)
+        self.arena_memory = PinnedMemory() if tier == "host" and memory is None else self.memory
         self.device = torch.device(device)
         self.sub_bits = SUB_BITS_DEFAULT if sub_bits is None else int(sub_bits)
         if self.sub_bits < 32 or self.sub_bits % 32 or self.sub_bits > 1 << 20:
@@ -208,8 +336,14 @@ class FrameStore:
         return r["scan"].copy(), r["segs"].copy()
 
     def bytes_resident(self):
-        """Device bytes the store holds: the arena chunks in full, the header table and the record table."""
-        return sum(c[1] for c in self._chunks) + self._recs.nbytes + self._headers.nbytes
+        """Device bytes the store holds: the header table and the record table, and in the device tier the arena chunks
+        in full."""
+        chunks = 0 if self.tier == "host" else sum(c[1] for c in self._chunks)
+        return chunks + self._recs.nbytes + self._headers.nbytes
+
+    def bytes_pinned(self):
+        """Pinned host bytes the store holds: the arena chunks of the host tier in full."""
+        return sum(c[1] for c in self._chunks) if self.tier == "host" else 0
 
     # ------------------------------------------------------------------ filling
     def add(self, files):
@@ -226,27 +360,7 @@ class FrameStore:
         seg_len = nseg.astype(np.int64) * SCAN_SEG_DT.itemsize
         scan_len = (scan_bytes + SCAN_PAD + 15) & ~15
         size = scan_len + seg_len                           # a frame in the arena: its scan, padded, then its segment table
-        # placement: frames in order, a new chunk when the next frame does not fit.  Chunks are allocated, nothing of the
-        # store is touched until everything is in place.
-        ends = np.cumsum(size)
-        chunk_of, off_of = np.zeros(n, np.int64), np.zeros(n, np.int64)
-        new_chunks, at = [], 0
-        cur = len(self._chunks) - 1
-        room = self._chunks[cur][1] - self._chunks[cur][2] if cur >= 0 else 0
-        used0 = self._chunks[cur][2] if cur >= 0 else 0
-        while at < n:
-            before = int(ends[at - 1]) if at else 0
-            k = int(np.searchsorted(ends, before + room, side="right"))       # frames [at, k) fit
-            if k > at:
-                chunk_of[at:k] = cur
-                off_of[at:k] = used0 + ends[at:k] - size[at:k] - before
-                placed = int(ends[k - 1]) - before
-                room, used0, at = room - placed, used0 + placed, k
-                continue
-            cap = max(self.chunk_bytes, int(size[at]))
-            new_chunks.append([self.memory.alloc(cap), cap, 0])
-            cur, room, used0 = len(self._chunks) + len(new_chunks) - 1, cap, 0
-        chunks = self._chunks + new_chunks
+        chunk_of, off_of, chunks = self._place(size)
         # headers: equal to the previous frame's, or looked up by their bytes
         heads = store_headers(infos)
         hv = heads.view(np.uint8).reshape(n, -1)
@@ -273,28 +387,59 @@ class FrameStore:
                 pack[o:o + nb] = staged[scan_at[i]:scan_at[i] + nb]
                 o += int(scan_len[i])
                 pack[o:o + seg_len[i]] = staged[seg_at[i]:seg_at[i] + seg_len[i]]
-            self.memory.write(chunks[c][0], lo, pack)
+            self.arena_memory.write(chunks[c][0], lo, pack)
             chunks[c][2] = hi
-        base = np.array([self.memory.ptr(chunks[c][0]) for c in chunk_of], np.uint64)
+        self._commit(chunks, chunk_of, off_of, scan_bytes, nseg, header_of, heads[added], index,
+                     {f: infos[f] for f in ("width", "height", "nblocks", "coef_count")}, ws_need)
+        return range(first, first + n)
+
+    def _place(self, size):
+        """Placement of frames of `size` bytes each: in order, a new chunk when the next frame does not fit.  Returns
+        (chunk per frame, offset in it per frame, the chunk list to be).  Chunks are allocated, nothing of the store is
+        touched: a failed allocation leaves it as it was."""
+        ends = np.cumsum(size)
+        n = len(size)
+        chunk_of, off_of = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        new_chunks, at = [], 0
+        cur = len(self._chunks) - 1
+        room = self._chunks[cur][1] - self._chunks[cur][2] if cur >= 0 else 0
+        used0 = self._chunks[cur][2] if cur >= 0 else 0
+        while at < n:
+            before = int(ends[at - 1]) if at else 0
+            k = int(np.searchsorted(ends, before + room, side="right"))       # frames [at, k) fit
+            if k > at:
+                chunk_of[at:k] = cur
+                off_of[at:k] = used0 + ends[at:k] - size[at:k] - before
+                placed = int(ends[k - 1]) - before
+                room, used0, at = room - placed, used0 + placed, k
+                continue
+            cap = max(self.chunk_bytes, int(size[at]))
+            new_chunks.append([self.arena_memory.alloc(cap), cap, 0])
+            cur, room, used0 = len(self._chunks) + len(new_chunks) - 1, cap, 0
+        return chunk_of, off_of, [list(c) for c in self._chunks] + new_chunks
+
+    def _commit(self, chunks, chunk_of, off_of, scan_bytes, nseg, header_of, new_headers, new_index, fields, ws_need):
+        """The arena is written: the records, the new headers and the mirror of n more frames."""
+        n, first = len(chunk_of), self._recs.n
+        scan_len = (np.asarray(scan_bytes, np.int64) + SCAN_PAD + 15) & ~15
+        base = np.array([self.arena_memory.ptr(chunks[c][0]) for c in chunk_of], np.uint64)
         recs = np.zeros(n, STORE_REC_DT)
         recs["scan"] = base + off_of.astype(np.uint64)
         recs["segs"] = recs["scan"] + scan_len.astype(np.uint64)
         recs["scan_bytes"], recs["nseg"], recs["header"] = scan_bytes, nseg, header_of
-        # commit
         self._chunks = chunks
-        if added:
-            self._headers.append(heads[added])
-            self._header_index.update(index)
+        if len(new_headers):
+            self._headers.append(new_headers)
+            self._header_index.update(new_index)
         self._recs.append(recs)
         if first + n > len(self._mirror):
             grown = np.zeros(max(first + n, 2 * len(self._mirror)), MIRROR_DT)
             grown[:first] = self._mirror[:first]
             self._mirror = grown
         m = self._mirror[first:first + n]
-        for f in ("width", "height", "nblocks", "coef_count"):
-            m[f] = infos[f]
+        for f, v in fields.items():
+            m[f] = v
         m["scan_bytes"], m["nseg"], m["ws_need"], m["chunk"] = scan_bytes, nseg, ws_need, chunk_of
-        return range(first, first + n)
 
     # ------------------------------------------------------------------ decoding
     def _ids(self, ids):
@@ -316,12 +461,22 @@ class FrameStore:
         with torch.cuda.device(self.device):
             up = torch.from_numpy(blob).to(self.device)
             b = Batch(self, n, int(m["coef_count"].sum()), int(m["ws_need"].sum()), int(m["nblocks"].max()),
-                      int(m["width"].max()), int(m["height"].max()), up[table.nbytes:].view(torch.int32), up[:table.nbytes])
+                      int(m["width"].max()), int(m["height"].max()), up[table.nbytes:].view(torch.int32), up[:table.nbytes],
+                      **self._stage_sizes(m, None))
             b.launch()
         self.last_batch = b
         if self.check if check is None else check:
             b.raise_for_status()
         return b
+
+    def _stage_sizes(self, m, n):
+        """The staging buffer of a batch over the frames m (mirror rows): their exact sum (n None), or n times the largest
+        (a planned batch).  Nothing for the device tier."""
+        if self.tier != "host":
+            return {}
+        size = stage_bytes(m["scan_bytes"], m["nseg"])
+        largest = int(size.max())
+        return dict(stage_cap=int(size.sum()) if n is None else n * largest, max_frame_bytes=largest)
 
     def decode_into(self, ids, dst, check=None):
         """ids: n frame ids of frames of one size; dst: uint8 [n, H, W, 3] on the device, unit stride over the channels, 3
@@ -374,4 +529,147 @@ class FrameStore:
             dsts = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(self.device)
             ids = torch.full((n,), int(sel[0]), dtype=torch.int32, device=self.device)
             return Batch(self, n, n * int(m["coef_count"].max()), n * int(m["ws_need"].max()), int(m["nblocks"].max()),
-                         width, height, ids, dsts, dst)
+                         width, height, ids, dsts, dst, **self._stage_sizes(m, n))
+
+    # ------------------------------------------------------------------ pack files
+    def save(self, path, meta=None):
+        """Writes the store as one pack file (see PACK_HEAD): data only, no address.  meta: anything json.dumps takes; it
+        comes back from load()."""
+        n, nh = len(self), self._headers.n
+        blob = json.dumps(meta).encode("utf-8")
+        m = self._mirror[:n]
+        recs = self._recs.host[:n]
+        size = stage_bytes(m["scan_bytes"], m["nseg"])
+        tables = PACK_HEAD.size + nh * STORE_HEADER_DT.itemsize + n * PACK_FRAME_DT.itemsize
+        arena_at = (tables + 15) & ~15
+        used = np.array([c[2] for c in self._chunks], np.int64)
+        chunk_at = arena_at + np.cumsum(used) - used        # a chunk's used part holds its frames in order without a gap
+        base = np.array([self.arena_memory.ptr(c[0]) for c in self._chunks], np.uint64)
+        ft = np.zeros(n, PACK_FRAME_DT)
+        if n:
+            ft["offset"] = chunk_at[m["chunk"]].astype(np.uint64) + (recs["scan"] - base[m["chunk"]])
+        ft["length"] = size
+        for f in ("scan_bytes", "nseg", "width", "height", "nblocks", "coef_count"):
+            ft[f] = m[f]
+        ft["header"] = recs["header"]
+        with open(path, "wb") as f:
+            f.write(PACK_HEAD.pack(PACK_MAGIC, PACK_VERSION, STORE_HEADER_DT.itemsize, PACK_FRAME_DT.itemsize, self.sub_bits,
+                                   n, nh, arena_at, int(used.sum()), len(blob)))
+            f.write(self._headers.host[:nh].tobytes())
+            f.write(ft.tobytes())
+            f.write(b"\0" * (arena_at - tables))
+            for c in self._chunks:
+                step = 64 << 20
+                for lo in range(0, c[2], step):
+                    f.write(memoryview(np.ascontiguousarray(_read(self.arena_memory, c[0], lo, min(step, c[2] - lo)))))
+            f.write(blob)
+
+    @staticmethod
+    def _read_pack_tables(f, path):
+        """(sub_bits at save, header table, frame table, meta) of an open pack file; ValueError for any defect."""
+        def bad(why):
+            return ValueError("%s is not a frame pack this version reads: %s" % (path, why))
+        file_bytes = os.fstat(f.fileno()).st_size
+        head = f.read(PACK_HEAD.size)
+        if len(head) < PACK_HEAD.size:
+            raise bad("%d bytes, shorter than its head" % file_bytes)
+        magic, version, hbytes, fbytes, sub_bits, n, nh, arena_at, arena_bytes, meta_bytes = PACK_HEAD.unpack(head)
+        if magic != PACK_MAGIC:
+            raise bad("magic %r" % magic)
+        if version != PACK_VERSION:
+            raise bad("format version %d, not %d" % (version, PACK_VERSION))
+        if hbytes != STORE_HEADER_DT.itemsize or fbytes != PACK_FRAME_DT.itemsize:
+            raise bad("entries of %d and %d bytes, not %d and %d" % (hbytes, fbytes, STORE_HEADER_DT.itemsize,
+                                                                     PACK_FRAME_DT.itemsize))
+        if n >= 1 << 31 or nh >= 1 << 31 or (n and not nh):
+            raise bad("%d frames with %d headers" % (n, nh))
+        tables = PACK_HEAD.size + nh * hbytes + n * fbytes
+        if arena_at != (tables + 15) & ~15 or arena_at + arena_bytes + meta_bytes != file_bytes:
+            raise bad("its counts (%d frames, %d headers, %d arena bytes at %d, %d meta bytes) do not give its %d bytes" % (
+                n, nh, arena_bytes, arena_at, meta_bytes, file_bytes))
+        heads = np.frombuffer(f.read(nh * hbytes), STORE_HEADER_DT)
+        ft = np.frombuffer(f.read(n * fbytes), PACK_FRAME_DT)
+        if len(heads) != nh or len(ft) != n:
+            raise bad("shorter than its tables")
+        if n:
+            off, length = ft["offset"].astype(np.int64), ft["length"].astype(np.int64)
+            wrong = ((ft["scan_bytes"] < 0) | (ft["nseg"] < 1) | (length != stage_bytes(ft["scan_bytes"], ft["nseg"]))
+                     | (off < arena_at) | (off % 16 != 0) | (off + length > arena_at + arena_bytes) | (off + length < off))
+            if wrong.any():
+                i = int(np.flatnonzero(wrong)[0])
+                raise bad("frame %d: %d bytes at %d, outside the arena [%d, %d) or not what its sizes give" % (
+                    i, length[i], off[i], arena_at, arena_at + arena_bytes))
+            wrong = (ft["header"] < 0) | (ft["header"] >= nh)
+            if wrong.any():
+                i = int(np.flatnonzero(wrong)[0])
+                raise bad("frame %d: header %d of %d" % (i, ft["header"][i], nh))
+            h = heads[ft["header"]]
+            wrong = ((h["frame"]["width"] != ft["width"]) | (h["frame"]["height"] != ft["height"])
+                     | (h["frame"]["nblocks"] != ft["nblocks"]) | (h["scan"]["coef_count"] != ft["coef_count"])
+                     | (ft["coef_count"] != ft["nblocks"].astype(np.int64) * 64) | (ft["nblocks"] < 1) | (ft["width"] < 1)
+                     | (ft["height"] < 1))
+            if wrong.any():
+                i = int(np.flatnonzero(wrong)[0])
+                raise bad("frame %d: its sizes are not its header's" % i)
+        f.seek(arena_at + arena_bytes)
+        try:
+            meta = json.loads(f.read(meta_bytes).decode("utf-8"))
+        except ValueError as e:
+            raise bad("meta: %s" % e)
+        return sub_bits, heads, ft, meta
+
+    @classmethod
+    def read_meta(cls, path):
+        """The meta blob of a pack file, after the same checks of its tables as load() makes; no frame is read."""
+        with open(path, "rb") as f:
+            return cls._read_pack_tables(f, path)[3]
+
+    @classmethod
+    def load(cls, path, device, tier="device", sub_bits=None, ranges=None, memory=None, **kw):
+        """Reads a pack file.  Returns (store, meta, id_map).  ranges: a list of ranges of saved frame ids (None: all of
+        them); only those frames are read, placed as add() places frames, and id_map is the list of the ranges of their
+        new ids, one per entry of `ranges`.  sub_bits: None takes the one the pack was saved with.  The host tier reads
+        straight into each chunk's host view, the device tier through one staging buffer per chunk.  ValueError, before
+        any store exists, for a file that is not a whole pack of this version."""
+        with open(path, "rb") as f:
+            saved_bits, heads, ft, meta = cls._read_pack_tables(f, path)
+            if ranges is None:
+                ranges = [range(len(ft))]
+            ranges = [r if isinstance(r, range) else range(*r) for r in ranges]
+            for r in ranges:
+                if r.step != 1 or (len(r) and (r.start < 0 or r.stop > len(ft))):
+                    raise ValueError("range %r outside the %d frames of %s (or not of step 1)" % (r, len(ft), path))
+            sel = np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in ranges] + [np.zeros(0, np.int64)])
+            store = cls(device, sub_bits=saved_bits if sub_bits is None else sub_bits, memory=memory, tier=tier, **kw)
+            n = sel.size
+            at = np.cumsum([0] + [len(r) for r in ranges])
+            id_map = [range(int(a), int(b)) for a, b in zip(at[:-1], at[1:])]
+            if len(heads):
+                store._headers.append(heads)
+                store._header_index = {heads[i:i + 1].tobytes(): i for i in range(len(heads) - 1, -1, -1)}
+            if n == 0:
+                return store, meta, id_map
+            t = ft[sel]
+            size, src = t["length"].astype(np.int64), t["offset"].astype(np.int64)
+            chunk_of, off_of, chunks = store._place(size)
+            mem = store.arena_memory
+            for c in np.unique(chunk_of):
+                idx = np.flatnonzero(chunk_of == c)
+                lo, hi = int(off_of[idx[0]]), int(off_of[idx[-1]] + size[idx[-1]])
+                view = mem.host_view(chunks[c][0])[lo:hi] if hasattr(mem, "host_view") else np.empty(hi - lo, np.uint8)
+                # runs of frames that follow each other in the file: one read each
+                cut = np.flatnonzero(src[idx[1:]] != src[idx[:-1]] + size[idx[:-1]]) + 1
+                for run in np.split(idx, cut):
+                    a = int(off_of[run[0]]) - lo
+                    nb = int(size[run].sum())
+                    f.seek(int(src[run[0]]))
+                    if f.readinto(memoryview(view)[a:a + nb]) != nb:
+                        raise ValueError("%s ends inside frame %d" % (path, sel[run[0]]))
+                if not hasattr(mem, "host_view"):
+                    mem.write(chunks[c][0], lo, view)
+                chunks[c][2] = hi
+        uniq, inv = np.unique(np.stack([t["scan_bytes"], t["nseg"]], axis=1), axis=0, return_inverse=True)
+        ws = np.array([_jpeglib.workspace_bytes(a, b, store.sub_bits) for a, b in uniq.tolist()], np.int64)
+        store._commit(chunks, chunk_of, off_of, t["scan_bytes"], t["nseg"], t["header"], heads[:0], {},
+                      {f: t[f] for f in ("width", "height", "nblocks", "coef_count")}, ws[inv.reshape(-1)])
+        return store, meta, id_map
