@@ -18,6 +18,7 @@ from tests import jpeg_entropy_cases as jc
 from tests import jpeg_ref as jr
 from tests import jpegstore_ref as sr
 from tests import jpegtier_ref as tr
+from tests.test_jpeg_store_gpu import LENGTHS, _anno, folders          # noqa: F401  (the Charades frame folders, a fixture)
 from x3dhip import _jpeglib, jpegops, jpegstore
 from x3dhip._jpeglib import STORE_REC_DT
 from x3dhip._lib import X3DHipError, stream
@@ -381,6 +382,119 @@ def test_a_validation_window_pack_serves_kinetics_batches_and_refuses_other_fram
     with pytest.raises(ValueError, match=r"frame 39 of video class_b/vidB is not in the pack"):
         ds.videos[1].frames([0, 39])
     assert tuple(ds.videos[1].frames([0, 36]).shape) == (2, 64, 80, 3)
+
+
+@pytest.fixture(scope="module")
+def kinds(tree):
+    """The four training videos of the tree three ways: (labels, decoded tensors, FolderVideos on one decoder,
+    StoredVideos in one store)."""
+    entries = frames.list_annotation(*tree["train"], "train")
+    dec = jpegops.JpegDecoder(DEV, threads=2)
+    store = jpegstore.FrameStore(DEV, threads=2, chunk_bytes=64 << 10)
+    decoded = [frames.decode_folder(f, DEV, decoder=dec) for f, _ in entries]
+    folder = [frames.FolderVideo(f, dec) for f, _ in entries]
+    stored = [frames.StoredVideo(store, frames.add_folder(store, f)) for f, _ in entries]
+    assert [v.shape[1:3] for v in decoded] == [(t[4], t[3]) for t in tr.TREE]
+    return [label for _, label in entries], decoded, folder, stored
+
+
+@pytest.mark.parametrize("mix", ["sfdf", "dsfs", "fdsd"])
+def test_one_batch_across_decoded_folder_and_stored_videos(kinds, mix):
+    """A plain DeviceVideoKinetics whose videos are of all three kinds (d: decoded tensor, f: FolderVideo, s: StoredVideo;
+    videos 0 and 3 are 64 x 80, 1 and 2 are 80 x 64, so the letters put both sizes into one source or one size into two
+    sources) gives the all-decoded dataset's batches bit for bit: the groups of gather_frames and the slots after them."""
+    from kinetics_multigrid import DeviceVideoKinetics
+    labels, decoded, folder, stored = kinds
+    of = dict(d=decoded, f=folder, s=stored)
+    videos = [of[k][i] for i, k in enumerate(mix)]
+    assert {type(v) for v in videos} == {torch.Tensor, frames.FolderVideo, frames.StoredVideo}
+    a = DeviceVideoKinetics(decoded, labels, rng=random.Random(5), **KW)
+    b = DeviceVideoKinetics(videos, labels, rng=random.Random(5), **KW)
+    for picks, iteration, long_state in (([0, 1, 2, 3], 0, 3), ([3, 1, 1, 0, 2], 1, 2)):
+        ca, ya, la, sa = a.batch(picks, iteration, long_state)
+        cb, yb, lb, sb = b.batch(picks, iteration, long_state)
+        assert ca.shape == cb.shape and torch.equal(ca, cb), (picks, iteration, long_state)
+        assert torch.equal(ya, yb) and la == lb and sa == sb
+    va, ya = a.val_batch([0, 1, 2, 3], crops=3)
+    vb, yb = b.val_batch([0, 1, 2, 3], crops=3)
+    assert tuple(va.shape) == (4, 3, 3, 5, 32, 32) and torch.equal(va, vb) and torch.equal(ya, yb)
+    assert float(va.abs().sum()) > 0 and not torch.equal(va[0], va[3])
+    assert all(videos[i] is v for i, v in enumerate(b.videos))             # the dataset's videos stay what they were
+
+
+def test_gather_frames_gives_every_sample_its_own_frames(kinds):
+    """Interleaved samples [A, B, A, B] of two sources of one frame size (a store holding videos 1 and 2, a decoder reading
+    their folders): two decode_into calls, and every sample gets exactly its frame_idx, in its order, repeats included."""
+    _, decoded, folder, stored = kinds
+    picks = [(stored[1], [3, 0, 7, 7]), (folder[1], [5, 39, 1]), (stored[2], [30]), (folder[2], [10, 9, 0, 2, 2]),
+             (decoded[1], [4, 6])]
+    assert len({v.shape[1:] for v, _ in picks}) == 1
+    want = [v.frames(idx) if frames.is_lazy(v) else v for v, idx in picks]
+    calls = []
+    for src in (stored[1].source, folder[1].source):
+        real = src.decode_into
+        src.decode_into = lambda requests, dst, real=real: calls.append(len(requests)) or real(requests, dst)
+    samples = [dict(frames=v, frame_idx=list(idx), tag=k) for k, (v, idx) in enumerate(picks)]
+    try:
+        frames.gather_frames(samples)
+    finally:
+        del stored[1].source.decode_into, folder[1].source.decode_into
+    assert calls == [5, 8]                                                  # one call per source, over all its samples
+    for k, (s, (v, idx)) in enumerate(zip(samples, picks)):
+        assert s["tag"] == k and torch.equal(s["frames"], want[k]), k
+        if frames.is_lazy(v):
+            assert list(s["frame_idx"]) == list(range(len(idx))) and torch.equal(s["frames"], decoded[1 + (k > 1)][idx]), k
+        else:
+            assert s["frames"] is v and s["frame_idx"] == idx              # a decoded video passes through untouched
+    with pytest.raises(ValueError, match="frame index outside the video"):
+        frames.gather_frames([dict(frames=folder[1], frame_idx=[40])])
+    with pytest.raises(ValueError, match="frame 40 outside the 40 frames"):
+        folder[1].frames([40])
+    # neither a tensor nor a lazy video: left as it is, and refused by the clip kernels' own check
+    from kinetics_multigrid import DeviceVideoKinetics
+    bad = type("V", (), dict(shape=tuple(decoded[0].shape), device=DEV))()
+    assert not frames.is_lazy(bad) and frames.gather_frames is __import__("x3dhip.clip_input").clip_input.gather_frames
+    with pytest.raises(ValueError, match="frames must be contiguous uint8 tensors"):
+        DeviceVideoKinetics([bad], [0], **KW).val_batch([0], crops=3)
+
+
+@pytest.mark.parametrize("task", ["class", "loc"])
+def test_charades_batches_over_folder_videos_equal_those_over_decoded_ones(folders, task):    # noqa: F811
+    """Charades over frames.FolderVideo (files read and decoded per batch), on the folders of test_jpeg_store_gpu's
+    Charades test: batch and test_batch equal the decoded videos' bit for bit."""
+    import os
+    from charades import Charades
+    dec = frames.charades_videos(folders, _anno(["training"] * 3), DEV, threads=2)
+    decoder = jpegops.JpegDecoder(DEV, threads=2)
+    lazy = {}
+    for vid in LENGTHS:
+        path = os.path.join(folders, vid)
+        name = frames.FRAME_NAME if os.path.exists(os.path.join(path, frames.FRAME_NAME.format(1))) else vid + "-{:06d}.jpg"
+        lazy[vid] = frames.FolderVideo(frames.FrameFolder(path, name), decoder)
+        assert tuple(lazy[vid].shape) == tuple(dec[vid].shape) and frames.is_lazy(lazy[vid]) and not frames.is_lazy(dec[vid])
+    kw = dict(task=task, frames=80, gamma_tau=2, crop_size=20, c_size=20, scales=(0.8, 0.9))
+    train = [Charades(_anno(["training"] * 3), "training", v, rng=random.Random(4), **kw) for v in (dec, lazy)]
+    assert len(train[0]) == len(train[1]) == 3 and train[0].data == train[1].data
+    idx = [2, 0, 1, 0]
+    params = [train[0].draw(i) for i in idx]
+    a, b = train[0].batch(idx, params=params), train[1].batch(idx, params=params)
+    assert len(a) == len(b) == (2 if task == "class" else 3) and tuple(a[0].shape) == (4, 3, 40, 20, 20)
+    for x, y in zip(a, b):
+        assert x.dtype == y.dtype and torch.equal(x, y)
+    assert float(a[0].abs().sum()) > 0
+    train[0].rng, train[1].rng = random.Random(9), random.Random(9)    # and with draws of their own
+    for x, y in zip(train[0].batch([1, 2]), train[1].batch([1, 2])):
+        assert torch.equal(x, y)
+    test = [Charades(_anno(["testing"] * 3), "testing", v, crops=10, **kw) for v in (dec, lazy)]
+    a, b = test[0].test_batch([0, 1, 2]), test[1].test_batch([0, 1, 2])
+    assert len(a) == len(b) == (2 if task == "class" else 3)
+    assert tuple(a[0].shape) == ((3, 10, 3, 40, 20, 20) if task == "class" else (3, 3, 50, 20, 20))
+    for x, y in zip(a, b):
+        assert x.dtype == y.dtype and torch.equal(x, y)
+    for x, y in zip(test[0].test_batch([1]), test[1].test_batch([1])):
+        assert torch.equal(x, y)
+    with pytest.raises(ValueError, match="frames must be contiguous uint8 tensors on a CUDA"):
+        Charades(_anno(["training"] * 3), "training", dict(dec, AAAAA=dec["AAAAA"].cpu()), **kw)
 
 
 # --------------------------------------------------------------------------- 7. the scripts

@@ -2,7 +2,7 @@
 run serially) against the numpy restatement of tests/jpegtier_ref.py byte for byte inside guard bytes; the refusals; the
 staged tables taken through the job builder's twin and decoded on the CPU; the same lists once more in a stand-alone program
 built with the address and undefined-behaviour sanitisers; the C ABI; FrameStore.save / load on a store kept in host
-memory, with the files load must refuse."""
+memory, with the files load must refuse; jpegops.HostStages, through which a store is filled, on its own without a GPU."""
 import os
 import re
 import shutil
@@ -223,7 +223,41 @@ def test_stage_symbols_constants_and_argument_checks():
     assert b"argument check failed" in h.x3djpeg_last_error()
 
 
-# --------------------------------------------------------------------------- 6. pack files on host memory
+# --------------------------------------------------------------------------- 6. the host stages on their own
+def test_host_stages_prepare_in_plain_host_memory_without_a_gpu(monkeypatch):
+    """jpegops.HostStages is what FrameStore.add prepares frames with, and tools/pack_frames.py runs it on machines
+    without a GPU: it is no JpegDecoder, touches neither torch.cuda nor pinned memory, and its staging buffer holds, per
+    frame, the scan and the segment table x3djpeg_scan_prepare gives for that frame alone (sr.Tables)."""
+    import torch
+    from x3dhip import jpegops
+    T = _tables()
+
+    def refuse(*a, **kw):
+        raise AssertionError("the host stages reached for the GPU")
+    for name in ("init", "_lazy_init", "is_available", "device_count", "current_device", "set_device", "device",
+                 "synchronize", "current_stream", "Event", "Stream"):
+        monkeypatch.setattr(torch.cuda, name, refuse)
+    monkeypatch.setattr(torch.Tensor, "pin_memory", refuse)
+    stages = jpegops.HostStages(3, SUB_BITS)
+    assert issubclass(jpegops.JpegDecoder, jpegops.HostStages) and not isinstance(stages, jpegops.JpegDecoder)
+    assert stages.threads == 3 and stages.sub_bits == SUB_BITS and jpegops.HostStages(99, None).threads == 16
+    infos, staged, scan_at, seg_at, scan_bytes, nseg, ws = stages._prepare_stage(FILES)
+    monkeypatch.undo()
+    assert staged.device.type == "cpu" and staged.dtype == torch.uint8 and not staged.is_pinned()
+    assert not stages._staging(1).is_pinned() and stages._staging(1).data_ptr() == staged.data_ptr()     # reused
+    assert infos.tobytes() == T.infos.tobytes()
+    assert np.array_equal(scan_bytes, T.scan_bytes) and np.array_equal(nseg, T.nseg)
+    assert np.array_equal(ws, sr.workspace_bytes(T.scan_bytes, T.nseg, SUB_BITS))
+    got = staged.numpy()
+    for i in range(len(FILES)):
+        nb, sb = int(scan_bytes[i]) + SCAN_PAD, int(nseg[i]) * _jpeglib.SCAN_SEG_DT.itemsize
+        assert got[scan_at[i]:scan_at[i] + nb].tobytes() == T.arena[T.scan_at[i]:T.scan_at[i] + nb].tobytes(), NAMES[i]
+        assert got[seg_at[i]:seg_at[i] + sb].tobytes() == T.arena[T.seg_at[i]:T.seg_at[i] + sb].tobytes(), NAMES[i]
+    with pytest.raises(ValueError, match="sub_bits must be a multiple of 32"):
+        jpegops.HostStages(2, 48)
+
+
+# --------------------------------------------------------------------------- 7. pack files on host memory
 def _store(files=FILES, **kw):
     from x3dhip import jpegstore
     _lib()

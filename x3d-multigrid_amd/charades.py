@@ -1,7 +1,8 @@
 """Charades dataset for X3D on MI355X -- the drop-in for the reference's ``charades.py`` (make_dataset :68-104, Charades
 :107-164, custom_collate_fn :167-189) over decoded uint8 videos already resident in HBM (frames.charades_videos decodes
-folders of JPEG frames into that form), or over the same videos resident as prepared JPEG scans (frames.StoredVideo, about
-1/18 of the bytes): a batch then first decodes, on the GPU, exactly the frames it draws.
+folders of JPEG frames into that form), or over lazy videos (frames.py: the same videos as prepared JPEG scans in a frame
+store, frames.StoredVideo, about 1/18 of the bytes, or as folders, frames.FolderVideo): a batch then first decodes, on the
+GPU, exactly the frames it draws (frames.gather_frames).
 
 What is the same: the dataset filters and order, the doubling of ``frames`` and ``gamma_tau``, the random draws of a
 training sample in the reference's order from Python's ``random``, the label window at stride 1 under frames at stride
@@ -22,7 +23,7 @@ import random as _random
 import numpy as np
 import torch
 
-from frames import StoredVideo, decode_stored
+from frames import gather_frames, is_lazy
 from x3dhip import dataops
 from x3dhip.clip_input import center_crop_box
 
@@ -49,7 +50,7 @@ def annotation_ranges(num_frames, duration, actions):
 
 def make_dataset(split_file, split, videos, num_classes=157):
     """charades.py:68-104.  split_file: the annotation file's path, or its dict.  videos: {video id: uint8 CUDA tensor
-    [n_frames, H, W, 3], or a frames.StoredVideo}.  Keeps the reference's filters (the subset, the video present,
+    [n_frames, H, W, 3], or a lazy video of frames.py}.  Keeps the reference's filters (the subset, the video present,
     n_frames >= 162) and order.
     Returns (entries, table): entries [(vid, duration, n_frames)], table the device annotation table over them
     (dataops.AnnotationTable; video v of the table is entries[v])."""
@@ -66,7 +67,7 @@ def make_dataset(split_file, split, videos, num_classes=157):
         if vid not in videos:
             continue
         v = videos[vid]
-        if not isinstance(v, StoredVideo):
+        if not is_lazy(v):
             if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.uint8 or not v.is_contiguous():
                 raise ValueError("frames must be contiguous uint8 tensors on a CUDA(HIP) device (video %s)" % vid)
             if v.dim() != 4 or v.shape[3] != 3:
@@ -185,7 +186,7 @@ class Charades:
                                 x1=p["x1"], y1=p["y1"], crop=p["crop"], flip=p["flip"], dst_off=b * 3 * T * S * S,
                                 dst_cs=T * S * S, dst_ts=S * S))
             jobs.append((i, first, self.frames))                    # labels at stride 1 (:140)
-        decode_stored(samples)                                      # StoredVideo -> the frames drawn, decoded
+        gather_frames(samples)                                      # lazy videos -> the frames drawn, decoded
         self._clips(clips, samples, S)
         return (clips,) + self._labels(jobs, self.frames)
 
@@ -215,7 +216,7 @@ class Charades:
                 x1, y1, crop = center_crop_box(self.videos[i].shape[2], self.videos[i].shape[1])
                 samples.append(dict(frames=self.videos[i], frame_idx=strided[b], x1=x1, y1=y1, crop=crop, flip=False,
                                     dst_off=b * 3 * Tmax * S * S, dst_cs=Tmax * S * S, dst_ts=S * S, Tpad=Tmax))
-        decode_stored(samples)                                      # StoredVideo -> the frames drawn, decoded
+        gather_frames(samples)                                      # lazy videos -> the frames drawn, decoded
         self._clips(clips, samples, S)
         jobs = [(i, 0, self.data[i][2]) for i in indices]
         return (clips,) + self._labels(jobs, max(j[2] for j in jobs))

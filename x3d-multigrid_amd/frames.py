@@ -1,26 +1,32 @@
 """Folders of JPEG frames as a data source: the reference's on-disk protocol (kinetics.py:43-51: `frame_%05d.jpg`, 1-based)
-read from disk on the host and decoded on the GPU by x3dhip.jpegops.JpegDecoder (libx3djpeg.so, bit-exact with the PIL
-decode of the reference's loader).
+read from disk on the host and decoded on the GPU by libx3djpeg.so, bit-exact with the PIL decode of the reference's loader.
 
-FrameFolder      one video: frame count and size from the listing and the first file's header, raw bytes on demand
-FolderKinetics   DeviceVideoKinetics' batch / val_batch protocol over frame folders: only the frames a sample draws are
-                 decoded, straight into the [T, H, W, 3] tensor ClipPreprocessor consumes
-decode_folder    a whole video as uint8 [n, H, W, 3] in HBM (what charades.Charades(videos=...) takes)
-StoredVideo      a whole video in HBM as the prepared scans of its JPEG files (x3dhip.jpegstore.FrameStore), about the size
-                 of the files: charades.Charades takes it wherever it takes a decoded video and decodes, per batch, the
-                 frames the batch draws
-StoredKinetics   FolderKinetics' batches, bit for bit, over StoredVideos: the store lives in HBM (tier='device') or in
-                 pinned host memory (tier='host', for a set larger than HBM), filled from folders or read from a pack
-                 file (FrameStore.save / load; tools/pack_frames.py writes one without a GPU)
+A video reaches a dataset (kinetics_multigrid.DeviceVideoKinetics, charades.Charades) in one of two forms.  Decoded: a uint8
+tensor [n, H, W, 3] in HBM (decode_folder).  Lazy: an object with .shape = (n_frames, H, W, 3), .device, .source -- something
+with decode_into(requests, dst), a JpegDecoder or a FrameStore -- and .requests(idx), what that source takes for the
+0-based frames idx (ValueError for a frame it cannot serve):
+
+FolderVideo      a FrameFolder and the JpegDecoder that decodes it; the requests are the files' bytes
+StoredVideo      frames of a x3dhip.jpegstore.FrameStore (prepared scans, about the size of the files, in HBM or in pinned
+                 host memory); the requests are frame ids.  WindowedVideo: one of which only some frames are stored
+
+gather_frames (x3dhip.clip_input, also reachable from here) is the one place where lazy videos are decoded: per batch, exactly the frames the batch draws, one
+decode_into per source and frame size.  The datasets call it on their samples and hand the result to the clip kernels, so
+a dataset may mix all three kinds of video.  A new way of keeping frames resident is a new lazy video, not a new dataset.
+
+FrameFolder      one video on disk: frame count and size from the listing and the first file's header, raw bytes on demand
+FolderKinetics   DeviceVideoKinetics constructed over folders (FolderVideos on one decoder)
+StoredKinetics   DeviceVideoKinetics constructed over a store: filled from folders (from_annotation) or read from a pack
+                 file (from_pack; FrameStore.save / load, tools/pack_frames.py writes one without a GPU)
+charades_videos  the `videos` dict of charades.Charades from folders, decoded or as StoredVideos
 """
 import json
 import os
-import random
 
 import torch
 
-from cycle_batch_sampler import long_cycle_shapes
 from kinetics_multigrid import DeviceVideoKinetics
+from x3dhip.clip_input import gather_frames, is_lazy  # noqa: F401  (the protocol's two functions, beside the clip kernels' host side)
 
 FRAME_NAME = 'frame_{:05d}.jpg'
 MIN_FRAMES = 80 + 1          # kinetics.py:124: videos with n_frames <= 81 are skipped
@@ -114,58 +120,35 @@ def list_annotation(root, anno_json, labels_txt, subset):
     return entries
 
 
+class LazyVideo:
+    """What the lazy videos share: .frames(idx) decodes the 0-based frames idx now, uint8 [len(idx), H, W, 3] on .device."""
+
+    def frames(self, idx):
+        requests = self.requests(list(idx))
+        out = torch.empty((len(requests),) + self.shape[1:], dtype=torch.uint8, device=self.device)
+        return self.source.decode_into(requests, out)
+
+
+class FolderVideo(LazyVideo):
+    """A FrameFolder decoded by `decoder` (a JpegDecoder): the requests are the bytes of the files."""
+
+    def __init__(self, folder, decoder):
+        self.folder, self.source, self.device = folder, decoder, decoder.device
+        self.shape = (folder.n_frames, folder.height, folder.width, 3)
+        self.requests = folder.read
+
+
 class FolderKinetics(DeviceVideoKinetics):
-    """DeviceVideoKinetics over frame folders instead of decoded videos: same draws (draw_clip_params / val_crop_indices /
-    center_crop_box, through the parent's batch and val_batch), same return values.  Per sample only the drawn frames
-    are read and decoded, into a [T, H, W, 3] tensor that the clip kernels then index with range(T)."""
+    """DeviceVideoKinetics over frame folders (paths or FrameFolders), all read through one JpegDecoder (.decoder): per
+    batch only the drawn frames are read and decoded."""
 
-    class _Video:
-        """What the parent's loops ask of a video: .shape = (n_frames, H, W, 3)."""
-
-        def __init__(self, folder):
-            self.folder = folder
-            self.shape = (folder.n_frames, folder.height, folder.width, 3)
-
-    def __init__(self, folders, labels, sample_duration=80, gamma_tau=5, crop_size=224, x3d_version='M', rng=None,
-                 device='cuda:0', threads=8, entropy='host'):
-        from x3dhip.clip_input import ClipPreprocessor
+    def __init__(self, folders, labels, *args, device='cuda:0', threads=8, entropy='host', **kw):
         from x3dhip.jpegops import JpegDecoder
         if len(folders) != len(labels) or not folders:
             raise ValueError("one label per folder, at least one folder")
         self.folders = [f if isinstance(f, FrameFolder) else FrameFolder(f) for f in folders]
-        self.videos = [self._Video(f) for f in self.folders]
-        self.labels = labels
-        self.sample_duration, self.gamma_tau, self.crop_size = sample_duration, gamma_tau, crop_size
-        self.long_cycles = long_cycle_shapes(sample_duration, crop_size)
-        self.scales = [crop_size / i for i in self.RESIZE[x3d_version]]
-        self.rng = rng if rng is not None else random
-        self.device = torch.device(device)
-        self.decoder = JpegDecoder(self.device, threads=threads, entropy=entropy)
-        self._pre = ClipPreprocessor(self.device)
-
-    def pre(self, samples, out=None):
-        """The parent hands over (video, params) per sample; decode each sample's frames (one decoder batch for all
-        samples), then run the clip kernels on them."""
-        files, slots = [], []
-        for v, p in samples:
-            idx = p["frame_idx"]
-            files += v.folder.read(idx)
-            slots.append((v, len(idx)))
-        decoded, at = [], 0
-        same = len({v.shape[1:] for v, _ in slots}) == 1
-        if same:                                             # one destination tensor, one job table
-            H, W = slots[0][0].shape[1:3]
-            buf = torch.empty((len(files), H, W, 3), dtype=torch.uint8, device=self.device)
-            self.decoder.decode_into(files, buf)
-            for v, T in slots:
-                decoded.append(buf[at:at + T])
-                at += T
-        else:
-            bufs = [torch.empty((T, v.shape[1], v.shape[2], 3), dtype=torch.uint8, device=self.device) for v, T in slots]
-            self.decoder.decode(files, out=[b[t] for b in bufs for t in range(b.shape[0])])
-            decoded = bufs
-        clips = [(d, dict(p, frame_idx=list(range(d.shape[0])))) for d, (_, p) in zip(decoded, samples)]
-        return self._pre(clips, out=out)
+        self.decoder = JpegDecoder(device, threads=threads, entropy=entropy)
+        super().__init__([FolderVideo(f, self.decoder) for f in self.folders], labels, *args, **kw)
 
     @classmethod
     def from_annotation(cls, root, anno_json, labels_txt, subset, **kw):
@@ -189,9 +172,9 @@ def decode_folder(path, device, threads=8, decoder=None, chunk=256, name=FRAME_N
     return out
 
 
-class StoredVideo:
+class StoredVideo(LazyVideo):
     """One video in a FrameStore: frames ids[0], ids[1], ... of the store, all of one size.  .shape is what the decoded
-    video's would be; .frames(idx) decodes the 0-based frames idx now."""
+    video's would be; the requests are the store's frame ids."""
 
     def __init__(self, store, ids):
         ids = range(ids.start, ids.stop) if isinstance(ids, range) and ids.step == 1 else ids
@@ -200,22 +183,17 @@ class StoredVideo:
         w, h = store.width[ids.start:ids.stop], store.height[ids.start:ids.stop]
         if (w != w[0]).any() or (h != h[0]).any():
             raise ValueError("the frames of a video are of one size")
-        self.store, self.ids, self.device = store, ids, store.device
+        self.store = self.source = store
+        self.ids, self.device = ids, store.device
         self.shape = (len(ids), int(h[0]), int(w[0]), 3)
 
-    def frame_ids(self, idx):
+    def requests(self, idx):
         """The store's ids of the 0-based frames idx."""
         n = self.shape[0]
         for i in idx:
             if not 0 <= i < n:
                 raise ValueError("frame %d outside the %d frames of the video" % (i, n))
         return [self.ids.start + i for i in idx]
-
-    def frames(self, idx):
-        """uint8 [len(idx), H, W, 3] on the store's device."""
-        ids = self.frame_ids(list(idx))
-        out = torch.empty((len(ids),) + self.shape[1:], dtype=torch.uint8, device=self.device)
-        return self.store.decode_into(ids, out)
 
 
 class WindowedVideo(StoredVideo):
@@ -232,7 +210,7 @@ class WindowedVideo(StoredVideo):
         self._at = {orig: k for k, orig in enumerate(index)}
         self.shape = (int(n_frames),) + self.shape[1:]
 
-    def frame_ids(self, idx):
+    def requests(self, idx):
         try:
             return [self.ids.start + self._at[int(i)] for i in idx]
         except KeyError as e:
@@ -240,36 +218,21 @@ class WindowedVideo(StoredVideo):
                 e.args[0], self.name, len(self.ids), self.shape[0])) from None
 
 
-def decode_stored(samples):
-    """samples: dicts with 'frames' and 'frame_idx' (as dataops.ClipBatcher takes them).  Every sample whose 'frames' is a
-    StoredVideo gets, in place, the uint8 tensor of exactly its frame_idx and frame_idx = range(len): one decode_into per
-    store and frame size over all samples (what FolderKinetics.pre does for folders)."""
-    groups = {}
-    for s in samples:
-        v = s["frames"]
-        if isinstance(v, StoredVideo):
-            groups.setdefault((id(v.store),) + v.shape[1:3], []).append(s)
-    for group in groups.values():
-        v = group[0]["frames"]
-        for s in group:
-            n = s["frames"].shape[0]
-            if any(not 0 <= i < n for i in s["frame_idx"]):
-                raise ValueError("frame index outside the video")
-        ids = [i for s in group for i in s["frames"].frame_ids(s["frame_idx"])]
-        buf = torch.empty((len(ids),) + v.shape[1:], dtype=torch.uint8, device=v.device)
-        v.store.decode_into(ids, buf)
-        at = 0
-        for s in group:
-            T = len(s["frame_idx"])
-            s["frames"], s["frame_idx"] = buf[at:at + T], range(T)
-            at += T
-
-
 def val_window_frames(n_frames, gamma_tau, sample_duration, crops):
     """The sorted 0-based frames of a video that the validation windows of kinetics.Kinetics draw (they do not depend on
     anything but these four numbers)."""
     from x3dhip.clip_input import val_crop_indices
     return sorted({int(i) for idx in val_crop_indices(n_frames, gamma_tau, sample_duration, crops) for i in idx})
+
+
+def add_folder(store, folder, want=None, chunk=256):
+    """Adds the 0-based frames `want` (None: all of them) of a FrameFolder to the store, `chunk` files at a time.  Returns
+    the range of their ids."""
+    want = range(folder.n_frames) if want is None else want
+    first = len(store)
+    for s in range(0, len(want), chunk):
+        store.add(folder.read(want[s:s + chunk]))
+    return range(first, len(store))
 
 
 def fill_store(store, entries, windows=None, chunk=256):
@@ -280,38 +243,21 @@ def fill_store(store, entries, windows=None, chunk=256):
     videos = []
     for folder, label in entries:
         index = None if windows is None else val_window_frames(folder.n_frames, **windows)
-        want = list(range(folder.n_frames)) if index is None else index
-        first = len(store)
-        for s in range(0, len(want), chunk):
-            store.add(folder.read(want[s:s + chunk]))
-        videos.append(dict(name="/".join(os.path.normpath(folder.path).split(os.sep)[-2:]), label=int(label), first=first,
-                           frames=len(want), n_frames=folder.n_frames, index=index))
+        ids = add_folder(store, folder, index, chunk)
+        videos.append(dict(name="/".join(os.path.normpath(folder.path).split(os.sep)[-2:]), label=int(label),
+                           first=ids.start, frames=len(ids), n_frames=folder.n_frames, index=index))
     return dict(videos=videos, windows=windows)
 
 
 class StoredKinetics(DeviceVideoKinetics):
-    """FolderKinetics over StoredVideos: the same draws from the parent (draw_clip_params / val_crop_indices /
-    center_crop_box), so that with equal rng seeds a batch is bit for bit the FolderKinetics batch; per batch the drawn
-    frames are decoded from the store by id (decode_stored), then the same clip kernels run."""
+    """DeviceVideoKinetics over the StoredVideos of one FrameStore (.store); meta: the pack meta they came with.  With
+    equal rng seeds a batch is bit for bit the FolderKinetics batch of the same videos."""
 
-    def __init__(self, videos, labels, sample_duration=80, gamma_tau=5, crop_size=224, x3d_version='M', rng=None, meta=None):
-        from x3dhip.clip_input import ClipPreprocessor
+    def __init__(self, videos, labels, *args, meta=None, **kw):
         if len(videos) != len(labels) or not videos:
             raise ValueError("one label per video, at least one video")
-        self.videos, self.labels, self.meta = list(videos), list(labels), meta
-        self.store = self.videos[0].store
-        self.sample_duration, self.gamma_tau, self.crop_size = sample_duration, gamma_tau, crop_size
-        self.long_cycles = long_cycle_shapes(sample_duration, crop_size)
-        self.scales = [crop_size / i for i in self.RESIZE[x3d_version]]
-        self.rng = rng if rng is not None else random
-        self.device = self.store.device
-        self._pre = ClipPreprocessor(self.device)
-
-    def pre(self, samples, out=None):
-        drawn = [dict(frames=v, frame_idx=list(p["frame_idx"])) for v, p in samples]
-        decode_stored(drawn)
-        clips = [(d["frames"], dict(p, frame_idx=list(d["frame_idx"]))) for d, (_, p) in zip(drawn, samples)]
-        return self._pre(clips, out=out)
+        super().__init__(list(videos), list(labels), *args, **kw)
+        self.store, self.meta = self.videos[0].store, meta
 
     @classmethod
     def from_annotation(cls, root, anno_json, labels_txt, subset, tier='device', device='cuda:0', threads=8,
@@ -321,7 +267,7 @@ class StoredKinetics(DeviceVideoKinetics):
         entries = list_annotation(root, anno_json, labels_txt, subset)[rank::world]
         if not entries:
             raise ValueError("rank %d of %d has no video of subset %r under %s" % (rank, world, subset, root))
-        store = FrameStore(device, threads=threads, tier=tier, **({} if chunk_bytes is None else dict(chunk_bytes=chunk_bytes)))
+        store = FrameStore(device, threads=threads, tier=tier, chunk_bytes=chunk_bytes)
         meta = fill_store(store, entries)
         return cls._over(store, meta, [range(v["first"], v["first"] + v["frames"]) for v in meta["videos"]], **kw)
 
@@ -336,9 +282,8 @@ class StoredKinetics(DeviceVideoKinetics):
         mine = meta["videos"][rank::world]
         if not mine:
             raise ValueError("rank %d of %d has no video of %s" % (rank, world, path))
-        store, _, id_map = FrameStore.load(path, device, tier=tier, ranges=[range(v["first"], v["first"] + v["frames"])
-                                                                            for v in mine],
-                                           **({} if chunk_bytes is None else dict(chunk_bytes=chunk_bytes)))
+        store, _, id_map = FrameStore.load(path, device, tier=tier, chunk_bytes=chunk_bytes,
+                                           ranges=[range(v["first"], v["first"] + v["frames"]) for v in mine])
         return cls._over(store, dict(meta, videos=mine), id_map, **kw)
 
     @classmethod
@@ -359,7 +304,7 @@ def charades_videos(root, anno, device, threads=8, entropy='host', resident='dec
         raise ValueError("resident must be 'decoded' or 'compressed' (got %r)" % (resident,))
     if resident == 'compressed':
         from x3dhip.jpegstore import FrameStore
-        store = FrameStore(device, threads=threads, tier=tier, **({} if chunk_bytes is None else dict(chunk_bytes=chunk_bytes)))
+        store = FrameStore(device, threads=threads, tier=tier, chunk_bytes=chunk_bytes)
     else:
         from x3dhip.jpegops import JpegDecoder
         dec = JpegDecoder(device, threads=threads, entropy=entropy)
@@ -370,12 +315,7 @@ def charades_videos(root, anno, device, threads=8, entropy='host', resident='dec
             continue
         name = FRAME_NAME if os.path.exists(os.path.join(path, FRAME_NAME.format(1))) else vid + '-{:06d}.jpg'
         if resident == 'compressed':
-            folder = FrameFolder(path, name)
-            ids = None
-            for s in range(0, folder.n_frames, 256):
-                r = store.add(folder.read(range(s, min(folder.n_frames, s + 256))))
-                ids = r if ids is None else range(ids.start, r.stop)
-            videos[vid] = StoredVideo(store, ids)
+            videos[vid] = StoredVideo(store, add_folder(store, FrameFolder(path, name)))
         else:
             videos[vid] = decode_folder(path, device, decoder=dec, name=name)
     return videos

@@ -1,8 +1,9 @@
 """Drop-in for the reference's `kinetics.py` (the validation dataset, kinetics.py:161-242): the videos of a subset of the
 annotation file, every video as `crops` temporal windows of `sample_duration // gamma_tau` frames, centre crop scaled to
-`crop_size`, read from folders of JPEG frames and decoded on the GPU (frames.FolderKinetics.val_batch), or held as prepared scans
-in a frame store in HBM or pinned host memory and decoded by frame id (Kinetics.from_dataset over
-frames.StoredKinetics: no file is opened during a validation pass).
+`crop_size`.  The clips come from kinetics_multigrid.DeviceVideoKinetics.val_batch, whatever form its videos have
+(frames.py): Kinetics(...) lists the subset and reads folders of JPEG frames, decoded on the GPU (frames.FolderKinetics);
+Kinetics.from_dataset takes a ready dataset, for one over a frame store in HBM or pinned host memory
+(frames.StoredKinetics: no file is opened during a validation pass).
 
     from kinetics import Kinetics
     val = Kinetics('data/kinetics/frames_val', 'kinetics_val.json', 'labels.txt', 'validate', sample_duration=80,
@@ -41,10 +42,10 @@ class Kinetics:
 
     @classmethod
     def from_dataset(cls, dataset, crops=10, sharded=None):
-        """Over a ready frames.FolderKinetics, frames.StoredKinetics (or kinetics_multigrid.DeviceVideoKinetics): anything
-        with __len__ and val_batch(indices, crops=).  sharded=(rank, world): the dataset already holds only the videos rank,
-        rank + world, ... of the listing (frames.StoredKinetics.from_pack(..., rank=, world=)); shard() and batches() then
-        take that rank and world only, and give all of it."""
+        """Over a ready kinetics_multigrid.DeviceVideoKinetics (frames.FolderKinetics and frames.StoredKinetics construct
+        one): anything with __len__ and val_batch(indices, crops=).  sharded=(rank, world): the dataset already holds only
+        the videos rank, rank + world, ... of the listing (frames.StoredKinetics.from_pack(..., rank=, world=)); shard() and
+        batches() then take that rank and world only, and give all of it."""
         self = cls.__new__(cls)
         self._init(dataset, crops)
         if sharded is not None:

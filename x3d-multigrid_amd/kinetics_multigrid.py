@@ -1,7 +1,7 @@
 """Synthetic stand-in for the reference's Kinetics multigrid dataset (kinetics_multigrid.py).
 
-The reference dataset decodes JPEG frame folders on NFS with PIL (here: frames.FolderKinetics, which decodes
-them on the GPU and then follows DeviceVideoKinetics below);
+The reference dataset decodes JPEG frame folders on NFS with PIL; here DeviceVideoKinetics below takes its videos decoded,
+as frame folders or as frames of a frame store alike (the lazy videos of frames.py, decoded on the GPU batch by batch);
 what matters for the hot path is the *shape protocol* of ``Kinetics.__getitem__``
 (kinetics_multigrid.py:214-259): the index carries (DataLoader task index, (sample, long-cycle
 state)), the clip comes back as float32 [3, T, H, W] with
@@ -13,6 +13,7 @@ zero-mean / unit-variance); ``device_batch`` produces a whole step's batch direc
 import torch
 
 from cycle_batch_sampler import long_cycle_shapes, step_clip_shape
+from x3dhip.clip_input import ClipPreprocessor, center_crop_box, draw_clip_params, gather_frames, val_crop_indices
 
 
 class SyntheticKinetics(torch.utils.data.Dataset):
@@ -45,32 +46,32 @@ def device_batch(B, T, H, n_classes, device, generator=None):
 
 
 class DeviceVideoKinetics:
-    """Kinetics.__getitem__'s protocol (kinetics_multigrid.py:214-259) over decoded uint8 videos that are already
-    resident in HBM: the per-sample random draws happen on the host in the reference's order
-    (x3dhip.clip_input.draw_clip_params), and crop + PIL-bilinear resize + flip + ToTensor + Normalize + the
+    """Kinetics.__getitem__'s protocol (kinetics_multigrid.py:214-259) over videos on one GPU: the per-sample random
+    draws happen on the host in the reference's order (x3dhip.clip_input.draw_clip_params), the frames drawn from lazy
+    videos are decoded (x3dhip.clip_input.gather_frames), and crop + PIL-bilinear resize + flip + ToTensor + Normalize + the
     [3,T,H,W] stacking run as two HIP kernels for the whole batch (x3dhip.clip_input.ClipPreprocessor over the clip
     kernels of libx3ddata.so).
 
-    videos: list of uint8 CUDA tensors [n_frames, H, W, 3]; labels: list of ints.  ``batch(indices, iteration,
-    long_cycle_state)`` returns (clips float32 [B,3,T,S,S], labels int64 [B,1], long_cycle_state, stats)."""
+    videos: list of uint8 CUDA tensors [n_frames, H, W, 3] or lazy videos (frames.FolderVideo, frames.StoredVideo), in any
+    mix; labels: list of ints.  ``batch(indices, iteration, long_cycle_state)`` returns (clips float32 [B,3,T,S,S],
+    labels int64 [B,1], long_cycle_state, stats)."""
 
     RESIZE = {'S': [180., 225.], 'M': [256., 320.], 'XL': [360., 450.]}      # train_x3d_kinetics_multigrid.py:54
 
     def __init__(self, videos, labels, sample_duration=80, gamma_tau=5, crop_size=224, x3d_version='M', rng=None):
         import random
-        from x3dhip.clip_input import ClipPreprocessor
         self.videos, self.labels = videos, labels
         self.sample_duration, self.gamma_tau, self.crop_size = sample_duration, gamma_tau, crop_size
         self.long_cycles = long_cycle_shapes(sample_duration, crop_size)
         self.scales = [crop_size / i for i in self.RESIZE[x3d_version]]       # train...:70
         self.rng = rng if rng is not None else random
-        self.pre = ClipPreprocessor(videos[0].device)
+        self.device = videos[0].device
+        self.pre = ClipPreprocessor(self.device)
 
     def __len__(self):
         return len(self.videos)
 
     def batch(self, indices, iteration, long_cycle_state, out=None):
-        from x3dhip.clip_input import draw_clip_params
         frames, crop = self.long_cycles[long_cycle_state]
         stats = (frames, crop // 2, int(crop / 2 ** 0.5), crop)
         T, S = step_clip_shape(long_cycle_state, iteration, self.sample_duration, self.gamma_tau, self.crop_size)
@@ -79,7 +80,9 @@ class DeviceVideoKinetics:
             v = self.videos[i]
             p = draw_clip_params(v.shape[0], v.shape[2], v.shape[1], self.scales, S, self.sample_duration, self.gamma_tau,
                                  frames, rng=self.rng)
-            samples.append((v, p))
+            p["frames"] = v
+            samples.append(p)
+        gather_frames(samples)
         clips = self.pre(samples, out=out)
         y = torch.tensor([[self.labels[i]] for i in indices], dtype=torch.int64, device=clips.device)
         return clips, y, long_cycle_state, stats
@@ -88,7 +91,6 @@ class DeviceVideoKinetics:
         """The validation dataset's batch (kinetics.py:205-239 with the transforms of train...:132-136): for every video
         `crops` temporal windows, centre crop scaled to crop_size, no flip.  Returns (clips float32
         [B, crops, 3, T, S, S], labels int64 [B]) -- what train_x3d_kinetics_multigrid.validate consumes."""
-        from x3dhip.clip_input import center_crop_box, val_crop_indices
         sd = self.sample_duration if sample_duration is None else sample_duration
         S = self.crop_size if crop_size is None else crop_size
         samples = []
@@ -96,7 +98,8 @@ class DeviceVideoKinetics:
             v = self.videos[i]
             x1, y1, crop = center_crop_box(v.shape[2], v.shape[1])
             for idx in val_crop_indices(v.shape[0], self.gamma_tau, sd, crops):
-                samples.append((v, dict(frame_idx=idx, x1=x1, y1=y1, crop=crop, out=S, flip=False)))
+                samples.append(dict(frames=v, frame_idx=idx, x1=x1, y1=y1, crop=crop, out=S, flip=False))
+        gather_frames(samples)
         clips = self.pre(samples)
         B = len(indices)
         y = torch.tensor([self.labels[i] for i in indices], dtype=torch.int64, device=clips.device)

@@ -1,6 +1,6 @@
 """Host side of the GPU clip input pipeline: the integer/random logic of the reference's per-sample transforms, the
-resample coefficient tables, and ClipPreprocessor, which hands a Kinetics step's samples to dataops.ClipBatcher (the
-clip kernels of csrc_data/clipbatch.hip, libx3ddata.so).
+resample coefficient tables, gather_frames (lazy videos -> the frames a batch draws, decoded), and ClipPreprocessor,
+which hands a Kinetics step's samples to dataops.ClipBatcher (the clip kernels of csrc_data/clipbatch.hip, libx3ddata.so).
 
 Reference call sites mirrored (random draws in the reference's order, from Python's `random` like the reference):
   kinetics_multigrid.py:240-253 (__getitem__), transforms/temporal_transforms.py:94-117 (TemporalRandomCrop),
@@ -109,11 +109,43 @@ def resize_coeffs(in_size, out_size):
     return out
 
 
+def is_lazy(video):
+    """Whether `video` is a lazy video rather than a decoded tensor: .shape = (n_frames, H, W, 3), .device, .source (an object
+    with decode_into(requests, dst)) and .requests(idx), what the source takes for the 0-based frames idx (frames.py)."""
+    return not isinstance(video, torch.Tensor) and all(hasattr(video, a) for a in ("shape", "device", "source", "requests"))
+
+
+def gather_frames(samples):
+    """samples: dicts with 'frames' and 'frame_idx' (as dataops.ClipBatcher takes them).  Every sample whose 'frames' is a
+    lazy video gets, in place, the uint8 tensor of exactly its frame_idx and frame_idx = range(len): one decode_into per
+    source and frame size over all samples, into one buffer.  A decoded tensor is left as it is."""
+    groups = {}
+    for s in samples:
+        v = s["frames"]
+        if is_lazy(v):
+            groups.setdefault((id(v.source),) + v.shape[1:3], []).append(s)
+    for group in groups.values():
+        v = group[0]["frames"]
+        for s in group:
+            n = s["frames"].shape[0]
+            if any(not 0 <= i < n for i in s["frame_idx"]):
+                raise ValueError("frame index outside the video")
+        requests = [r for s in group for r in s["frames"].requests(s["frame_idx"])]
+        buf = torch.empty((len(requests),) + v.shape[1:], dtype=torch.uint8, device=v.device)
+        v.source.decode_into(requests, buf)
+        at = 0
+        for s in group:
+            T = len(s["frame_idx"])
+            s["frames"], s["frame_idx"] = buf[at:at + T], range(T)
+            at += T
+
+
 class ClipPreprocessor:
     """Turns decoded uint8 videos resident on the GPU into the normalised float NCTHW batch of one training step: an
     adapter that lays the samples out for dataops.ClipBatcher (one job table, one scratch buffer, two launches).
 
-    samples: list of (frames uint8 CUDA tensor [Tsrc, H, W, 3], params dict from draw_clip_params); all samples of
+    samples: list of dicts with 'frames' (uint8 CUDA tensor [Tsrc, H, W, 3]) and the params of draw_clip_params
+    (frame_idx, x1, y1, crop, out, flip) -- what gather_frames rewrites -- or of (frames, params) pairs; all samples of
     a step share T and the output size (the multigrid schedule fixes both per step)."""
 
     def __init__(self, device, mean=KINETICS_MEAN, std=KINETICS_STD):
@@ -122,12 +154,13 @@ class ClipPreprocessor:
         self._batcher = ClipBatcher(self.device, mean, std)
 
     def __call__(self, samples, out=None):
-        B = len(samples)
-        T = len(samples[0][1]["frame_idx"])
-        S = samples[0][1]["out"]
+        pairs = [(s["frames"], s) if isinstance(s, dict) else s for s in samples]
+        B = len(pairs)
+        T = len(pairs[0][1]["frame_idx"])
+        S = pairs[0][1]["out"]
         batch = out if out is not None else torch.empty((B, 3, T, S, S), dtype=torch.float32, device=self.device)
         jobs = []
-        for b, (frames, p) in enumerate(samples):
+        for b, (frames, p) in enumerate(pairs):
             if len(p["frame_idx"]) != T or p["out"] != S:
                 raise ValueError("all samples of a step share T and the output size")
             jobs.append(dict(frames=frames, frame_idx=p["frame_idx"], x1=p["x1"], y1=p["y1"], crop=p["crop"],

@@ -11,6 +11,10 @@ entropy-coded bytes instead of the coefficients (about 1/18 of them), and one mo
 (x3djpeg_entropy_decode_batch, one workgroup per frame) fills the coefficient buffer the two kernels read, bit for bit
 what the host decoder writes.  A damaged scan is then found on the device: the per-frame status is read back once per
 batch, after the launches.
+
+HostStages holds the part of this that needs no device (the pool, the header parse, the scan preparation into plain host
+memory): jpegstore.FrameStore fills itself through one, and JpegDecoder is a HostStages whose staging buffer is pinned.
+check_dst, check_sub_bits and status_text are the argument checks and the status wording the decoder and the store share.
 """
 from concurrent.futures import ThreadPoolExecutor
 
@@ -32,6 +36,45 @@ def fill_jobs(jobs, infos):
     jobs["qt"] = np.take_along_axis(infos["qt"], tq[:, :, None].astype(np.int64), axis=1)
 
 
+def frame_jobs(infos, offs, coef, planes, targets):
+    """The X3DJpegFrameJob table of a batch: frame i's coefficients and planes at element offs[i] of the device buffers
+    coef (int16) and planes (uint8), its destination targets[i] = (data_ptr, row stride in bytes)."""
+    jobs = np.zeros(len(infos), dtype=FRAME_JOB_DT)
+    fill_jobs(jobs, infos)
+    jobs["coef"] = coef.data_ptr() + 2 * offs[:-1]
+    jobs["planes"] = planes.data_ptr() + offs[:-1]
+    jobs["dst"] = [t[0] for t in targets]
+    jobs["dst_stride"] = [t[1] for t in targets]
+    return jobs
+
+
+def check_sub_bits(sub_bits):
+    """The subsequence length of the device Huffman decoder as an int (None: the library's default), or ValueError."""
+    bits = SUB_BITS_DEFAULT if sub_bits is None else int(sub_bits)
+    if bits < 32 or bits % 32 or bits > 1 << 20:
+        raise ValueError("sub_bits must be a multiple of 32 in 32 .. 2^20 (got %r)" % (sub_bits,))
+    return bits
+
+
+def check_dst(dst, n, device):
+    """decode_into's destination: uint8 [n, H, W, 3] on `device`, unit stride over the channels, 3 over x, any row stride
+    >= 3 * W and any frame stride.  Returns (H, W), or ValueError."""
+    if (not isinstance(dst, torch.Tensor) or dst.device != device or dst.dtype != torch.uint8 or dst.dim() != 4
+            or dst.shape[3] != 3 or dst.shape[0] != n):
+        raise ValueError("dst must be a uint8 tensor [%d, H, W, 3] on %s" % (n, device))
+    _, H, W, _ = dst.shape
+    if dst.stride(3) != 1 or dst.stride(2) != 3 or dst.stride(1) < 3 * W or dst.stride(0) < 0:
+        raise ValueError("dst needs strides (any, >= 3 * W, 3, 1), got %s" % (tuple(dst.stride()),))
+    return H, W
+
+
+def status_text(rc):
+    """What a nonzero per-frame status of the device Huffman decoder says."""
+    if rc == _jpeglib.ECORRUPT:
+        return "corrupt JPEG: the device Huffman decoder refused the scan"
+    return "the scan job does not fit its sizes or its workspace"
+
+
 def read_header(data):
     """(width, height) of a JPEG file from its headers, without decoding; X3DHipError if the decoder does not take it."""
     rc, info, msg = _jpeglib.parse(bytes(data))
@@ -40,30 +83,17 @@ def read_header(data):
     return int(info["width"][0]), int(info["height"][0])
 
 
-class JpegDecoder:
-    """entropy: "host" (Huffman decoding in the thread pool) or "device" (on the GPU).  For "device": sub_bits is the
-    length of a subsequence in bits, a multiple of 32 (None: the library's default); check=False skips the read of the
-    per-frame status after a batch and leaves it, an int32 tensor on the device, in last_status."""
+class HostStages:
+    """The host work on a batch of files that needs no device: the thread pool, the header parse and the scan preparation
+    for the device Huffman decoder, into a reused staging buffer of plain host memory.  A FrameStore fills itself through
+    one; JpegDecoder is built on it.  threads is never sized from the machine's core count."""
 
-    def __init__(self, device, threads=8, entropy="host", sub_bits=None, check=True):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("JpegDecoder needs a GPU device (got %s)" % self.device)
-        if entropy not in ("host", "device"):
-            raise ValueError("entropy must be 'host' or 'device' (got %r)" % (entropy,))
-        self.entropy = entropy
-        self.sub_bits = SUB_BITS_DEFAULT if sub_bits is None else int(sub_bits)
-        if self.sub_bits < 32 or self.sub_bits % 32 or self.sub_bits > 1 << 20:
-            raise ValueError("sub_bits must be a multiple of 32 in 32 .. 2^20 (got %r)" % (sub_bits,))
-        self.check = bool(check)
-        self.last_status = None
-        self.last_bytes_copied = 0  # of the last batch's host-to-device copy of coefficients or scan bytes
-        self.threads = max(1, min(16, int(threads)))       # never sized from the machine's core count
+    def __init__(self, threads, sub_bits):
+        self.sub_bits = check_sub_bits(sub_bits)
+        self.threads = max(1, min(16, int(threads)))
         _jpeglib.lib()
         self._pool = ThreadPoolExecutor(max_workers=self.threads) if self.threads > 1 else None
-        self._pinned = None
-        self._pinned_bytes = None   # entropy="device": scans and segment tables
-        self._copied = None         # event after the last H2D copy out of the pinned buffer
+        self._buffers = {}          # dtype -> reused host buffer: scans and segment tables (uint8), coefficients (int16)
 
     def _chunks(self, fn, n):
         """fn(lo, hi) over [0, n) cut into one contiguous range per thread; the results in order.  A range per thread,
@@ -98,46 +128,18 @@ class JpegDecoder:
                 raise X3DHipError(msg)
         return infos
 
-    def _host_stage(self, frames):
-        """Headers and Huffman decoding of all frames.  Returns (infos, pinned int16 tensor holding the coefficients of
-        the frames back to back, element offsets).  Raises X3DHipError naming the first frame that fails."""
-        n = len(frames)
-        L = _jpeglib.lib()
-        infos = self._parse_stage(frames)
-        info_ptr, info_size = infos.ctypes.data, INFO_DT.itemsize
-        fail = self._fail
-        counts = infos["coef_count"].astype(np.int64)
-        offs = np.concatenate([[0], np.cumsum(counts)])
-        total = int(offs[-1])
-        if self._copied is not None:
-            self._copied.synchronize()                      # the previous batch's copy has left the pinned buffer
-        if self._pinned is None or self._pinned.numel() < total:
-            self._pinned = torch.empty(max(total, 1 << 16), dtype=torch.int16).pin_memory()
-        base = self._pinned.data_ptr()
-        at, size = (base + 2 * offs[:-1]).tolist(), (2 * counts).tolist()
+    def _alloc(self, n, dtype):
+        return torch.empty(n, dtype=dtype)
 
-        def decode(lo, hi):
-            out = []
-            for i in range(lo, hi):
-                rc = L.x3djpeg_entropy_decode(frames[i], len(frames[i]), info_ptr + i * info_size, at[i], size[i])
-                out.append(fail(i, rc) if rc else None)
-            return out
-
-        for msg in self._chunks(decode, n):
-            if msg:
-                raise X3DHipError(msg)
-        return infos, self._pinned[:total], offs
-
-    def _staging(self, total):
-        """The reused pinned byte buffer of _prepare_stage, at least `total` bytes, once nothing reads it any more."""
-        if self._copied is not None:
-            self._copied.synchronize()                      # the previous batch's copy has left the pinned buffer
-        if self._pinned_bytes is None or self._pinned_bytes.numel() < total:
-            self._pinned_bytes = torch.empty(max(total, 1 << 16), dtype=torch.uint8).pin_memory()
-        return self._pinned_bytes
+    def _staging(self, total, dtype=torch.uint8):
+        """The reused host buffer of `dtype`, at least `total` elements: its user has read it before the next call."""
+        buf = self._buffers.get(dtype)
+        if buf is None or buf.numel() < total:
+            buf = self._buffers[dtype] = self._alloc(max(total, 1 << 16), dtype)
+        return buf
 
     def _prepare_stage(self, frames):
-        """Headers and scan preparation of all frames for the device decoder.  Returns (infos, pinned uint8 tensor: per
+        """Headers and scan preparation of all frames for the device decoder.  Returns (infos, uint8 host tensor: per
         frame its unstuffed scan with padding, then per frame its segment table; byte offsets of the scans, of the tables;
         scan bytes, segments and workspace bytes per frame).  Raises X3DHipError naming the first frame that fails."""
         n = len(frames)
@@ -152,7 +154,8 @@ class JpegDecoder:
         scan_at = np.concatenate([[0], np.cumsum(cap)])
         seg_at = scan_at[-1] + np.concatenate([[0], np.cumsum(nseg * SCAN_SEG_DT.itemsize)])
         total = int(seg_at[-1])
-        base = self._staging(total).data_ptr()
+        staging = self._staging(total)
+        base = staging.data_ptr()
         written = np.zeros((n, 2), dtype=np.uint64)         # scan bytes, segments
         ws = np.zeros(n, dtype=np.int64)
         out_ptr = written.ctypes.data
@@ -172,7 +175,62 @@ class JpegDecoder:
         for msg in self._chunks(prepare, n):
             if msg:
                 raise X3DHipError(msg)
-        return infos, self._pinned_bytes[:total], scan_at, seg_at, written[:, 0].astype(np.int64), nseg, ws
+        return infos, staging[:total], scan_at, seg_at, written[:, 0].astype(np.int64), nseg, ws
+
+
+class JpegDecoder(HostStages):
+    """entropy: "host" (Huffman decoding in the thread pool) or "device" (on the GPU).  For "device": sub_bits is the
+    length of a subsequence in bits, a multiple of 32 (None: the library's default); check=False skips the read of the
+    per-frame status after a batch and leaves it, an int32 tensor on the device, in last_status."""
+
+    def __init__(self, device, threads=8, entropy="host", sub_bits=None, check=True):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("JpegDecoder needs a GPU device (got %s)" % self.device)
+        if entropy not in ("host", "device"):
+            raise ValueError("entropy must be 'host' or 'device' (got %r)" % (entropy,))
+        self.entropy = entropy
+        super().__init__(threads, sub_bits)
+        self.check = bool(check)
+        self.last_status = None
+        self.last_bytes_copied = 0  # of the last batch's host-to-device copy of coefficients or scan bytes
+        self._copied = None         # event after the last H2D copy out of a staging buffer
+
+    def _alloc(self, n, dtype):
+        return torch.empty(n, dtype=dtype).pin_memory()
+
+    def _staging(self, total, dtype=torch.uint8):
+        """Pinned, and only once the previous batch's copy has left it."""
+        if self._copied is not None:
+            self._copied.synchronize()
+        return super()._staging(total, dtype)
+
+    def _host_stage(self, frames):
+        """Headers and Huffman decoding of all frames.  Returns (infos, pinned int16 tensor holding the coefficients of
+        the frames back to back, element offsets).  Raises X3DHipError naming the first frame that fails."""
+        n = len(frames)
+        L = _jpeglib.lib()
+        infos = self._parse_stage(frames)
+        info_ptr, info_size = infos.ctypes.data, INFO_DT.itemsize
+        fail = self._fail
+        counts = infos["coef_count"].astype(np.int64)
+        offs = np.concatenate([[0], np.cumsum(counts)])
+        total = int(offs[-1])
+        pinned = self._staging(total, torch.int16)
+        base = pinned.data_ptr()
+        at, size = (base + 2 * offs[:-1]).tolist(), (2 * counts).tolist()
+
+        def decode(lo, hi):
+            out = []
+            for i in range(lo, hi):
+                rc = L.x3djpeg_entropy_decode(frames[i], len(frames[i]), info_ptr + i * info_size, at[i], size[i])
+                out.append(fail(i, rc) if rc else None)
+            return out
+
+        for msg in self._chunks(decode, n):
+            if msg:
+                raise X3DHipError(msg)
+        return infos, pinned[:total], offs
 
     def _stage_device(self, frames, dsts):
         """Everything of a device-path batch short of the launches: the host work, the copy of the scan bytes, the
@@ -196,12 +254,7 @@ class JpegDecoder:
             planes = torch.empty(total, dtype=torch.uint8, device=self.device)
             workspace = torch.empty(int(ws_off[-1]), dtype=torch.uint8, device=self.device)
             status = torch.empty(n, dtype=torch.int32, device=self.device)
-            jobs = np.zeros(n, dtype=FRAME_JOB_DT)
-            fill_jobs(jobs, infos)
-            jobs["coef"] = coef.data_ptr() + 2 * offs[:-1]
-            jobs["planes"] = planes.data_ptr() + offs[:-1]
-            jobs["dst"] = [t[0] for t in targets]
-            jobs["dst_stride"] = [t[1] for t in targets]
+            jobs = frame_jobs(infos, offs, coef, planes, targets)
             sj = np.zeros(n, dtype=SCAN_JOB_DT)
             _jpeglib.fill_scan_jobs(sj, infos)
             sj["scan"] = dev_bytes.data_ptr() + scan_at[:-1]
@@ -237,8 +290,7 @@ class JpegDecoder:
                 if bad.size:
                     i = int(bad[0])
                     raise X3DHipError("JPEG frame %d of the batch: libx3djpeg error %d: %s" % (
-                        i, int(st[i]), "corrupt JPEG: the device Huffman decoder refused the scan" if st[i] == _jpeglib.ECORRUPT
-                        else "the scan job does not fit its sizes or its workspace"))
+                        i, int(st[i]), status_text(st[i])))
 
     def _run(self, frames, dsts):
         """dsts(infos) -> per frame (data_ptr, row stride in bytes, tensor to keep alive), called after the host stage
@@ -259,12 +311,7 @@ class JpegDecoder:
             self._copied = torch.cuda.Event()
             self._copied.record()
             planes = torch.empty(total, dtype=torch.uint8, device=self.device)
-            jobs = np.zeros(n, dtype=FRAME_JOB_DT)
-            fill_jobs(jobs, infos)
-            jobs["coef"] = coef.data_ptr() + 2 * offs[:-1]
-            jobs["planes"] = planes.data_ptr() + offs[:-1]
-            jobs["dst"] = [t[0] for t in targets]
-            jobs["dst_stride"] = [t[1] for t in targets]
+            jobs = frame_jobs(infos, offs, coef, planes, targets)
             jd = torch.from_numpy(jobs.view(np.uint8)).to(self.device)
             _jpeglib.check(_jpeglib.lib().x3djpeg_decode_batch(
                 jd.data_ptr(), n, int(infos["nblocks"].max()), int(infos["width"].max()), int(infos["height"].max()),
@@ -301,12 +348,8 @@ class JpegDecoder:
     def decode_into(self, frames, dst):
         """frames: n files of one size; dst: uint8 [n, H, W, 3] on the device, unit stride over the channels, 3 over x, any
         row stride >= 3 * W and any frame stride.  ValueError when a frame's size is not dst's."""
-        if (not isinstance(dst, torch.Tensor) or dst.device != self.device or dst.dtype != torch.uint8 or dst.dim() != 4
-                or dst.shape[3] != 3 or dst.shape[0] != len(frames)):
-            raise ValueError("dst must be a uint8 tensor [%d, H, W, 3] on %s" % (len(frames), self.device))
-        n, H, W, _ = dst.shape
-        if dst.stride(3) != 1 or dst.stride(2) != 3 or dst.stride(1) < 3 * W or dst.stride(0) < 0:
-            raise ValueError("dst needs strides (any, >= 3 * W, 3, 1), got %s" % (tuple(dst.stride()),))
+        n = len(frames)
+        H, W = check_dst(dst, n, self.device)
 
         def dsts(infos):
             for i in range(n):

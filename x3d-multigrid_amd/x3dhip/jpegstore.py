@@ -37,9 +37,9 @@ import torch
 
 from . import _jpeglib
 from ._jpeglib import (FRAME_JOB_DT, SCAN_JOB_DT, SCAN_PAD, SCAN_SEG_DT, STORE_DST_DT, STORE_HEADER_DT, STORE_REC_DT,
-                       SUB_BITS_DEFAULT, stage_bytes)
+                       stage_bytes)
 from ._lib import X3DHipError, stream
-from .jpegops import JpegDecoder, fill_jobs
+from .jpegops import HostStages, check_dst, check_sub_bits, fill_jobs, status_text
 
 MIRROR_DT = np.dtype([("width", "<i4"), ("height", "<i4"), ("nblocks", "<i4"), ("scan_bytes", "<i4"), ("nseg", "<i4"),
                       ("chunk", "<i4"), ("coef_count", "<i8"), ("ws_need", "<i8")])
@@ -162,23 +162,6 @@ class NumpyMemory:
         return buf
 
 
-class _HostStages(JpegDecoder):
-    """JpegDecoder's parse and prepare stages on their own: the thread pool and the staging buffer, no device."""
-
-    def __init__(self, threads, sub_bits):
-        from concurrent.futures import ThreadPoolExecutor
-        self.sub_bits = sub_bits
-        self.threads = max(1, min(16, int(threads)))
-        self._pool = ThreadPoolExecutor(max_workers=self.threads) if self.threads > 1 else None
-        self._bytes = None
-
-    def _staging(self, total):                              # read by add() before it returns: plain memory will do
-        if self._bytes is None or self._bytes.numel() < total:
-            self._bytes = torch.empty(max(total, 1 << 16), dtype=torch.uint8)
-        self._pinned_bytes = self._bytes
-        return self._bytes
-
-
 class _Table:
     """A table on the device with its host copy, grown by doubling.  Growth writes a new buffer and leaves the old one to
     whoever still holds it (a planned batch)."""
@@ -276,36 +259,32 @@ class Batch:
             i = int(bad[0]) if bad.size else -1
             raise X3DHipError("JPEG frame %d of the batch: libx3djpeg error %d: %s" % (
                 i, int(st[i]) if bad.size else _jpeglib.EINVAL,
-                what % ", ".join(why) if why else
-                "corrupt JPEG: the device Huffman decoder refused the scan" if st[i] == _jpeglib.ECORRUPT else
-                "the scan job does not fit its sizes or its workspace"))
+                what % ", ".join(why) if why else status_text(st[i])))
 
 
 class FrameStore:
-    """device: where the frames live.  chunk_bytes: the size of an arena chunk (a frame larger than that gets a chunk of
-    its own).  sub_bits: the subsequence length of the device Huffman decoder (None: the library's default), fixed for the
-    store since the workspace a frame needs depends on it.  threads: host threads of add().  check=False skips the read of
+    """device: where the frames live.  chunk_bytes: the size of an arena chunk (None: 64 MiB; a frame larger than that gets
+    a chunk of its own).  sub_bits: the subsequence length of the device Huffman decoder (None: the library's default),
+    fixed for the store since the workspace a frame needs depends on it.  threads: host threads of add() (a
+    jpegops.HostStages: no device is involved in filling).  check=False skips the read of
     the status words after decode / decode_into and leaves the batch in last_batch.  memory: see TorchMemory.  tier:
     "device" keeps the arena chunks where the tables are; "host" keeps them in pinned host memory (PinnedMemory) and
     decodes through a staging buffer per batch.  A `memory` given by the caller holds tables and chunks alike."""
 
-    def __init__(self, device, chunk_bytes=64 << 20, sub_bits=None, threads=2, check=True, memory=None, tier="device"):
+    def __init__(self, device, chunk_bytes=None, sub_bits=None, threads=2, check=True, memory=None, tier="device"):
         if tier not in TIERS:
             raise ValueError("tier must be one of %s (got %r)" % (", ".join(TIERS), tier))
         self.tier = tier
         self.memory = memory if memory is not None else TorchMemory(device)
         self.arena_memory = PinnedMemory() if tier == "host" and memory is None else self.memory
         self.device = torch.device(device)
-        self.sub_bits = SUB_BITS_DEFAULT if sub_bits is None else int(sub_bits)
-        if self.sub_bits < 32 or self.sub_bits % 32 or self.sub_bits > 1 << 20:
-            raise ValueError("sub_bits must be a multiple of 32 in 32 .. 2^20 (got %r)" % (sub_bits,))
-        self.chunk_bytes = int(chunk_bytes)
+        self.sub_bits = check_sub_bits(sub_bits)
+        self.chunk_bytes = 64 << 20 if chunk_bytes is None else int(chunk_bytes)
         if self.chunk_bytes < 16 or self.chunk_bytes % 16:
             raise ValueError("chunk_bytes must be a positive multiple of 16 (got %r)" % (chunk_bytes,))
         self.check = bool(check)
         self.last_batch = None
-        _jpeglib.lib()
-        self._stages = _HostStages(threads, self.sub_bits)
+        self._stages = HostStages(threads, self.sub_bits)
         self._chunks = []            # [buffer, bytes, bytes used]
         self._recs = _Table(self.memory, STORE_REC_DT, 1024)
         self._headers = _Table(self.memory, STORE_HEADER_DT, 8)
@@ -483,12 +462,8 @@ class FrameStore:
         over x, any row stride >= 3 * W and any frame stride.  ValueError for an id outside the store or a frame whose size
         is not dst's, before anything is launched."""
         ids = self._ids(ids)
-        if (not isinstance(dst, torch.Tensor) or dst.device != self.device or dst.dtype != torch.uint8 or dst.dim() != 4
-                or dst.shape[3] != 3 or dst.shape[0] != ids.size):
-            raise ValueError("dst must be a uint8 tensor [%d, H, W, 3] on %s" % (ids.size, self.device))
-        n, H, W, _ = dst.shape
-        if dst.stride(3) != 1 or dst.stride(2) != 3 or dst.stride(1) < 3 * W or dst.stride(0) < 0:
-            raise ValueError("dst needs strides (any, >= 3 * W, 3, 1), got %s" % (tuple(dst.stride()),))
+        n = ids.size
+        H, W = check_dst(dst, n, self.device)
         w, h = self._mirror["width"][ids], self._mirror["height"][ids]
         bad = np.flatnonzero((w != W) | (h != H))
         if bad.size:
