@@ -31,7 +31,9 @@
  * one workgroup per frame, by many decoders that start at fixed bit offsets (every sub_bits bits of a segment) and are
  * relaxed until each starts in the state its predecessor ended in (JPEG Huffman streams self-synchronise; Weissenberger
  * & Schmidt, "Accelerating JPEG decompression on GPUs").  x3djpeg_entropy_decode_parallel_host runs the same scheme
- * through the same code (csrc_jpeg/entropy_core.h) serially on the CPU.
+ * through the same code (csrc_jpeg/entropy_core.h) serially on the CPU.  For frames that are stored, the states the
+ * relaxation converges to can be computed once and kept (x3djpeg_index_build): x3djpeg_entropy_decode_indexed then fills
+ * the same buffer in one pass and checks the index as it goes ("Sync index" below).
  */
 #ifndef X3DJPEG_H
 #define X3DJPEG_H
@@ -50,6 +52,7 @@ extern "C" {
 #define X3DJPEG_ELAUNCH (-2)       /* hipLaunch error */
 #define X3DJPEG_EUNSUPPORTED (-3)  /* a valid file of a kind this decoder does not take; the message names the feature */
 #define X3DJPEG_ECORRUPT (-4)      /* truncated or inconsistent stream */
+#define X3DJPEG_EINDEX (-5)        /* a sync index that does not describe the scan it is used with */
 
 /* What x3djpeg_parse reads from the headers of one file. */
 typedef struct X3DJpegInfo {
@@ -269,6 +272,62 @@ int x3djpeg_stage_host(const void* recs, int nrecs, const void* ids, int n, size
  * is X3DJPEG_ELAUNCH with the byte count in the message. */
 int x3djpeg_pinned_alloc(size_t bytes, void** host, void** dev);
 int x3djpeg_pinned_free(void* host);
+
+/* Sync index: what the relaxation of x3djpeg_entropy_decode_batch finds out again for every batch -- the decoder state at
+ * the start of every subsequence -- depends only on the stored bytes, so it can be computed once, on the host, when a
+ * frame is stored.  An index covers one frame at one granularity index_bits (as sub_bits: a multiple of 32, 32 .. 2^20)
+ * and holds one 8-byte entry per subsequence of every segment, in the order the relaxation decoder numbers them
+ * (x3djpeg_index_count of them).  An entry is two uint32 words:
+ *     word 0   p, the bit position within the segment
+ *     word 1   b (bits 0-2, the block within the MCU) | k << 3 (bits 3-9, the zigzag index) | first << 10 (bits 10-31,
+ *              the index within the segment of the block the state is in)
+ * Entry 0 of a segment is all zero.  Entry i + 1 is the state in which the serial decoder stands at the first symbol
+ * boundary (a Huffman code with its extra bits is one symbol) at or after bit (i + 1) * index_bits of the segment, or, if
+ * the segment's last block ends before that bit, the state at that end (b 0, k 0, first the segment's block count).
+ * A segment of 2^22 blocks or more cannot be indexed.
+ *
+ * Cost: 8 bytes per index_bits bits of scan -- 6.25 % of the scan bytes at 1024, 12.5 % at 512. */
+#define X3DJPEG_INDEX_BITS_DEFAULT 512    /* the fastest end to end: profiles/jpeg_index/README.md */
+#define X3DJPEG_INDEX_MAX_BLOCKS (1 << 22)
+
+/* Where a stored frame's entries are: entries [first_entry, first_entry + nentries) of the entry array.  The table
+ * [nrecs] is parallel to the store's record table: it is indexed by frame id. */
+typedef struct X3DJpegIndexRec {
+    int64_t first_entry;
+    int32_t nentries;
+    int32_t pad;
+} X3DJpegIndexRec;
+
+size_t x3djpeg_index_rec_bytes(void);
+/* Entries of a frame with these segments; 0 for an index_bits the decoder does not take (or segs null). */
+size_t x3djpeg_index_count(const X3DJpegScanSeg* segs, size_t nseg, int index_bits);
+/* Host, no HIP call: the index of one prepared scan (what x3djpeg_scan_prepare wrote for `info`), one serial pass per
+ * segment through csrc_jpeg/entropy_core.h, into entries[0, cap); *n receives the count.  X3DJPEG_ECORRUPT exactly where
+ * x3djpeg_entropy_decode refuses the file; X3DJPEG_EUNSUPPORTED for a segment of X3DJPEG_INDEX_MAX_BLOCKS blocks or more;
+ * X3DJPEG_EINVAL for a null pointer, a bad index_bits, a segment table that is not the scan's, or cap too small. */
+int x3djpeg_index_build(const uint8_t* scan, size_t scan_bytes, const X3DJpegScanSeg* segs, size_t nseg,
+                        const X3DJpegInfo* info, int index_bits, uint64_t* entries, size_t cap, size_t* n);
+
+/* Huffman decoding of njobs prepared scans from their sync indices: one workgroup per frame, one launch, one pass over
+ * each scan, no workspace.  jobs: the X3DJpegScanJob [njobs] x3djpeg_store_build_jobs wrote (ws_off and ws_bytes are not
+ * read); ids: int32 [njobs], the frame id of each job in the index tables (for a host-tier store the ids before
+ * x3djpeg_stage, not the staged ones); index_recs: X3DJpegIndexRec [nrecs]; entries: the entry array, entries_total
+ * entries, 8-byte aligned; status: int32 [njobs].  All on the device.
+ *
+ * Per frame the status is 0, X3DJPEG_EINVAL (a job that does not fit its own sizes; an id outside [0, nrecs); a record
+ * outside the entry array; nentries that is not x3djpeg_index_count of the job's own segment table), X3DJPEG_EINDEX (an
+ * entry that is not what the index rule gives for this scan) or X3DJPEG_ECORRUPT (a stream the host decoder refuses too).
+ * Every worker decodes its subsequences from their entries and compares the state it ends in -- p, b, k and the block --
+ * with the next entry of the segment; the first entry of a segment is compared with the start state.  So status 0 means:
+ * entry 0 was exact and every hand-over matched, and by induction the coefficients are the serial decoder's.  Whatever
+ * the entries hold, every scan read is checked against the segment, every store against coef_count and every loop is
+ * bounded by the segment's bits: a failed frame's coefficients are unspecified but stay inside its own range, and the
+ * other frames are not affected. */
+int x3djpeg_entropy_decode_indexed(const void* jobs, int njobs, const void* ids, const void* index_recs, int nrecs,
+                                   const void* entries, size_t entries_total, int index_bits, void* status, void* stream);
+/* The same through the same code (csrc_jpeg/index_core.h) serially on the CPU; every pointer is a host pointer. */
+int x3djpeg_entropy_decode_indexed_host(const void* jobs, int njobs, const void* ids, const void* index_recs, int nrecs,
+                                        const void* entries, size_t entries_total, int index_bits, void* status);
 
 #ifdef __cplusplus
 }

@@ -169,14 +169,18 @@ X3DJ_HD static inline int32_t seg_nsub(uint32_t byte_len, int32_t sub_bits) {
 }
 
 // By one worker.  Checks the job against itself (the rest of the code relies on nothing else) and derives the context;
-// X3DJPEG_EINVAL if it does not hold together.  tables: storage for 8 HuffTables (DC 0-3, AC 0-3).
-X3DJ_HD static inline int setup(const X3DJpegScanJob& J, int sub_bits, uint8_t* workspace, int64_t workspace_bytes,
-                                const HuffTable* tables, FrameCtx* C) {
+// X3DJPEG_EINVAL if it does not hold together.  tables: storage for 8 HuffTables (DC 0-3, AC 0-3).  WS: with the frame's
+// part of the workspace and its coefficient buffer (setup); without, neither is looked at and every workspace pointer of
+// the context is null (setup_frame: the indexed decoder of index_core.h starts from that alone).
+template <bool WS>
+X3DJ_HD static inline int setup_any(const X3DJpegScanJob& J, int sub_bits, uint8_t* workspace, int64_t workspace_bytes,
+                                    const HuffTable* tables, FrameCtx* C) {
     const int nc = J.ncomp;
     bool ok = (nc == 1 || nc == 3) && J.mcus_x > 0 && J.mcus_y > 0 && J.mcus_x <= 8192 && J.mcus_y <= 8192 && J.scan &&
-              J.segs && J.coef && J.scan_bytes >= 0 && J.scan_bytes <= X3DJPEG_SCAN_MAX_BYTES && J.restart_interval >= 0 &&
-              sub_bits >= 32 && sub_bits % 32 == 0 && sub_bits <= (1 << 20) && J.ws_off >= 0 && J.ws_off % 16 == 0 &&
-              J.ws_bytes >= 16 && J.ws_off <= workspace_bytes && J.ws_bytes <= workspace_bytes - J.ws_off && workspace;
+              J.segs && (!WS || J.coef) && J.scan_bytes >= 0 && J.scan_bytes <= X3DJPEG_SCAN_MAX_BYTES &&
+              J.restart_interval >= 0 && sub_bits >= 32 && sub_bits % 32 == 0 && sub_bits <= (1 << 20) &&
+              (!WS || (J.ws_off >= 0 && J.ws_off % 16 == 0 && J.ws_bytes >= 16 && J.ws_off <= workspace_bytes &&
+                       J.ws_bytes <= workspace_bytes - J.ws_off && workspace));
     if (!ok) return X3DJPEG_EINVAL;
     int64_t nb = 0;
     int bpm = 0;
@@ -204,7 +208,7 @@ X3DJ_HD static inline int setup(const X3DJpegScanJob& J, int sub_bits, uint8_t* 
     C->ri = J.restart_interval;
     const int64_t want_seg = C->ri ? ((int64_t)C->nmcu + C->ri - 1) / C->ri : 1;
     if (J.coef_count != nb * 64 || J.nseg != want_seg) return X3DJPEG_EINVAL;
-    if (workspace_need(J.nseg, J.nseg) > J.ws_bytes) return X3DJPEG_EINVAL;  // at least one subsequence per segment
+    if (WS && workspace_need(J.nseg, J.nseg) > J.ws_bytes) return X3DJPEG_EINVAL;  // at least one subsequence per segment
     C->scan = J.scan;
     C->segs = J.segs;
     C->coef = J.coef;
@@ -216,16 +220,35 @@ X3DJ_HD static inline int setup(const X3DJpegScanJob& J, int sub_bits, uint8_t* 
     C->ncomp = nc;
     C->bpm = bpm;
     C->mcus_x = J.mcus_x;
-    C->ws_bytes = J.ws_bytes;
-    C->head = (int32_t*)(workspace + J.ws_off);
-    C->seg_first = C->head + 4;
-    C->head[0] = 0;
-    C->head[1] = 0;
+    if (WS) {
+        C->ws_bytes = J.ws_bytes;
+        C->head = (int32_t*)(workspace + J.ws_off);
+        C->seg_first = C->head + 4;
+        C->head[0] = 0;
+        C->head[1] = 0;
+    } else {
+        C->ws_bytes = 0;
+        C->head = nullptr;
+        C->seg_first = nullptr;
+        C->sub_seg = nullptr;
+        C->entry = nullptr;
+        C->exits = nullptr;
+        C->cnt = nullptr;
+    }
     const uint8_t zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
     for (int i = 0; i < 64; ++i) C->zigzag[i] = zz[i];
     return X3DJPEG_OK;
+}
+
+X3DJ_HD static inline int setup(const X3DJpegScanJob& J, int sub_bits, uint8_t* workspace, int64_t workspace_bytes,
+                                const HuffTable* tables, FrameCtx* C) {
+    return setup_any<true>(J, sub_bits, workspace, workspace_bytes, tables, C);
+}
+
+X3DJ_HD static inline int setup_frame(const X3DJpegScanJob& J, int sub_bits, const HuffTable* tables, FrameCtx* C) {
+    return setup_any<false>(J, sub_bits, nullptr, 0, tables, C);
 }
 
 // worker tid's share of [0, n): contiguous, in order of tid
@@ -295,19 +318,17 @@ X3DJ_HD static inline void seg_place(const FrameCtx& C, int tid, int nt, const i
     }
 }
 
-enum { kRun = 0, kWrite = 1 };
+enum { kRun = 0, kWrite = 1, kCheck = 2 };
 
-// Decodes subsequence i from state (*p, *bk).  kRun: until the subsequence ends; bad codes are skipped; *blocks gets the
-// blocks completed.  kWrite: from an exact state, with first_block the index within the segment of the block the state is
-// in; stores coefficients, stops at the subsequence's end or at the segment's last block (the last subsequence of a
-// segment runs on until then), returns nonzero where the host decoder does.
+// Decodes subsequence `local` of segment s (g: its table entry; last: it is the segment's last) from state (*p, *bk).
+// kRun: until the subsequence ends; bad codes are skipped; *blocks gets the blocks completed.  kWrite: from an exact
+// state, with first_block the index within the segment of the block the state is in; stores coefficients, stops at the
+// subsequence's end or at the segment's last block (the last subsequence of a segment runs on until then), returns nonzero
+// where the host decoder does.  kCheck: kWrite in every check and every state it leaves, without the stores (C.coef is
+// not touched).
 template <int MODE>
-X3DJ_HD static inline int decode_sub(const FrameCtx& C, int32_t i, uint32_t* p_io, uint32_t* bk_io, int32_t first_block,
-                                     int32_t* blocks) {
-    const int32_t s = C.sub_seg[i];
-    const X3DJpegScanSeg g = C.segs[s];
-    const int32_t local = i - C.seg_first[s];
-    const bool last = i + 1 == C.nsub || C.sub_seg[i + 1] != s;
+X3DJ_HD static inline int decode_span(const FrameCtx& C, int32_t s, const X3DJpegScanSeg g, int32_t local, bool last,
+                                      uint32_t* p_io, uint32_t* bk_io, int32_t first_block, int32_t* blocks) {
     const uint32_t seg_bits = g.byte_len * 8u;
     const uint32_t end = last ? seg_bits : (uint32_t)(local + 1) * (uint32_t)C.sub_bits;
     const int32_t total = g.mcu_count * C.bpm;  // blocks of the segment
@@ -328,16 +349,16 @@ X3DJ_HD static inline int decode_sub(const FrameCtx& C, int32_t i, uint32_t* p_i
         const int64_t off = C.coef_off[c] +
                             ((int64_t)(my * C.comp_v[c] + C.blk_by[b]) * C.blocks_w[c] + (mx * C.comp_h[c] + C.blk_bx[b])) * 64;
         if (off < 0 || off + 64 > C.coef_count) return false;
-        blk = C.coef + off;
+        if (MODE == kWrite) blk = C.coef + off;
         return true;
     };
-    if (MODE == kWrite) {
+    if (MODE != kRun) {
         if (first_block >= total) return 0;  // the segment's blocks ended in an earlier subsequence
         if (!locate(first_block)) return X3DJPEG_EINVAL;
     }
     uint32_t p = br.bitpos();
     for (;;) {
-        if (MODE == kWrite) {
+        if (MODE != kRun) {
             if (last) {
                 if (p > seg_bits) return X3DJPEG_ECORRUPT;  // scan data ends inside an MCU
             } else if (p >= end) {
@@ -383,14 +404,14 @@ X3DJ_HD static inline int decode_sub(const FrameCtx& C, int32_t i, uint32_t* p_i
             }
         }
         if (bad) {
-            if (MODE == kWrite) return X3DJPEG_ECORRUPT;
+            if (MODE != kRun) return X3DJPEG_ECORRUPT;
             br.seek(p + 1);
             k = 0;
         } else if (k >= 64) {
             k = 0;
             ++done;
             b = b + 1 == C.bpm ? 0 : b + 1;
-            if (MODE == kWrite) {
+            if (MODE != kRun) {
                 if (first_block + done >= total) {
                     // the segment's last block: the host's checks at a restart marker and at the end of the scan
                     p = br.bitpos();
@@ -407,6 +428,17 @@ X3DJ_HD static inline int decode_sub(const FrameCtx& C, int32_t i, uint32_t* p_i
     *bk_io = (uint32_t)b | ((uint32_t)k << 8);
     *blocks = done;
     return 0;
+}
+
+// Subsequence i of the frame, through the workspace's subsequence -> segment map.
+template <int MODE>
+X3DJ_HD static inline int decode_sub(const FrameCtx& C, int32_t i, uint32_t* p_io, uint32_t* bk_io, int32_t first_block,
+                                     int32_t* blocks) {
+    const int32_t s = C.sub_seg[i];
+    const X3DJpegScanSeg g = C.segs[s];
+    const int32_t local = i - C.seg_first[s];
+    const bool last = i + 1 == C.nsub || C.sub_seg[i + 1] != s;
+    return decode_span<MODE>(C, s, g, local, last, p_io, bk_io, first_block, blocks);
 }
 
 X3DJ_HD static inline void run_sub(const FrameCtx& C, int32_t i) {

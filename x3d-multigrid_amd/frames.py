@@ -261,20 +261,22 @@ class StoredKinetics(DeviceVideoKinetics):
 
     @classmethod
     def from_annotation(cls, root, anno_json, labels_txt, subset, tier='device', device='cuda:0', threads=8,
-                        chunk_bytes=None, rank=0, world=1, **kw):
-        """The listing of FolderKinetics.from_annotation, its videos i % world == rank read into a FrameStore of `tier`."""
+                        chunk_bytes=None, rank=0, world=1, index_bits=None, **kw):
+        """The listing of FolderKinetics.from_annotation, its videos i % world == rank read into a FrameStore of `tier`
+        (index_bits: with a sync index of that granularity; None: without)."""
         from x3dhip.jpegstore import FrameStore
         entries = list_annotation(root, anno_json, labels_txt, subset)[rank::world]
         if not entries:
             raise ValueError("rank %d of %d has no video of subset %r under %s" % (rank, world, subset, root))
-        store = FrameStore(device, threads=threads, tier=tier, chunk_bytes=chunk_bytes)
+        store = FrameStore(device, threads=threads, tier=tier, chunk_bytes=chunk_bytes, index_bits=index_bits)
         meta = fill_store(store, entries)
         return cls._over(store, meta, [range(v["first"], v["first"] + v["frames"]) for v in meta["videos"]], **kw)
 
     @classmethod
-    def from_pack(cls, path, device='cuda:0', tier='device', rank=0, world=1, chunk_bytes=None, **kw):
+    def from_pack(cls, path, device='cuda:0', tier='device', rank=0, world=1, chunk_bytes=None, index_bits=None, **kw):
         """The videos i % world == rank of a pack file (tools/pack_frames.py, or FrameStore.save with fill_store's meta):
-        only their frames are read."""
+        only their frames are read.  index_bits: None uses the pack's sync index if it has one beside it (path + '.idx');
+        an int builds an index of that granularity while loading."""
         from x3dhip.jpegstore import FrameStore
         meta = FrameStore.read_meta(path)
         if not isinstance(meta, dict) or not isinstance(meta.get("videos"), list):
@@ -282,7 +284,7 @@ class StoredKinetics(DeviceVideoKinetics):
         mine = meta["videos"][rank::world]
         if not mine:
             raise ValueError("rank %d of %d has no video of %s" % (rank, world, path))
-        store, _, id_map = FrameStore.load(path, device, tier=tier, chunk_bytes=chunk_bytes,
+        store, _, id_map = FrameStore.load(path, device, tier=tier, chunk_bytes=chunk_bytes, index=index_bits,
                                            ranges=[range(v["first"], v["first"] + v["frames"]) for v in mine])
         return cls._over(store, dict(meta, videos=mine), id_map, **kw)
 
@@ -293,18 +295,20 @@ class StoredKinetics(DeviceVideoKinetics):
         return cls(videos, [v["label"] for v in meta["videos"]], meta=meta, **kw)
 
 
-def charades_videos(root, anno, device, threads=8, entropy='host', resident='decoded', chunk_bytes=None, tier='device'):
+def charades_videos(root, anno, device, threads=8, entropy='host', resident='decoded', chunk_bytes=None, tier='device',
+                    index_bits=None):
     """{video id: video} for every video of the annotation dict that has a folder under root: the `videos` argument of
     charades.Charades and the Charades training scripts.  resident='decoded': uint8 [n, H, W, 3], decoded whole.
     resident='compressed': StoredVideo over one FrameStore shared by all videos (chunk_bytes: its arena chunk size),
     decoded batch by batch on the GPU, Huffman decoding included; `entropy` is not used then; tier: where that store
-    keeps its frames ('device', or 'host': pinned host memory).  Frames are named
+    keeps its frames ('device', or 'host': pinned host memory); index_bits: that store keeps a sync index of that
+    granularity and decodes through it.  Frames are named
     frame_%05d.jpg or, as in the reference's Charades loader (charades.py:47), <video id>-%06d.jpg."""
     if resident not in ('decoded', 'compressed'):
         raise ValueError("resident must be 'decoded' or 'compressed' (got %r)" % (resident,))
     if resident == 'compressed':
         from x3dhip.jpegstore import FrameStore
-        store = FrameStore(device, threads=threads, tier=tier, chunk_bytes=chunk_bytes)
+        store = FrameStore(device, threads=threads, tier=tier, chunk_bytes=chunk_bytes, index_bits=index_bits)
     else:
         from x3dhip.jpegops import JpegDecoder
         dec = JpegDecoder(device, threads=threads, entropy=entropy)

@@ -39,6 +39,10 @@ def main(argv=None):
     parser.add_argument('--version', default=tk.X3D_VERSION)
     parser.add_argument('--bf16', action='store_true', help='bf16 storage of the wide bottleneck tensors (fp32 arithmetic)')
     parser.add_argument('--decode-threads', type=int, default=8, help='host threads that prepare the frames (1..16)')
+    parser.add_argument('--index-bits', type=int, nargs='?', const=True, default=None,
+                        help='keep a sync index of the stored frames, one entry per that many bits of scan, and Huffman decode '
+                             'through it in one pass; no value: the library\'s default.  A pack with its index beside it '
+                             '(PACK.idx) is used indexed without this')
     args = parser.parse_args(argv)
     if args.pack is None and (args.frames_root is None or args.anno is None or args.labels is None):
         parser.error('give --pack, or --frames-root, --anno and --labels')
@@ -46,7 +50,8 @@ def main(argv=None):
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5, 'L': 5}[args.version]
     crop_size = {'S': 160, 'M': 224, 'XL': 312, 'L': 312}[args.version]
-    kw = dict(root=args.frames_root, anno=args.anno, labels=args.labels, subset=args.subset, threads=args.decode_threads)
+    kw = dict(root=args.frames_root, anno=args.anno, labels=args.labels, subset=args.subset, threads=args.decode_threads,
+              index_bits=args.index_bits)
     stored = tk.stored_dataset(frames, args.resident, args.pack, kw, args.subset, rank, world,
                                dict(sample_duration=files_script.FRAMES, gamma_tau=gamma_tau, crop_size=crop_size, device=dev))
     dataset = Kinetics.from_dataset(stored, args.crops, sharded=(rank, world))

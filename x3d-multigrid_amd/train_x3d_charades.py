@@ -99,6 +99,10 @@ def main(run_fn, default_save):
     parser.add_argument('--resident', choices=('decoded', 'compressed'), default='decoded',
                         help='how the videos of --frames-root stay in HBM: decoded whole, or as prepared JPEG scans in a frame '
                              'store, decoded batch by batch (implies the GPU Huffman decoder)')
+    parser.add_argument('--index-bits', type=int, nargs='?', const=True, default=None,
+                        help='with --resident compressed: keep a sync index of the stored frames, one entry per that many bits '
+                             'of scan, and Huffman decode through it in one pass (x3djpeg_entropy_decode_indexed); no value: '
+                             'the library\'s default')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -110,7 +114,7 @@ def main(run_fn, default_save):
             with open(args.anno, 'r') as f:
                 anno = json.load(f)
             size['videos'] = frames.charades_videos(args.frames_root, anno, str(dev), entropy=args.jpeg_entropy,
-                                                       resident=args.resident)
+                                                       resident=args.resident, index_bits=args.index_bits)
         run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version,
                load_ckpt=args.load, resume=args.resume, save_model=args.save, save_every=args.save_every,
                use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,

@@ -188,12 +188,13 @@ def stored_dataset(frames_mod, resident, pack, kw, subset, rank, world, common):
         raise ValueError("resident must be 'files', 'hbm' or 'host' (got %r)" % (resident,))
     kw = dict(kw)
     kw.pop('entropy', None)                      # a store decodes on the GPU, Huffman stage included
-    threads = kw.pop('threads', 8)
+    threads, index_bits = kw.pop('threads', 8), kw.pop('index_bits', None)
     if pack is not None:
-        return frames_mod.StoredKinetics.from_pack(pack, tier=TIERS[resident], rank=rank, world=world, **common)
+        return frames_mod.StoredKinetics.from_pack(pack, tier=TIERS[resident], rank=rank, world=world,
+                                                   index_bits=index_bits, **common)
     return frames_mod.StoredKinetics.from_annotation(kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', subset),
                                                      tier=TIERS[resident], threads=threads, rank=rank, world=world,
-                                                     **common, **kw)
+                                                     index_bits=index_bits, **common, **kw)
 
 
 def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_UPSCALE, steps=0, max_steps_run=None,
@@ -279,6 +280,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                           x3d_version='XL' if x3d_version == 'L' else x3d_version, rng=random.Random(4321 + rank), device=dev)
             resident, pack = kw.pop('resident', 'files'), kw.pop('pack', None)
             if resident == 'files':
+                kw.pop('index_bits', None)       # a sync index belongs to a store
                 folder_ds = frames_mod.FolderKinetics.from_annotation(
                     kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'train'), **common, **kw)
             else:
@@ -296,6 +298,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
             kw = dict(val_frames)
             resident, pack = kw.pop('resident', 'files'), kw.pop('pack', None)
             if resident == 'files':
+                kw.pop('index_bits', None)       # a sync index belongs to a store
                 val_ds = kinetics.Kinetics(kw.pop('root'), kw.pop('anno'), kw.pop('labels'), kw.pop('subset', 'validate'),
                                            sample_duration=frames, gamma_tau=gamma_tau, crops=val_crops,
                                            crop_size=clip_size or crop_size, device=dev, **kw)
@@ -425,25 +428,30 @@ if __name__ == '__main__':
                                                          '--val-windows) instead of --val-frames-root')
     parser.add_argument('--jpeg-entropy', choices=('host', 'device'), default='host',
                         help='where the JPEG frames are Huffman decoded: host threads, or the GPU (x3djpeg_entropy_decode_batch)')
+    parser.add_argument('--index-bits', type=int, nargs='?', const=True, default=None,
+                        help='the stores of --resident / --val-resident hbm or host keep a sync index, one entry per that many '
+                             'bits of scan, and Huffman decode through it in one pass (x3djpeg_entropy_decode_indexed); no '
+                             'value: the library\'s default.  A pack with its index beside it (PACK.idx) is used indexed '
+                             'without this')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
     frames_root = None
     if args.pack is not None:
-        frames_root = dict(resident=args.resident, pack=args.pack)
+        frames_root = dict(resident=args.resident, pack=args.pack, index_bits=args.index_bits)
     elif args.frames_root is not None:
         if args.anno is None or args.labels is None:
             parser.error('--frames-root needs --anno and --labels')
         frames_root = dict(root=args.frames_root, anno=args.anno, labels=args.labels, threads=args.decode_threads,
-                           entropy=args.jpeg_entropy, resident=args.resident)
+                           entropy=args.jpeg_entropy, resident=args.resident, index_bits=args.index_bits)
     val_frames = None
     if args.val_pack is not None:
-        val_frames = dict(resident=args.val_resident, pack=args.val_pack)
+        val_frames = dict(resident=args.val_resident, pack=args.val_pack, index_bits=args.index_bits)
     elif args.val_frames_root is not None:
         if args.val_anno is None or args.labels is None:
             parser.error('--val-frames-root needs --val-anno and --labels')
         val_frames = dict(root=args.val_frames_root, anno=args.val_anno, labels=args.labels, threads=args.decode_threads,
-                          entropy=args.jpeg_entropy, resident=args.val_resident)
+                          entropy=args.jpeg_entropy, resident=args.val_resident, index_bits=args.index_bits)
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
     run(init_lr=(1.6 / 1024) * args.batch, warmup_steps=args.warmup_steps, max_epochs=args.max_epochs,

@@ -17,8 +17,10 @@ LIB_PATH = os.path.join(_HERE, "libx3djpeg.so")
 ABI_VERSION = 2
 SCAN_PAD = 16                # X3DJPEG_SCAN_PAD
 SUB_BITS_DEFAULT = 1024      # X3DJPEG_SUB_BITS_DEFAULT
+INDEX_BITS_DEFAULT = 512     # X3DJPEG_INDEX_BITS_DEFAULT
+INDEX_MAX_BLOCKS = 1 << 22   # X3DJPEG_INDEX_MAX_BLOCKS
 
-OK, EINVAL, ELAUNCH, EUNSUPPORTED, ECORRUPT = 0, -1, -2, -3, -4
+OK, EINVAL, ELAUNCH, EUNSUPPORTED, ECORRUPT, EINDEX = 0, -1, -2, -3, -4, -5
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -53,6 +55,11 @@ SIGNATURES = {
     "x3djpeg_stage_host": (_I, [_P, _I, _P, _I, _Z, _P, _Z, _P, _P, _P, _P]),
     "x3djpeg_pinned_alloc": (_I, [_Z, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
     "x3djpeg_pinned_free": (_I, [_P]),
+    "x3djpeg_index_rec_bytes": (_Z, []),
+    "x3djpeg_index_count": (_Z, [_P, _Z, _I]),
+    "x3djpeg_index_build": (_I, [_P, _Z, _P, _Z, _P, _I, _P, _Z, _P]),
+    "x3djpeg_entropy_decode_indexed": (_I, [_P, _I, _P, _P, _I, _P, _Z, _I, _P, _P]),
+    "x3djpeg_entropy_decode_indexed_host": (_I, [_P, _I, _P, _P, _I, _P, _Z, _I, _P]),
 }
 
 # X3DJpegInfo / X3DJpegFrameJob / X3DJpegScanSeg / X3DJpegScanJob of include/x3djpeg.h
@@ -82,6 +89,9 @@ STORE_DST_DT = np.dtype([("dst", "<u8"), ("dst_stride", "<i8"), ("width", "<i4")
 STORE_BAD_ID, STORE_BAD_SIZE, STORE_NO_COEF, STORE_NO_WS = 1, 2, 4, 8
 STORE_PLAN_THREADS, STORE_PLAN_CHUNK = 256, 1024
 STAGE_BAD_ID, STAGE_NO_ROOM = 1, 2
+# X3DJpegIndexRec of the sync index; an entry is two little-endian uint32 words (p, b | k << 3 | first block << 10)
+INDEX_REC_DT = np.dtype([("first_entry", "<i8"), ("nentries", "<i4"), ("pad", "<i4")])
+INDEX_ENTRY_BYTES = 8
 
 
 def stage_bytes(scan_bytes, nseg):
@@ -123,6 +133,9 @@ def lib():
         raise X3DHipError("libx3djpeg.so store structs (%d, %d, %d bytes) differ from the binding's (%d, %d, %d)" % (
             h.x3djpeg_store_header_bytes(), h.x3djpeg_store_rec_bytes(), h.x3djpeg_store_dst_bytes(),
             STORE_HEADER_DT.itemsize, STORE_REC_DT.itemsize, STORE_DST_DT.itemsize))
+    if h.x3djpeg_index_rec_bytes() != INDEX_REC_DT.itemsize:
+        raise X3DHipError("libx3djpeg.so index record (%d bytes) differs from the binding's (%d)" % (
+            h.x3djpeg_index_rec_bytes(), INDEX_REC_DT.itemsize))
     _lib = h
     return h
 
@@ -206,3 +219,24 @@ def entropy_decode_parallel_host(data, info, coef_ptr, sub_bits=SUB_BITS_DEFAULT
                                                      status.ctypes.data, rounds.ctypes.data))
     head = np.frombuffer((ctypes.c_int32 * 2).from_address(base), np.int32)
     return int(status[0]), int(rounds[0]), int(head[1]), ""
+
+
+def index_count(segs, index_bits):
+    """x3djpeg_index_count of a SCAN_SEG_DT array: entries of the frame's sync index (0: index_bits is not taken)."""
+    segs = np.ascontiguousarray(segs, SCAN_SEG_DT)
+    return int(lib().x3djpeg_index_count(segs.ctypes.data, segs.size, int(index_bits)))
+
+
+def index_build(scan, segs, info, index_bits):
+    """x3djpeg_index_build of one prepared scan (uint8 with its padding, SCAN_SEG_DT segments, INFO_DT record).  Returns
+    (rc, uint32 [n, 2] entries or None, message)."""
+    segs = np.ascontiguousarray(segs, SCAN_SEG_DT)
+    cap = index_count(segs, index_bits)
+    entries = np.zeros(max(cap, 1), np.uint64)
+    n = np.zeros(1, np.uint64)
+    rc = lib().x3djpeg_index_build(scan.ctypes.data, scan.size - SCAN_PAD, segs.ctypes.data, segs.size, info.ctypes.data,
+                                   int(index_bits), entries.ctypes.data, cap, n.ctypes.data)
+    if rc:
+        return rc, None, last_error()
+    assert int(n[0]) == cap
+    return 0, entries[:cap].view("<u4").reshape(cap, 2), ""

@@ -72,6 +72,8 @@ def status_text(rc):
     """What a nonzero per-frame status of the device Huffman decoder says."""
     if rc == _jpeglib.ECORRUPT:
         return "corrupt JPEG: the device Huffman decoder refused the scan"
+    if rc == _jpeglib.EINDEX:
+        return "the sync index does not describe the scan it was used with"
     return "the scan job does not fit its sizes or its workspace"
 
 

@@ -26,6 +26,13 @@ more launches, ids still read on the device, still capturable), and the builder 
 Pack files.  store.save(path, meta) writes the whole store -- header table, per-frame fields, arena bytes, a JSON blob the
 caller owns -- as one file of data, without addresses; FrameStore.load(path, device, tier=...) reads it back with bulk
 reads (all of it or ranges of its frames) instead of opening, parsing and un-stuffing every JPEG file again.
+
+Sync index.  FrameStore(..., index_bits=N) also keeps, per frame, the decoder state at the start of every N-bit
+subsequence of its scan (x3djpeg_index_build, on the host threads of add()): 8 bytes per N bits of scan, always in device
+memory, in both tiers.  A batch of such a store runs x3djpeg_entropy_decode_indexed in place of
+x3djpeg_entropy_decode_batch: one pass over the scan instead of a speculative pass and its relaxation rounds, every
+hand-over between subsequences compared with the index, so an index that is not the scan's reports X3DJPEG_EINDEX and
+never wrong pixels.  save() of an indexed store writes the pack as ever and the index beside it (path + ".idx").
 """
 import ctypes
 import json
@@ -36,13 +43,13 @@ import numpy as np
 import torch
 
 from . import _jpeglib
-from ._jpeglib import (FRAME_JOB_DT, SCAN_JOB_DT, SCAN_PAD, SCAN_SEG_DT, STORE_DST_DT, STORE_HEADER_DT, STORE_REC_DT,
-                       stage_bytes)
+from ._jpeglib import (FRAME_JOB_DT, INDEX_REC_DT, INFO_DT, SCAN_JOB_DT, SCAN_PAD, SCAN_SEG_DT, STORE_DST_DT,
+                       STORE_HEADER_DT, STORE_REC_DT, stage_bytes)
 from ._lib import X3DHipError, stream
 from .jpegops import HostStages, check_dst, check_sub_bits, fill_jobs, status_text
 
 MIRROR_DT = np.dtype([("width", "<i4"), ("height", "<i4"), ("nblocks", "<i4"), ("scan_bytes", "<i4"), ("nseg", "<i4"),
-                      ("chunk", "<i4"), ("coef_count", "<i8"), ("ws_need", "<i8")])
+                      ("chunk", "<i4"), ("coef_count", "<i8"), ("ws_need", "<i8"), ("nentries", "<i4")])
 _REASONS = ((_jpeglib.STORE_BAD_ID, "a frame id outside the store"),
             (_jpeglib.STORE_BAD_SIZE, "a frame of another size than its destination"),
             (_jpeglib.STORE_NO_COEF, "coefficients beyond the buffer"), (_jpeglib.STORE_NO_WS, "workspace beyond the buffer"))
@@ -58,6 +65,22 @@ PACK_HEAD = struct.Struct("<8sIIIIQQQQQ")       # magic, version, header entry b
 #                                                 nframes, nheaders, arena offset, arena bytes, meta bytes
 PACK_FRAME_DT = np.dtype([("offset", "<u8"), ("length", "<u8"), ("scan_bytes", "<i4"), ("nseg", "<i4"), ("header", "<i4"),
                           ("width", "<i4"), ("height", "<i4"), ("nblocks", "<i4"), ("coef_count", "<i8")])
+
+# The sidecar of a pack (path + ".idx"), little-endian: INDEX_HEAD, the entry count of every frame (uint32 [nframes]),
+# zeros up to a multiple of 8, the entries of all frames in frame order (8 bytes each).
+INDEX_SUFFIX, INDEX_MAGIC, INDEX_VERSION = ".idx", b"X3DJPIDX", 1
+INDEX_HEAD = struct.Struct("<8sIIQQQ")          # magic, version, index_bits, nframes and arena bytes of the pack it
+#                                                 belongs to, entries in all
+
+
+def check_index_bits(index_bits):
+    """The granularity of a sync index as an int (True: the library's default), None for no index, or ValueError."""
+    if index_bits is None or index_bits is False:
+        return None
+    bits = _jpeglib.INDEX_BITS_DEFAULT if index_bits is True else int(index_bits)
+    if bits < 32 or bits % 32 or bits > 1 << 20:
+        raise ValueError("index_bits must be a multiple of 32 in 32 .. 2^20 (got %r)" % (index_bits,))
+    return bits
 
 
 def store_headers(infos):
@@ -230,21 +253,31 @@ class Batch:
                                 self.stage_cap, self.staged_recs.data_ptr(), self.staged_ids.data_ptr(),
                                 self.offsets.data_ptr(), self.stage_status.data_ptr())
             recs_ptr, nrecs, ids_ptr = self.staged_recs.data_ptr(), self.n, self.staged_ids.data_ptr()
+        # an indexed store: the index tables as they are now, and the ids as the caller wrote them (not the staged ones)
+        self.index_bits, self._index_args = store.index_bits, None
+        if self.index_bits is not None:
+            self._index_recs, self._entries = store._index_recs.dev, store._entries.dev
+            self._index_args = (ids.data_ptr(), mem.ptr(self._index_recs), store._index_recs.n, mem.ptr(self._entries),
+                                store._entries.n, self.index_bits)
         self._args = (recs_ptr, nrecs, mem.ptr(self._headers), self.nheaders, ids_ptr, self.n,
                       self.sub_bits, self.coef.data_ptr(), self.coef_cap, self.planes.data_ptr(), self.coef_cap, self.ws_cap,
                       dsts.data_ptr(), self.plan.data_ptr(), self.scan_jobs.data_ptr(), self.frame_jobs.data_ptr(),
                       self.build_status.data_ptr())
 
     def launch(self):
-        """x3djpeg_store_build_jobs (two launches), x3djpeg_entropy_decode_batch, x3djpeg_decode_batch (two) on the current
-        stream, after x3djpeg_stage (two) for a host-tier store, and nothing else: no allocation, no copy, no
-        synchronisation."""
+        """x3djpeg_store_build_jobs (two launches), x3djpeg_entropy_decode_batch (x3djpeg_entropy_decode_indexed for an
+        indexed store), x3djpeg_decode_batch (two) on the current stream, after x3djpeg_stage (two) for a host-tier store,
+        and nothing else: no allocation, no copy, no synchronisation."""
         L, s = _jpeglib.lib(), stream()
         if self._stage_args is not None:
             _jpeglib.check(L.x3djpeg_stage(*self._stage_args, s))
         _jpeglib.check(L.x3djpeg_store_build_jobs(*self._args, s))
-        _jpeglib.check(L.x3djpeg_entropy_decode_batch(self.scan_jobs.data_ptr(), self.n, self.sub_bits,
-                                                      self.workspace.data_ptr(), self.ws_cap, self.status.data_ptr(), s))
+        if self._index_args is not None:
+            _jpeglib.check(L.x3djpeg_entropy_decode_indexed(self.scan_jobs.data_ptr(), self.n, *self._index_args,
+                                                            self.status.data_ptr(), s))
+        else:
+            _jpeglib.check(L.x3djpeg_entropy_decode_batch(self.scan_jobs.data_ptr(), self.n, self.sub_bits,
+                                                          self.workspace.data_ptr(), self.ws_cap, self.status.data_ptr(), s))
         _jpeglib.check(L.x3djpeg_decode_batch(self.frame_jobs.data_ptr(), self.n, self.max_blocks, self.max_w, self.max_h, s))
 
     def raise_for_status(self):
@@ -269,9 +302,13 @@ class FrameStore:
     jpegops.HostStages: no device is involved in filling).  check=False skips the read of
     the status words after decode / decode_into and leaves the batch in last_batch.  memory: see TorchMemory.  tier:
     "device" keeps the arena chunks where the tables are; "host" keeps them in pinned host memory (PinnedMemory) and
-    decodes through a staging buffer per batch.  A `memory` given by the caller holds tables and chunks alike."""
+    decodes through a staging buffer per batch.  A `memory` given by the caller holds tables and chunks alike.
+    index_bits: None for the relaxation decoder; a multiple of 32 (True: the library's default) keeps a sync index of
+    that granularity for every frame, in device memory in both tiers, and decodes through it (the workspace is still
+    sized for sub_bits: the indexed decoder does not use it)."""
 
-    def __init__(self, device, chunk_bytes=None, sub_bits=None, threads=2, check=True, memory=None, tier="device"):
+    def __init__(self, device, chunk_bytes=None, sub_bits=None, threads=2, check=True, memory=None, tier="device",
+                 index_bits=None):
         if tier not in TIERS:
             raise ValueError("tier must be one of %s (got %r)" % (", ".join(TIERS), tier))
         self.tier = tier
@@ -290,6 +327,10 @@ class FrameStore:
         self._headers = _Table(self.memory, STORE_HEADER_DT, 8)
         self._header_index = {}      # header bytes -> index
         self._mirror = np.zeros(1024, MIRROR_DT)
+        self.index_bits = check_index_bits(index_bits)
+        if self.index_bits is not None:
+            self._index_recs = _Table(self.memory, INDEX_REC_DT, 1024)
+            self._entries = _Table(self.memory, np.dtype("<u8"), 1 << 14)
 
     def __len__(self):
         return self._recs.n
@@ -299,6 +340,7 @@ class FrameStore:
 
     width, height, nblocks = _field("width"), _field("height"), _field("nblocks")
     scan_bytes, nseg, coef_count, ws_need = _field("scan_bytes"), _field("nseg"), _field("coef_count"), _field("ws_need")
+    nentries = _field("nentries")                           # of the frame's sync index; 0 in a store without one
     del _field
 
     @property
@@ -315,10 +357,14 @@ class FrameStore:
         return r["scan"].copy(), r["segs"].copy()
 
     def bytes_resident(self):
-        """Device bytes the store holds: the header table and the record table, and in the device tier the arena chunks
-        in full."""
+        """Device bytes the store holds: the header table, the record table and the sync index, and in the device tier
+        the arena chunks in full."""
         chunks = 0 if self.tier == "host" else sum(c[1] for c in self._chunks)
-        return chunks + self._recs.nbytes + self._headers.nbytes
+        return chunks + self._recs.nbytes + self._headers.nbytes + self.bytes_index()
+
+    def bytes_index(self):
+        """Device bytes of the sync index: its record table and its entry array as allocated; 0 without an index."""
+        return 0 if self.index_bits is None else self._index_recs.nbytes + self._entries.nbytes
 
     def bytes_pinned(self):
         """Pinned host bytes the store holds: the arena chunks of the host tier in full."""
@@ -335,6 +381,8 @@ class FrameStore:
         infos, staged, scan_at, seg_at, scan_bytes, nseg, ws_need = self._stages._prepare_stage(files)
         if int(scan_bytes.max()) >= 1 << 31 or first + n >= 1 << 31:
             raise ValueError("the store holds fewer than 2^31 frames of fewer than 2^31 scan bytes")
+        base = staged.data_ptr()
+        entries = self._build_index(infos, base + scan_at[:-1], scan_bytes, base + seg_at[:-1], nseg)
         staged = staged.numpy()
         seg_len = nseg.astype(np.int64) * SCAN_SEG_DT.itemsize
         scan_len = (scan_bytes + SCAN_PAD + 15) & ~15
@@ -369,8 +417,38 @@ class FrameStore:
             self.arena_memory.write(chunks[c][0], lo, pack)
             chunks[c][2] = hi
         self._commit(chunks, chunk_of, off_of, scan_bytes, nseg, header_of, heads[added], index,
-                     {f: infos[f] for f in ("width", "height", "nblocks", "coef_count")}, ws_need)
+                     {f: infos[f] for f in ("width", "height", "nblocks", "coef_count")}, ws_need, entries)
         return range(first, first + n)
+
+    def _build_index(self, infos, scan_ptr, scan_bytes, seg_ptr, nseg):
+        """The sync index of n prepared frames on the host threads: (entries per frame, uint64 entries of all of them in
+        order), or None for a store without an index.  infos: INFO_DT [n]; the rest one entry per frame, host addresses.
+        X3DHipError naming the first frame the indexer refuses."""
+        if self.index_bits is None:
+            return None
+        L, bits, n = _jpeglib.lib(), self.index_bits, len(infos)
+        scan_p, seg_p = [int(v) for v in scan_ptr], [int(v) for v in seg_ptr]
+        scan_b, nseg_l = [int(v) for v in scan_bytes], [int(v) for v in nseg]
+        count = np.array([L.x3djpeg_index_count(seg_p[i], nseg_l[i], bits) for i in range(n)], np.int64)
+        at = np.concatenate([[0], np.cumsum(count)])
+        out = np.zeros(int(at[-1]), np.uint64)
+        wrote = np.zeros(n, np.uint64)
+        info_ptr, info_size, out_ptr, wrote_ptr = infos.ctypes.data, INFO_DT.itemsize, out.ctypes.data, wrote.ctypes.data
+        at_l, count_l, fail = at.tolist(), count.tolist(), self._stages._fail
+
+        def build(lo, hi):
+            res = []
+            for i in range(lo, hi):
+                rc = L.x3djpeg_index_build(scan_p[i], scan_b[i], seg_p[i], nseg_l[i], info_ptr + i * info_size, bits,
+                                           out_ptr + 8 * at_l[i], count_l[i], wrote_ptr + 8 * i)
+                res.append(fail(i, rc) if rc else None)
+            return res
+
+        for msg in self._stages._chunks(build, n):
+            if msg:
+                raise X3DHipError(msg)
+        assert np.array_equal(wrote.astype(np.int64), count)
+        return count, out
 
     def _place(self, size):
         """Placement of frames of `size` bytes each: in order, a new chunk when the next frame does not fit.  Returns
@@ -397,8 +475,10 @@ class FrameStore:
             cur, room, used0 = len(self._chunks) + len(new_chunks) - 1, cap, 0
         return chunk_of, off_of, [list(c) for c in self._chunks] + new_chunks
 
-    def _commit(self, chunks, chunk_of, off_of, scan_bytes, nseg, header_of, new_headers, new_index, fields, ws_need):
-        """The arena is written: the records, the new headers and the mirror of n more frames."""
+    def _commit(self, chunks, chunk_of, off_of, scan_bytes, nseg, header_of, new_headers, new_index, fields, ws_need,
+                entries=None):
+        """The arena is written: the records, the new headers, the mirror and (entries: what _build_index gave) the sync
+        index of n more frames."""
         n, first = len(chunk_of), self._recs.n
         scan_len = (np.asarray(scan_bytes, np.int64) + SCAN_PAD + 15) & ~15
         base = np.array([self.arena_memory.ptr(chunks[c][0]) for c in chunk_of], np.uint64)
@@ -419,6 +499,13 @@ class FrameStore:
         for f, v in fields.items():
             m[f] = v
         m["scan_bytes"], m["nseg"], m["ws_need"], m["chunk"] = scan_bytes, nseg, ws_need, chunk_of
+        if entries is not None:
+            count, words = entries
+            irecs = np.zeros(n, INDEX_REC_DT)
+            irecs["first_entry"] = self._entries.n + np.cumsum(count) - count
+            irecs["nentries"] = m["nentries"] = count
+            self._entries.append(words)
+            self._index_recs.append(irecs)
 
     # ------------------------------------------------------------------ decoding
     def _ids(self, ids):
@@ -538,6 +625,47 @@ class FrameStore:
                 for lo in range(0, c[2], step):
                     f.write(memoryview(np.ascontiguousarray(_read(self.arena_memory, c[0], lo, min(step, c[2] - lo)))))
             f.write(blob)
+        if self.index_bits is not None:
+            total = self._entries.n
+            with open(path + INDEX_SUFFIX, "wb") as f:
+                f.write(INDEX_HEAD.pack(INDEX_MAGIC, INDEX_VERSION, self.index_bits, n, int(used.sum()), total))
+                f.write(m["nentries"].astype("<u4").tobytes())
+                f.write(b"\0" * (-(INDEX_HEAD.size + 4 * n) % 8))
+                f.write(self._entries.host[:total].tobytes())
+
+    @staticmethod
+    def _read_index_tables(f, path, nframes, arena_bytes, scan_bytes, nseg):
+        """(index_bits, entry count per frame, file offset of the entries) of an open sidecar, checked against the pack it
+        is read with (its frame count and arena bytes, and per frame the bounds its sizes put on the count); ValueError
+        for any defect."""
+        def bad(why):
+            return ValueError("%s is not the sync index of this pack in a form this version reads: %s" % (path, why))
+        file_bytes = os.fstat(f.fileno()).st_size
+        head = f.read(INDEX_HEAD.size)
+        if len(head) < INDEX_HEAD.size:
+            raise bad("%d bytes, shorter than its head" % file_bytes)
+        magic, version, bits, n, arena, total = INDEX_HEAD.unpack(head)
+        if magic != INDEX_MAGIC:
+            raise bad("magic %r" % magic)
+        if version != INDEX_VERSION:
+            raise bad("format version %d, not %d" % (version, INDEX_VERSION))
+        if bits < 32 or bits % 32 or bits > 1 << 20:
+            raise bad("index_bits %d" % bits)
+        if n != nframes or arena != arena_bytes:
+            raise bad("made for a pack of %d frames and %d arena bytes, not %d and %d" % (n, arena, nframes, arena_bytes))
+        at = (INDEX_HEAD.size + 4 * n + 7) & ~7
+        if total >= 1 << 59 or at + 8 * total != file_bytes:
+            raise bad("its counts (%d frames, %d entries) do not give its %d bytes" % (n, total, file_bytes))
+        count = np.frombuffer(f.read(4 * n), "<u4").astype(np.int64)
+        if len(count) != n or int(count.sum()) != total:
+            raise bad("the frames' entry counts do not sum to its %d entries" % total)
+        # a segment has ceil(bits / index_bits) entries, at least one: what the sizes alone say (the decoder checks the rest)
+        most = np.asarray(scan_bytes, np.int64) * 8 // bits + np.asarray(nseg, np.int64)
+        wrong = (count < np.asarray(nseg, np.int64)) | (count > most)
+        if wrong.any():
+            i = int(np.flatnonzero(wrong)[0])
+            raise bad("frame %d: %d entries for %d scan bytes in %d segments" % (i, count[i], scan_bytes[i], nseg[i]))
+        return bits, count, at
 
     @staticmethod
     def _read_pack_tables(f, path):
@@ -600,14 +728,19 @@ class FrameStore:
             return cls._read_pack_tables(f, path)[3]
 
     @classmethod
-    def load(cls, path, device, tier="device", sub_bits=None, ranges=None, memory=None, **kw):
+    def load(cls, path, device, tier="device", sub_bits=None, ranges=None, memory=None, index=None, **kw):
         """Reads a pack file.  Returns (store, meta, id_map).  ranges: a list of ranges of saved frame ids (None: all of
         them); only those frames are read, placed as add() places frames, and id_map is the list of the ranges of their
         new ids, one per entry of `ranges`.  sub_bits: None takes the one the pack was saved with.  The host tier reads
         straight into each chunk's host view, the device tier through one staging buffer per chunk.  ValueError, before
-        any store exists, for a file that is not a whole pack of this version."""
+        any store exists, for a file that is not a whole pack of this version.  index: None uses the pack's sync index
+        (path + ".idx") if that file is there -- only the entries of the frames read are read -- and gives a store
+        without an index otherwise; False ignores the file; an int (True: the library's default) builds the index of that
+        granularity from the scans as they are read.  A sidecar that is not this pack's whole index is a ValueError too."""
         with open(path, "rb") as f:
             saved_bits, heads, ft, meta = cls._read_pack_tables(f, path)
+            f.seek(0)
+            arena_bytes = PACK_HEAD.unpack(f.read(PACK_HEAD.size))[8]
             if ranges is None:
                 ranges = [range(len(ft))]
             ranges = [r if isinstance(r, range) else range(*r) for r in ranges]
@@ -615,7 +748,26 @@ class FrameStore:
                 if r.step != 1 or (len(r) and (r.start < 0 or r.stop > len(ft))):
                     raise ValueError("range %r outside the %d frames of %s (or not of step 1)" % (r, len(ft), path))
             sel = np.concatenate([np.arange(r.start, r.stop, dtype=np.int64) for r in ranges] + [np.zeros(0, np.int64)])
-            store = cls(device, sub_bits=saved_bits if sub_bits is None else sub_bits, memory=memory, tier=tier, **kw)
+            side = None                                     # (entry count per frame read, their entries)
+            if index is None and os.path.exists(path + INDEX_SUFFIX):
+                with open(path + INDEX_SUFFIX, "rb") as g:
+                    index_bits, count, ent_at = cls._read_index_tables(g, path + INDEX_SUFFIX, len(ft), arena_bytes,
+                                                                       ft["scan_bytes"], ft["nseg"])
+                    first = np.cumsum(count) - count
+                    words = np.zeros(int(count[sel].sum()), np.uint64)
+                    o = 0
+                    for r in ranges:                        # the frames of a range follow each other in the sidecar
+                        nb = int(count[r.start:r.stop].sum()) if len(r) else 0
+                        if nb:
+                            g.seek(ent_at + 8 * int(first[r.start]))
+                            if g.readinto(memoryview(words)[o:o + nb]) != 8 * nb:
+                                raise ValueError("%s ends inside frame %d" % (path + INDEX_SUFFIX, r.start))
+                        o += nb
+                    side = (count[sel], words)
+            else:
+                index_bits = check_index_bits(index)
+            store = cls(device, sub_bits=saved_bits if sub_bits is None else sub_bits, memory=memory, tier=tier,
+                        index_bits=index_bits, **kw)
             n = sel.size
             at = np.cumsum([0] + [len(r) for r in ranges])
             id_map = [range(int(a), int(b)) for a, b in zip(at[:-1], at[1:])]
@@ -628,6 +780,11 @@ class FrameStore:
             size, src = t["length"].astype(np.int64), t["offset"].astype(np.int64)
             chunk_of, off_of, chunks = store._place(size)
             mem = store.arena_memory
+            L, built = _jpeglib.lib(), []
+            scan_len = (t["scan_bytes"].astype(np.int64) + SCAN_PAD + 15) & ~15
+            if index_bits is not None and side is None:
+                infos = np.zeros(n, INFO_DT)                # what the indexer reads of an info is what a scan job holds
+                _jpeglib.fill_scan_jobs(infos, heads[t["header"]]["scan"])
             for c in np.unique(chunk_of):
                 idx = np.flatnonzero(chunk_of == c)
                 lo, hi = int(off_of[idx[0]]), int(off_of[idx[-1]] + size[idx[-1]])
@@ -640,11 +797,23 @@ class FrameStore:
                     f.seek(int(src[run[0]]))
                     if f.readinto(memoryview(view)[a:a + nb]) != nb:
                         raise ValueError("%s ends inside frame %d" % (path, sel[run[0]]))
+                if index_bits is not None:
+                    scan_ptr = view.ctypes.data + off_of[idx] - lo
+                    if side is None:
+                        built.append(store._build_index(infos[idx], scan_ptr, t["scan_bytes"][idx], scan_ptr + scan_len[idx],
+                                                        t["nseg"][idx]))
+                    else:                                   # the counts against the segment tables themselves
+                        for i, sp in zip(idx.tolist(), (scan_ptr + scan_len[idx]).tolist()):
+                            if L.x3djpeg_index_count(sp, int(t["nseg"][i]), index_bits) != side[0][i]:
+                                raise ValueError("%s is not the sync index of this pack: frame %d has %d entries at "
+                                                 "index_bits %d" % (path + INDEX_SUFFIX, sel[i], side[0][i], index_bits))
                 if not hasattr(mem, "host_view"):
                     mem.write(chunks[c][0], lo, view)
                 chunks[c][2] = hi
         uniq, inv = np.unique(np.stack([t["scan_bytes"], t["nseg"]], axis=1), axis=0, return_inverse=True)
         ws = np.array([_jpeglib.workspace_bytes(a, b, store.sub_bits) for a, b in uniq.tolist()], np.int64)
         store._commit(chunks, chunk_of, off_of, t["scan_bytes"], t["nseg"], t["header"], heads[:0], {},
-                      {f: t[f] for f in ("width", "height", "nblocks", "coef_count")}, ws[inv.reshape(-1)])
+                      {f: t[f] for f in ("width", "height", "nblocks", "coef_count")}, ws[inv.reshape(-1)],
+                      side if side is not None else
+                      (np.concatenate([b[0] for b in built]), np.concatenate([b[1] for b in built])) if built else None)
         return store, meta, id_map
