@@ -2,7 +2,7 @@
 comparison against fp64 meaningful (tests/test_exact_inputs_host.py proves them on the CPU, tests/test_exact_gpu.py
 compares the kernels with `torch.equal`).
 
-Two families:
+Three families:
 
 * Integer sets.  Effective activations in {0, +-1, +-2}, weights in {0, +-1/2, +-1} (sparse rows whose non-zeros walk over
   all of K from row to row), BN prologue coefficients with power-of-two scales and dyadic shifts, BN-backward combine
@@ -19,6 +19,9 @@ Two families:
   operands 1 + 2^-10 need mid.mid (product 1 + 2^-9 + 2^-20).  The products the kernels drop by design (mid.lo, lo.mid,
   lo.lo) are zero on these inputs.  Signs are constant within a contraction, so the signed count of non-zero products of
   an output is 0 only where no product is non-zero at all.
+
+* Hot integer sets, for the mixed-storage mode (bf16 storage of the wide tensors): the integer sets with a large power of two
+  on a few voxels, so that a bf16 store of an output rounds; see "mixed storage" below.
 """
 import math
 from types import SimpleNamespace
@@ -619,6 +622,317 @@ def probe_wgrad(shape, kind, seed=0):
     dY = A.view(Co, N, P).transpose(0, 1).contiguous().view(N, Co, T, H, W)
     x = B.t().contiguous().view(Ci, N, P).transpose(0, 1).contiguous().view(N, Ci, T, H, W)
     return dY, x, A @ B
+
+
+# ----------------------------------------------------------------------------------------------------- mixed storage
+# bf16 storage of the wide tensors (include/x3dhip.h X3D_MX_*).  The integer sets above give outputs of at most 8
+# significant bits: a bf16 store of them never rounds.  The HOT variant puts a large power of two on a few voxels of a
+# sample in some channels (of x: what a forward output is large from; of g: what a data gradient is large from); an output
+# there is a large term plus a small one (128.5, 257.5, 130.25) of 9 to 11 significant bits, on the same power-of-two grid,
+# so the store rounds: ties where the small part is half an ulp, non-ties where the grid is finer than that (magnitude
+# 256 against a grid of 1/2; the gradients' grid of 1/4).  The reference of a bf16 output is the fp64 result, which is an
+# fp32 number, cast by torch's CPU round-to-nearest-even; the statistics that describe it are the fp64 sums over THAT
+# tensor.  tests/test_exact_inputs_host.py proves per case that the rounding really is exercised.
+HOT = (64., -64., 128., -128., 256., -256.)
+HOT_P = (0.05, 0.05, 0.1, 0.1, 0.35, 0.35)
+HOT_ROW_P = (0.03, 0.02, 0.45, 0.2, 0.18, 0.12)        # (channelwise: what follows a ReLU is better positive)
+
+
+def bf16_ok(t):
+    """Every element is a bf16 number."""
+    return torch.equal(t.float().bfloat16().double(), t.double())
+
+
+def stored(v):
+    """v as a kernel stores it in a bf16 tensor: round to nearest even (torch's CPU cast) of the fp32 value, in v's dtype."""
+    f = v.float()
+    assert torch.equal(f.double(), v.double()), "not an fp32 number (bug in the case)"
+    return f.bfloat16().to(v.dtype)
+
+
+def _bits(v):
+    f = v.float()
+    assert torch.equal(f.double(), v.double())
+    return f.contiguous().view(torch.int32)
+
+
+def stored_by_truncation(v):
+    """Control: the low 16 bits dropped."""
+    return (_bits(v) & -65536).view(torch.float32).to(v.dtype)
+
+
+def stored_half_away(v):
+    """Control: 0x8000 added to the (sign-magnitude) bits, then truncated -- round half away from zero."""
+    return ((_bits(v) + 0x8000) & -65536).view(torch.float32).to(v.dtype)
+
+
+def rounding_census(v):
+    """How the bf16 store of v (fp64 holding fp32 numbers) rounds: counts of elements that are not bf16 numbers, of ties
+    rounded up / down in magnitude (to the even neighbour) and of non-ties rounded up / down in magnitude."""
+    low = _bits(v) & 0xFFFF
+    up = stored(v).abs() > v.abs()
+    tie, ne = low == 0x8000, low != 0
+    cnt = lambda m: int(m.sum())
+    return {"inexact": cnt(ne), "tie_up": cnt(tie & up), "tie_down": cnt(tie & ~up), "up": cnt(ne & ~tie & up),
+            "down": cnt(ne & ~tie & ~up)}
+
+
+def _fit_raw(t, pre):
+    """With a prologue the RAW tensor (raw_for) must stay a bf16 tensor: a hot value whose raw image needs a ninth bit
+    (128 + 1/2) is halved until it fits."""
+    for _ in range(3):
+        raw = raw_for(t, pre)
+        t = torch.where(raw.float().bfloat16().double() != raw, t / 2, t)
+    assert bf16_ok(raw_for(t, pre))
+    return t
+
+
+def heat(target, seed, pre=None):
+    """The hot variant of an activation / gradient tensor [N, C, T, H, W] of effective values: on P / 2 voxels of a sample (at
+    most 48) every channel takes, with probability 1 / 8 (at least two channels per voxel on average), a value of HOT -- other
+    channels at each voxel, so that the hot terms reach every output row but seldom two of them the same output."""
+    N, C = target.shape[:2]
+    t = target.clone().flatten(2)
+    P = t.shape[2]
+    nv = min(max(P // 2, 1), 48)
+    q = max(1.0 / 8, 2.0 / C)
+    g = _gen(seed)
+    for n in range(N):
+        vox = torch.randperm(P, generator=g)[:nv]
+        vals = pick((C, nv), (0.,) + HOT, (1 - q,) + tuple(q * p for p in HOT_P), seed + 1 + n)
+        t[n][:, vox] = torch.where(vals != 0, vals, t[n][:, vox])
+    t = t.view_as(target)
+    return t if pre is None else _fit_raw(t, pre)
+
+
+def heat_rows(target, seed, pre=None, frac=4, most=24):
+    """heat() for the channelwise convs, where every (n, c) row is a convolution of its own: each row gets its own hot voxels,
+    1 / frac of the row's at most, `most` at most."""
+    N, C = target.shape[:2]
+    t = target.clone().flatten(2)
+    P = t.shape[2]
+    nv = min(max(int(P / frac), 1), most)
+    g = _gen(seed)
+    vox = torch.stack([torch.randperm(P, generator=g)[:nv] for _ in range(N * C)]).view(N, C, nv)
+    t.scatter_(2, vox, pick((N, C, nv), HOT, HOT_ROW_P, seed + 1))
+    t = t.view_as(target)
+    return t if pre is None else _fit_raw(t, pre)
+
+
+def _st(r, name, second=None, order=0):
+    """Adds to r the stored form of the bf16 output r[name] and the two statistics of the stored tensor: {sum y, sum y^2}, or
+    {sum dx, sum dx * second} for a gradient."""
+    st = stored(r[name])
+    r[name + "_st"] = st
+    r[name + "_st_s0"] = rowsum(st, order)
+    r[name + "_st_s1"] = rowsum(st * (st if second is None else second), order)
+
+
+def _st_mags(m, r, name, second=None):
+    st = r[name + "_st"]
+    u = unit_of(st)
+    m[name + "_st_s0"] = (rowsum(st.abs()), u)
+    m[name + "_st_s1"] = (rowsum((st * (st if second is None else second)).abs()), u * (u if second is None else unit_of(second)))
+
+
+# pointwise rows of the case tables of tests/test_mixed_storage_gpu.py (PW_FWD, PW_BWD): the smallest row on each mixed-storage
+# kernel, and every row where the mixed mode runs ANOTHER kernel than fp32 (marked *).  (N, Cin, Cout, T, H, W, act)
+PW_MX = [
+    (2, 24, 54, 4, 16, 16, 1),      # forward: streaming split-bf16 kernel, wide output; backward: the fused kernel's shapes
+    (2, 54, 24, 4, 16, 16, 1),      # fp32-MFMA streaming kernel (pw3), wide input
+    (2, 48, 216, 4, 6, 6, 0),       # K < 64: pw3 with a wide output; data gradient M = 48: pw3 with bf16 g, a
+    (1, 24, 54, 2, 9, 7, 1),        # * P % 4 != 0: pw3 scalar form, bf16 element stores
+    (1, 54, 24, 2, 9, 7, 1),        # * P % 4 != 0: bf16 element loads
+    (2, 96, 216, 4, 12, 12, 0),     # * whole-K item kernel pw6 (fp32: pw8); conv1 data gradient: item kernel pw7 (fp32, two terms: chunked)
+    (2, 216, 96, 4, 12, 12, 1),     # pw6, wide input; data gradient pw7, M = 216
+    (2, 432, 192, 2, 6, 6, 1),      # K = 432: dynamic LDS > 64 KB
+    (2, 192, 432, 2, 6, 6, 0),
+    (2, 54, 54, 2, 8, 8, 1),        # both sides bf16
+    (1, 96, 216, 2, 7, 7, 0),       # * stage 3 with P % 4 != 0: streaming kernel instead of the LDS-tiled ones
+    (1, 216, 96, 2, 7, 7, 1),       # *
+]
+FUSED_MX = [(2, 24, 54, 4, 16, 16, 1), (2, 54, 24, 4, 16, 16, 1), (3, 48, 108, 2, 20, 20, 1), (2, 108, 48, 2, 14, 14, 1),
+            (2, 24, 108, 4, 12, 12, 1)]                                 # the five tile shapes of x3d_pw_bwd_fused (FUSED)
+PW_MX_GRID = [(3, 24, 54, 4, 20, 20, 1)]                                # persistent loops (option fb_grid): the streaming forward ...
+FUSED_MX_GRID = [(3, 24, 54, 4, 20, 20, 1)]                             # ... and the fused backward
+# DW rows: W % 4 != 0 and odd sizes (element loads / stores), the 16-channel block with a tail, float2 and float4 rows,
+# stride 2, three row tiles.  The base-shape planes add nothing about rounding or tails.
+DW_MX = [(2, 6, 4, 14, 14, 1), (1, 5, 5, 13, 9, 1), (2, 4, 4, 16, 16, 2), (1, 3, 3, 15, 11, 2), (1, 33, 2, 4, 4, 2), (1, 2, 3, 40, 56, 1)]
+
+
+# the seeds at which every case below meets the "rounding is exercised" conditions of tests/test_exact_inputs_host.py (how many
+# outputs round, and how, is a property of the draw; the conditions are asserted there, per case)
+MX_SEED = 3
+DW_MX_SEED = {(2, 6, 4, 14, 14, 1): 6}
+DW_MX_SEED_DEFAULT = 7
+DW_BN_SEED = {(1, 33, 2, 4, 4, 2): 3}                  # (of the BN side of x3d_dw333_fwd_stats)
+
+
+def pw_mx_case(case, seed=MX_SEED):
+    """pw_case with hot x (effective values; the raw tensor stays bf16) and hot g.  The other tensors a kernel may read as
+    bf16 (a) are integers."""
+    N, Ci, Co, T, H, W, act = case
+    c = pw_case((N, Ci, Co, T, H, W, 1, act), seed)
+    eff = affine(c.pre, c.x) if c.act else c.x
+    hot = heat(eff, seed + 20, c.pre if c.act else None)
+    c.x = raw_for(hot, c.pre) if c.act else hot
+    c.g = heat(c.g, seed + 30)
+    return c
+
+
+def pw_mx_ref(c, dt=F64, order=0):
+    """pw_ref plus, for the outputs a mixed-storage call writes as bf16 (y; dx of the ReLU-backward form without addend),
+    the stored tensor and its statistics.  What is computed FROM bf16 tensors keeps pw_ref's entry."""
+    r = pw_ref(c, dt, order)
+    _st(r, "y", order=order)
+    if c.act:
+        x = c.x.to(dt)
+        r["dx_act"] = r["din"] * (affine(c.pre.to(dt), x) > 0).to(dt)
+        r["dx_act_s0"], r["dx_act_s1"] = rowsum(r["dx_act"], order), rowsum(r["dx_act"] * x, order)
+        _st(r, "dx_act", second=x, order=order)
+    return r
+
+
+def pw_mx_mags(c, r):
+    m = pw_mags(c, r)
+    _st_mags(m, r, "y")
+    if c.act:
+        m["dx_act_s0"] = (rowsum(r["dx_act"].abs()), m["din"][1])
+        m["dx_act_s1"] = (rowsum((r["dx_act"] * c.x).abs()), m["din"][1] * unit_of(c.x))
+        _st_mags(m, r, "dx_act", c.x)
+    return m
+
+
+def fused_mx_case(case, seed=MX_SEED):
+    c = fused_case(case, seed)
+    c.x = raw_for(heat(affine(c.pre, c.x), seed + 20, c.pre), c.pre)
+    c.g = heat(c.g, seed + 30)
+    return c
+
+
+def fused_mx_ref(c, dt=F64, order=0):
+    r = fused_ref(c, dt, order)
+    _st(r, "m1_dx0", second=c.x.to(dt), order=order)                   # X | Y: mode 1 without addend
+    return r
+
+
+def fused_mx_mags(c, r):
+    m = fused_mags(c, r)
+    _st_mags(m, r, "m1_dx0", c.x)
+    return m
+
+
+def dw_mx_case(case, seed=None, pre=None, cb=None):
+    """dw_case with hot x and g and NINE taps per channel instead of three: an output next to a hot voxel then has small terms
+    too, whose half decides the rounding."""
+    seed = DW_MX_SEED.get(tuple(case), DW_MX_SEED_DEFAULT) if seed is None else seed
+    c = dw_case(case, seed)
+    c.w = sparse_rows(case[1], 27, 9, seed + 2).view(case[1], 1, 3, 3, 3)
+    eff = affine(c.pre, c.x)
+    eff = torch.where(eff == -1, -eff, eff)                            # more odd terms behind the ReLU (-2 stays)
+    if pre is not None:
+        c.pre = pre
+    if cb is not None:
+        c.cb = cb
+    # a hot voxel of x reaches nine outputs at stride 1 but two or three at stride 2; sum y^2 of a row bounds how many it may hold
+    c.x = raw_for(heat_rows(eff, seed + 20, c.pre, *((4, 32) if c.s == 1 else (1.5, 96))), c.pre)
+    c.g = heat_rows(c.g, seed + 30, None, 4 if c.s == 1 else 2, 24)
+    return c
+
+
+def dw_mx_ref(c, dt=F64, order=0):
+    r = dw_ref(c, dt, order)
+    _st(r, "y", order=order)
+    _st(r, "dx", second=c.x.to(dt), order=order)
+    return r
+
+
+def dw_mx_mags(c, r):
+    m = dw_mags(c, r)
+    _st_mags(m, r, "y")
+    _st_mags(m, r, "dx", c.x)
+    return m
+
+
+# the BN finalizes folded into the channelwise kernels (x3d_dw333_fwd_stats, x3d_dw333_bwd_stats) are fp64 arithmetic on the
+# statistics partials; on dyadic statistics every step of it is exact (quotients by a count whose numerator is a multiple of
+# it, the square root of 1 or 1/4), so the coefficients they derive are the case's pre / cb and everything else follows.
+BN_EPS, BN_MOMENTUM = 2.0 ** -6, 0.25
+
+
+def _spread(total, N, tiles=3):
+    """[N, C, tiles, ...] partials (dyadic fractions 1/2, 1/4, 1/4 per sample) that sum to total [C, ...] over samples and tiles."""
+    f = torch.tensor([0.5, 0.25, 0.25], dtype=F64)[:tiles].view(1, 1, tiles, 1)
+    return (total[None, :, None] / N * f).expand(N, -1, -1, -1).contiguous()
+
+
+def dw_bn_fwd(N, C, S, seed=0):
+    """Statistics partials of a producer conv, BN parameters and running statistics of x3d_dw333_fwd_stats with S splits, and
+    what its finalize makes of them: coef [N, C, 2] (the prologue the conv then applies), save [2, S, C], the updated running
+    statistics.  The element count of a split is 9 or 2: cnt - 1 is a power of two, so the unbiased variance is exact."""
+    ns = N // S
+    assert N % S == 0 and ns in (1, 2)
+    b = SimpleNamespace(S=S, count=9 if ns == 1 else 1, eps=BN_EPS, momentum=BN_MOMENTUM)
+    cnt = float(b.count * ns)
+    b.gamma = pick((C,), (1., -1., 0.5), (0.4, 0.3, 0.3), seed + 40)
+    b.beta = pick((C,), (0., 0.5, -0.5, 1.), (0.25, 0.25, 0.25, 0.25), seed + 41)
+    mean = pick((S, C), (0., 0.5, -0.5), (0.4, 0.3, 0.3), seed + 42)
+    invstd = pick((S, C), (1., 2.), (0.5, 0.5), seed + 43)
+    var = 1 / (invstd * invstd) - b.eps
+    b.rm = pick((S, C), (0., 0.5, -1.), (0.4, 0.3, 0.3), seed + 44)
+    b.rv = pick((S, C), (1., 0.5, 2.), (0.4, 0.3, 0.3), seed + 45)
+    tot = torch.stack([mean * cnt, (var + mean * mean) * cnt], -1)      # [S, C, 2]: the sums over a split
+    b.sp = torch.cat([_spread(tot[j], ns) for j in range(S)], 0)        # samples j, j + S, ... of split j
+    b.sp = b.sp.view(S, ns, C, 3, 2).transpose(0, 1).reshape(N, C, 3, 2).contiguous()
+    sc = b.gamma * invstd
+    coef = torch.stack([sc, b.beta - mean * sc], -1)                    # [S, C, 2]
+    b.coef = coef.repeat(ns, 1, 1)                                      # sample n belongs to split n % S
+    b.save = torch.stack([mean, invstd], 0)
+    b.rm_new = (1 - b.momentum) * b.rm + b.momentum * mean
+    b.rv_new = (1 - b.momentum) * b.rv + b.momentum * (var * cnt / (cnt - 1))
+    return b
+
+
+def dw_bn_bwd(N, C, seed=0):
+    """Statistics partials {sum g, sum g a} of a BN backward, gamma and the saved mean / invstd of x3d_dw333_bwd_stats (one
+    split), and what its finalize makes of them: cb [N, C, 3], dgamma, dbeta.  N count = 16."""
+    b = SimpleNamespace(count=16 // N)
+    M = float(b.count * N)
+    b.gamma = pick((C,), (1., -1., 0.5), (0.4, 0.3, 0.3), seed + 50)
+    mean = pick((C,), (0., 0.5, -0.5), (0.4, 0.3, 0.3), seed + 51)
+    invstd = pick((C,), (1., 2.), (0.5, 0.5), seed + 52)
+    b.save = torch.stack([mean, invstd], 0).view(2, 1, C)
+    k = b.gamma * invstd
+    c1 = pick((C,), (0., 0.5, -0.5), (0.4, 0.3, 0.3), seed + 53)
+    c2 = pick((C,), (0., 0.5, -0.5), (0.4, 0.3, 0.3), seed + 54)
+    sgx = -c1 * M / (k * invstd)
+    sg = -(c2 + mean * c1) * M / k
+    sga = sgx / invstd + mean * sg
+    b.sp = _spread(torch.stack([sg, sga], -1), N)
+    b.dgamma, b.dbeta = sgx, sg
+    # the kernel's own expressions
+    sgx_k = (sga - mean * sg) * invstd
+    cb = torch.stack([k, -k * invstd * sgx_k / M, -k * sg / M + k * invstd * mean * sgx_k / M], -1)
+    assert torch.equal(cb, torch.stack([k, c1, c2], -1)) and torch.equal(sgx_k, sgx)
+    b.cb = cb[None].repeat(N, 1, 1)
+    return b
+
+
+def dw_mx_bn_fwd_case(case, S, seed=None):
+    """(case, BN side) of x3d_dw333_fwd_stats: the hot case whose prologue is what the finalize derives."""
+    b = dw_bn_fwd(case[0], case[1], S, DW_BN_SEED.get(tuple(case), 0) if seed is None else seed)
+    return dw_mx_case(case, seed, pre=b.coef), b
+
+
+def dw_mx_bn_bwd_case(case, seed=None):
+    """(case, BN side) of x3d_dw333_bwd_stats: the hot case whose combine coefficients are what the finalize derives."""
+    b = dw_bn_bwd(case[0], case[1], 0 if seed is None else seed)
+    return dw_mx_case(case, seed, cb=b.cb), b
+
+
+def dw_bn_splits(case):
+    """The split counts the forward BN form is run with: one split per sample, and one split over both samples."""
+    return [case[0]] + ([1] if case[0] == 2 else [])
 
 
 # ----------------------------------------------------------------------------------------------------- case lists

@@ -14,7 +14,10 @@ whole-tensor norm, a split term lost in a forward kernel (the two-term form sits
 3. operands as the Trainer hands them: parameters, running statistics and weight-gradient outputs as views at unpadded
    (+2, +1, +3 float) offsets inside one NaN-filled flat buffer, bitwise the fresh-tensor call, the rest of the buffer
    untouched;
-4. the head GEMMs on integer inputs."""
+4. the head GEMMs on integer inputs;
+5. mixed storage (bf16 storage of the wide tensors): every entry point that takes `mx`, on hot integer inputs whose bf16 stores
+   round -- a bf16 output is bitwise `ref64.float().bfloat16()`, its statistics are bitwise the fp64 sums over the STORED
+   tensor; also the BN-finalize forms of the channelwise kernels (dw333_fwd_stats, dw333_bwd(bn=...)) in both storage modes."""
 import pytest
 import torch
 
@@ -91,6 +94,28 @@ def _eq_stats(partial, ref0, ref1, what):
 
 def _to(t, dev):
     return None if t is None else t.float().contiguous().to(dev)
+
+
+BF = torch.bfloat16
+
+
+def _to_bf(t, dev):
+    """A tensor a kernel reads as bf16: the cast must not change a value (tests/test_exact_inputs_host.py proves it does not)."""
+    b = t.float().to(BF)
+    assert torch.equal(b.double(), t.double()), "not a bf16 tensor (bug in the case)"
+    return b.contiguous().to(dev)
+
+
+def _eq_bf(got, ref64, what):
+    """got (bf16, from the GPU) is bitwise the round-to-nearest-even bf16 of the fp64 reference, which is an fp32 number."""
+    f = ref64.float()
+    assert torch.equal(f.double(), ref64), what + ": the reference is not representable in fp32 (bug in the case)"
+    ref = f.to(BF)
+    g = got.detach().cpu()
+    assert g.dtype == BF and g.numel() == ref.numel(), (what, g.dtype, tuple(g.shape), tuple(ref.shape))
+    g = g.reshape(ref.shape)
+    if not torch.equal(g, ref):
+        raise AssertionError("%s: %s" % (what, _where(~(g == ref), g.float(), ref.float())))
 
 
 BWD_OPTS = ({}, {"bwd_terms": 2}, {"dgrad_f32": 1, "wgrad_f32": 1})      # integers are pure hi: all exact
@@ -182,18 +207,22 @@ def test_pw_exact_integers_sixteen_wave_modes(mode):
             _pw_backward(ops, c, r, d, "%s pw_waves16 %d" % (case, mode))
 
 
-def _fused(ops, case, dev, what=""):
+def _fused(ops, case, dev, what="", ga_bf=False):
+    """ga_bf: the hot case with g and a handed over as bf16 tensors (X3D_MX_GA); every output is fp32 and keeps its reference."""
     N, Ci, Co, T, H, W, act = case
     P = T * H * W
-    assert ops.pw_bwd_fused_ok(Ci, Co, P)
-    c = ei.fused_case(case)
+    mx = ops.MX_GA if ga_bf else 0
+    assert ops.pw_bwd_fused_ok(Ci, Co, P, mx=mx)
+    c = ei.fused_mx_case(case) if ga_bf else ei.fused_case(case)
     r = ei.fused_ref(c)
     d = {k: _to(getattr(c, k), dev) for k in ("x", "w", "pre", "xo", "ex", "g", "a", "cb", "addend", "add2")}
+    if ga_bf:
+        d["g"], d["a"] = _to_bf(c.g, dev), _to_bf(c.a, dev)
     wpt = ops.pw_pack(d["w"], transposed=True)
-    tag = "%s %s pw_bwd_fused" % (case, what)
+    tag = "%s %s pw_bwd_fused%s" % (case, what, " (g, a bf16)" if ga_bf else "")
     adds = {0: (None, 1), 1: (d["addend"], 1), 2: (d["add2"], 2)}
     for k in (0, 1, 2):                                                   # mode 0: plain (+ addend)
-        if not ops.pw_bwd_fused_ok(Ci, Co, P, 0, k != 0):                 # (epilogue, addend) pairs the entry point refuses
+        if not ops.pw_bwd_fused_ok(Ci, Co, P, 0, k != 0, mx):             # (epilogue, addend) pairs the entry point refuses
             continue
         dx, partial, dw = ops.pw_bwd_fused(d["g"], d["a"], d["cb"], (Co, Ci), wpt, d["x"], mode=0, addend=adds[k][0],
                                            addend_stride=adds[k][1])
@@ -202,14 +231,14 @@ def _fused(ops, case, dev, what=""):
         _eq(dw, r["m0_dw"], "%s mode 0 dW (addend %d)" % (tag, k))
     if c.act:                                                             # mode 1: ReLU backward of the conv's input
         for k in (0, 2):
-            if not ops.pw_bwd_fused_ok(Ci, Co, P, 1, k != 0):
+            if not ops.pw_bwd_fused_ok(Ci, Co, P, 1, k != 0, mx):
                 continue
             dx, partial, dw = ops.pw_bwd_fused(d["g"], d["a"], d["cb"], (Co, Ci), wpt, d["x"], xpre=d["pre"], xact=1, mode=1,
                                                addend=adds[k][0], addend_stride=adds[k][1])
             _eq(dx, r["m1_dx%d" % k], "%s mode 1 dx (addend %d)" % (tag, k))
             _eq(dw, r["m1_dw"], "%s mode 1 dW (addend %d)" % (tag, k))
             _eq_stats(partial, r["m1_dx%d_sg" % k], r["m1_dx%d_sgx" % k], "%s mode 1 statistics (addend %d)" % (tag, k))
-    if ops.pw_bwd_fused_ok(Ci, Co, P, 2, True):                           # mode 2: residual-add + ReLU backward
+    if ops.pw_bwd_fused_ok(Ci, Co, P, 2, True, mx):                        # mode 2: residual-add + ReLU backward
         for k in (1, 2):
             dx, partial, dw = ops.pw_bwd_fused(d["g"], d["a"], d["cb"], (Co, Ci), wpt, d["xo"], mode=2, ex=d["ex"],
                                                addend=adds[k][0], addend_stride=adds[k][1])
@@ -661,3 +690,228 @@ def test_elementwise_sgd_and_grad_accumulate_on_flat_buffer_ranges(n):
 
     params = {"w": _rn(n, seed=1), "g": _rn(n, seed=2), "acc": _nan(n), "m": _nan(n)}
     _as_the_trainer_hands_them(dev, fn, params, "sgd / accumulate n = %d" % n)
+
+
+# --------------------------------------------------------------------------------------------------- 5. mixed storage
+# bf16 storage of the wide tensors (include/x3dhip.h X3D_MX_*) on the HOT integer inputs of tests/exact_inputs.py, whose bf16
+# stores really round (ties both ways, non-ties both ways; tests/test_exact_inputs_host.py proves it per case and shows that a
+# truncating store, a store rounding half away from zero and statistics taken before the store all differ from these
+# references).  A bf16 output is compared with `ref64.float().bfloat16()`, the statistics that describe it with the fp64 sums
+# over THAT tensor, everything else with the fp32 case's reference.  Entry point (flags its header comment admits) -> test:
+#   x3d_pw_fwd             X, Y, X|Y (packed weights); y and statistics          test_pw_exact_mx
+#   x3d_pw_bwd_data        GA (dense / stride-2 addend, ReLU backward);
+#                          X|Y and GA|X|Y with ReLU backward; out and statistics test_pw_exact_mx
+#   x3d_pw_bwd_data_res    GA; three addend forms; out and statistics            test_pw_exact_mx
+#   x3d_pw_bwd_weight      GA, X, GA|X; single and through DeferredGrads
+#   (x3d_pw_bwd_weight_batch)                                                    test_pw_exact_mx
+#   x3d_pw_bwd_fused       GA in modes 0 / 1 / 2 (all addend forms); X|Y in
+#                          mode 1; dx, dW, statistics                            test_pw_exact_mx_bwd_fused
+#   x3d_pw_fwd, x3d_pw_bwd_fused   persistent loops on 3 / 40 workgroups         test_pw_exact_mx_long_item_loops
+#   x3d_dw333_fwd          X|Y                                                   test_dw333_exact_mx
+#   x3d_dw333_bwd          GA|X|Y; dx, dw, statistics                            test_dw333_exact_mx
+#   x3d_dw333_fwd_stats    0 and X|Y; y, statistics, coef, save, running stats   test_dw333_exact_bn_forms
+#   x3d_dw333_bwd_stats    0 and GA|X|Y; dx, dw, statistics, dgamma, dbeta       test_dw333_exact_bn_forms
+#   x3d_pw_bwd_tiles, x3d_pw_bwd_fused_ok   (queries with the call's mx)         asked by the ops layer in every call above
+# The backward entry points of the pointwise convs run under bwd_terms 3 and 2 (exact either way: dY is hi + mid, every other
+# operand pure hi).
+MX_BWD_OPTS = ({}, {"bwd_terms": 2})
+# the kernel a case must land on in the mixed mode: (forward, data gradient).  * = another kernel than the fp32 mode runs
+_S, _P3, _P6, _P7 = "pw_fwd_stream_kernel", "pw3_kernel", "pw6_kernel", "pw7_kernel"
+MX_KERNELS = {(2, 24, 54, 4, 16, 16, 1): (_S, _P3), (2, 54, 24, 4, 16, 16, 1): (_P3, _P3), (2, 48, 216, 4, 6, 6, 0): (_P3, _P3),
+              (1, 24, 54, 2, 9, 7, 1): (_P3, _P3), (1, 54, 24, 2, 9, 7, 1): (_P3, _P3),                    # *
+              (2, 96, 216, 4, 12, 12, 0): (_P6, _P7),                                                      # *
+              (2, 216, 96, 4, 12, 12, 1): (_P6, _P7), (2, 432, 192, 2, 6, 6, 1): (_P6, _P7), (2, 192, 432, 2, 6, 6, 0): (_P6, _P7),
+              (2, 54, 54, 2, 8, 8, 1): (_S, _P3),
+              (1, 96, 216, 2, 7, 7, 0): (_P3, _P3), (1, 216, 96, 2, 7, 7, 1): (_P3, _P3)}                  # *
+
+
+def _pw_device_mx(c, dev):
+    d = _pw_device(c, dev)
+    d.update({k + "_bf": _to_bf(getattr(c, k), dev) for k in ("x", "g", "a")})
+    return d
+
+
+def _pw_forward_mx(ops, c, r, d, what):
+    wp = ops.pw_pack(d["w"])
+    for xb, yb in ((True, False), (False, True), (True, True)):
+        y, partial = ops.pw_fwd(d["x_bf"] if xb else d["x"], d["w"], pre=d["pre"], pre_act=c.act, wp=wp,
+                                out_dtype=BF if yb else torch.float32)
+        tag = "%s pw_fwd(x %s, y %s)" % (what, "bf16" if xb else "fp32", "bf16" if yb else "fp32")
+        if yb:
+            _eq_bf(y, r["y"], tag + " y")
+            _eq_stats(partial, r["y_st_s0"], r["y_st_s1"], tag + " statistics of the stored y")
+        else:
+            _eq(y, r["y"], tag + " y")
+            _eq_stats(partial, r["sy"], r["sy2"], tag + " statistics")
+
+
+def _pw_backward_mx(ops, c, r, d, what):
+    """Returns the kernel the data gradient (g, a bf16) ran on."""
+    from x3dhip import _lib
+    N, Ci, Co = c.shape[:3]
+    cb, w, pre = d["cb"], d["w"], d["pre"]
+    for ga, xb in ((True, False), (False, True), (True, True)):
+        g, a, x = d["g_bf" if ga else "g"], d["a_bf" if ga else "a"], d["x_bf" if xb else "x"]
+        tag = "%s pw_bwd_weight(g, a %s, x %s)" % (what, "bf16" if ga else "fp32", "bf16" if xb else "fp32")
+        _eq(ops.pw_bwd_weight(g, a, cb, x, (Co, Ci), pre=pre, pre_act=c.act), r["dw"], tag)
+        df = ops.DeferredGrads()
+        dw = ops.pw_bwd_weight(g, a, cb, x, (Co, Ci), pre=pre, pre_act=c.act, defer=df)
+        df.flush()
+        _eq(dw, r["dw"], tag + " through DeferredGrads")
+    wpt = ops.pw_pack(w, transposed=True)
+    g, a = d["g_bf"], d["a_bf"]                                           # GA: fp32 outputs, the fp32 case's references
+    tag = what + " (g, a bf16)"
+    out, partial = ops.pw_bwd_data(g, a, cb, w, x=d["x"] if c.act else None, pre=pre, pre_act=c.act, addend=d["addend"], wpt=wpt)
+    kernel = _lib.last_kernel()
+    _eq(out, r["dx_add"], tag + " pw_bwd_data + addend%s" % (" + ReLU backward" if c.act else ""))
+    if c.act:
+        _eq_stats(partial, r["dx_sg"], r["dx_sgx"], tag + " pw_bwd_data statistics")
+    out, _ = ops.pw_bwd_data(g, a, cb, w, addend=d["add2"], addend_stride=2, wpt=wpt)
+    _eq(out, r["dx_add2"], tag + " pw_bwd_data + stride-2 addend")
+    for name, add, astride in (("res0", None, 1), ("res1", d["addend"], 1), ("res2", d["add2"], 2)):
+        out, partial = ops.pw_bwd_data_res(g, a, cb, w, d["res_out"], d["res_raw"], addend=add, addend_stride=astride, wpt=wpt)
+        _eq(out, r[name], tag + " pw_bwd_data_res " + name)
+        _eq_stats(partial, r[name + "_sg"], r[name + "_sgx"], tag + " pw_bwd_data_res statistics " + name)
+    if c.act:                                                             # X | Y, and all three flags: x and its gradient bf16
+        for ga in (False, True):
+            tag = "%s pw_bwd_data(g, a %s, x bf16, out bf16) ReLU backward" % (what, "bf16" if ga else "fp32")
+            out, partial = ops.pw_bwd_data(d["g_bf" if ga else "g"], d["a_bf" if ga else "a"], cb, w, x=d["x_bf"], pre=pre,
+                                           pre_act=1, wpt=wpt, out_dtype=BF)
+            _eq_bf(out, r["dx_act"], tag)
+            _eq_stats(partial, r["dx_act_st_s0"], r["dx_act_st_s1"], tag + " statistics of the stored gradient")
+    return kernel
+
+
+@pytest.mark.parametrize("case", ei.PW_MX)
+def test_pw_exact_mx(case):
+    """Every pointwise entry point but the fused one in the mixed-storage mode, on every kernel that mode has of its own:
+    bf16 outputs bitwise RNE of the fp64 reference, their statistics bitwise the fp64 sums over the stored tensor, fp32
+    outputs bitwise the fp64 reference."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    c = ei.pw_mx_case(case)
+    r = ei.pw_mx_ref(c)
+    d = _pw_device_mx(c, dev)
+    _pw_forward_mx(ops, c, r, d, "%s" % (case,))
+    kernels = [_lib.last_kernel()]
+    for opts in MX_BWD_OPTS:
+        with _lib.options(**opts):
+            kernels.append(_pw_backward_mx(ops, c, r, d, "%s %s" % (case, opts)))
+    assert tuple(kernels) == MX_KERNELS[case] + MX_KERNELS[case][1:], (case, kernels)
+
+
+def _fused_xy(ops, case, dev, what=""):
+    """X3D_MX_X | X3D_MX_Y: x and dx bf16, activation-backward mode without addend."""
+    N, Ci, Co, T, H, W, act = case
+    assert ops.pw_bwd_fused_ok(Ci, Co, T * H * W, 1, False, ops.MX_X | ops.MX_Y)
+    c = ei.fused_mx_case(case)
+    r = ei.fused_mx_ref(c)
+    g, a, cb, w, pre = (_to(getattr(c, k), dev) for k in ("g", "a", "cb", "w", "pre"))
+    tag = "%s %s pw_bwd_fused (x, dx bf16)" % (case, what)
+    dx, partial, dw = ops.pw_bwd_fused(g, a, cb, (Co, Ci), ops.pw_pack(w, transposed=True), _to_bf(c.x, dev), xpre=pre, xact=1, mode=1)
+    _eq_bf(dx, r["m1_dx0"], tag + " dx")
+    _eq(dw, r["m1_dw"], tag + " dW")
+    _eq_stats(partial, r["m1_dx0_st_s0"], r["m1_dx0_st_s1"], tag + " statistics of the stored gradient")
+
+
+@pytest.mark.parametrize("terms", [3, 2])
+@pytest.mark.parametrize("case", ei.FUSED_MX)
+def test_pw_exact_mx_bwd_fused(case, terms):
+    """x3d_pw_bwd_fused: g, a bf16 in modes 0 / 1 / 2 with every addend form (fp32 outputs), x and dx bf16 in mode 1."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    with _lib.options(bwd_terms=terms):
+        _fused(ops, case, dev, "terms %d" % terms, ga_bf=True)
+        _fused_xy(ops, case, dev, "terms %d" % terms)
+
+
+@pytest.mark.parametrize("grid", [3, 40])
+def test_pw_exact_mx_long_item_loops(grid):
+    """The persistent kernels of the mixed mode (streaming forward, fused backward) with 3 / 40 workgroups, as
+    test_pw_exact_integers_long_item_loops (the whole-K forward kernel pw8 has no mixed-storage build: pw8_grid is inert)."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    with _lib.options(pw8_grid=grid, pw8_max_k=224, fb_grid=grid):
+        for case in ei.PW_MX_GRID:
+            c = ei.pw_mx_case(case)
+            _pw_forward_mx(ops, c, ei.pw_mx_ref(c), _pw_device_mx(c, dev), "%s grid %d" % (case, grid))
+            assert _lib.last_kernel() == "pw_fwd_stream_kernel", _lib.last_kernel()
+        for case in ei.FUSED_MX_GRID:
+            _fused(ops, case, dev, "grid %d" % grid, ga_bf=True)
+            _fused_xy(ops, case, dev, "grid %d" % grid)
+
+
+def _dw_device_mx(c, dev):
+    d = {k: _to(getattr(c, k), dev) for k in ("x", "w", "pre", "g", "a", "cb")}
+    d.update({k + "_bf": _to_bf(getattr(c, k), dev) for k in ("x", "g", "a")})
+    return d
+
+
+@pytest.mark.parametrize("case", ei.DW_MX)
+def test_dw333_exact_mx(case):
+    """dw333_fwd (x, y bf16) and dw333_bwd (g, a, x, dx bf16): y and dx bitwise RNE of the fp64 reference, both statistics
+    bitwise the fp64 sums over the stored tensors, dw bitwise the fp64 reference."""
+    from x3dhip import ops
+    dev = _dev()
+    c = ei.dw_mx_case(case)
+    r = ei.dw_mx_ref(c)
+    d = _dw_device_mx(c, dev)
+    what = "%s" % (case,)
+    y, partial = ops.dw333_fwd(d["x_bf"], d["w"], stride=c.s, pre=d["pre"], pre_act=1)
+    _eq_bf(y, r["y"], what + " dw333_fwd y")
+    _eq_stats(partial, r["y_st_s0"], r["y_st_s1"], what + " dw333_fwd statistics of the stored y")
+    out, dw, bp = ops.dw333_bwd(d["g_bf"], d["a_bf"], d["cb"], d["w"], d["x_bf"], stride=c.s, pre=d["pre"], pre_act=1)
+    _eq_bf(out, r["dx"], what + " dw333_bwd dx")
+    _eq(dw, r["dw"], what + " dw333_bwd dw")
+    _eq_stats(bp, r["dx_st_s0"], r["dx_st_s1"], what + " dw333_bwd statistics of the stored gradient")
+    # the same hot inputs in fp32 storage: nothing rounds
+    _dw(ops, c, r, d, what + " fp32 storage")
+
+
+@pytest.mark.parametrize("case", ei.DW_MX)
+def test_dw333_exact_bn_forms(case):
+    """x3d_dw333_fwd_stats and x3d_dw333_bwd_stats (the producer BN's finalize in the kernel's prologue), fp32 and bf16
+    storage: coef, save, the running statistics, dgamma and dbeta bitwise what the fp64 finalize gives on dyadic statistics
+    (the same in both storage modes), y / dx and their statistics as in test_dw333_exact_mx."""
+    from x3dhip import ops
+    dev = _dev()
+    N, C = case[:2]
+    for S in ei.dw_bn_splits(case):
+        c, b = ei.dw_mx_bn_fwd_case(case, S)
+        r = ei.dw_mx_ref(c)
+        d = _dw_device_mx(c, dev)
+        sp, gamma, beta = _to(b.sp, dev), _to(b.gamma, dev), _to(b.beta, dev)
+        for bf in (False, True):
+            what = "%s S = %d dw333_fwd_stats (%s)" % (case, S, "bf16" if bf else "fp32")
+            rm, rv = _to(b.rm, dev), _to(b.rv, dev)
+            y, partial, coef, save = ops.dw333_fwd_stats(d["x_bf" if bf else "x"], d["w"], sp, S, b.count, gamma, beta, rm.view(-1),
+                                                         rv.view(-1), stride=c.s, pre_act=1, momentum=b.momentum, eps=b.eps)
+            _eq(coef, b.coef, what + " coef")
+            _eq(save, b.save, what + " save")
+            _eq(rm, b.rm_new, what + " running mean")
+            _eq(rv, b.rv_new, what + " running variance")
+            if bf:
+                _eq_bf(y, r["y"], what + " y")
+                _eq_stats(partial, r["y_st_s0"], r["y_st_s1"], what + " statistics of the stored y")
+            else:
+                _eq(y, r["y"], what + " y")
+                _eq_stats(partial, r["sy"], r["sy2"], what + " statistics")
+    c, b = ei.dw_mx_bn_bwd_case(case)
+    r = ei.dw_mx_ref(c)
+    d = _dw_device_mx(c, dev)
+    sp, gamma, save = _to(b.sp, dev), _to(b.gamma, dev), _to(b.save, dev)
+    for bf in (False, True):
+        what = "%s dw333_bwd(bn=...) (%s)" % (case, "bf16" if bf else "fp32")
+        dgamma, dbeta = torch.full((C,), _NAN, device=dev), torch.full((C,), _NAN, device=dev)
+        g, a, x = (d[k + "_bf" if bf else k] for k in ("g", "a", "x"))
+        out, dw, bp = ops.dw333_bwd(g, a, None, d["w"], x, stride=c.s, pre=d["pre"], pre_act=1,
+                                    bn=(sp, b.count, gamma, save, dgamma, dbeta))
+        _eq(dgamma, b.dgamma, what + " dgamma")
+        _eq(dbeta, b.dbeta, what + " dbeta")
+        _eq(dw, r["dw"], what + " dw")
+        if bf:
+            _eq_bf(out, r["dx"], what + " dx")
+            _eq_stats(bp, r["dx_st_s0"], r["dx_st_s1"], what + " statistics of the stored gradient")
+        else:
+            _eq(out, r["dx"], what + " dx")
+            _eq_stats(bp, r["sg"], r["sgx"], what + " statistics")

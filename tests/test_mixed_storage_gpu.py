@@ -9,8 +9,11 @@ result (bf16 outputs).  Statistics that describe a bf16 OUTPUT (BN sums of a for
 gradient) are taken from the values as stored, so that the BN which follows sees the statistics of the tensor it reads:
 they are compared with fp64 sums over the stored tensor.
 The fp32 builds themselves are pinned to the fp64 oracle in tests/test_ops_gpu.py, so parity is transitive.
-Where the mixed mode picks another kernel than the fp32 default (one shape, see test_pw_bwd_data_mx), the comparison is the
-fp32 tolerance of test_ops_gpu.py instead of bitwise."""
+Where the mixed mode picks another kernel than the fp32 default (P % 4 != 0 at the large-channel layers, the conv1 data
+gradient with Cin = 96 and 128 < Cout < 256), the comparison HERE, on random floats, is the fp32 tolerance of test_ops_gpu.py
+instead of bitwise; those shapes are held exactly, bf16 rounding and the statistics of the stored tensors included, by
+section 5 of tests/test_exact_gpu.py (`torch.equal` against fp64 on integer inputs whose bf16 stores round), which also holds
+the same-kernel shapes, the BN-finalize forms of the channelwise kernels and round-to-nearest-even on exact ties."""
 import numpy as np
 import pytest
 import torch
@@ -319,6 +322,19 @@ def test_dw333_mx(case):
     d0, w0, b0 = ops.dw333_bwd(g, a, cb, w, x, stride=s, pre=pre, pre_act=1)
     d1, w1, b1 = ops.dw333_bwd(g.to(BF), a.to(BF), cb, w, x.to(BF), stride=s, pre=pre, pre_act=1)
     assert d1.dtype == BF and _same(d1, d0.to(BF)) and _same(w1, w0)
+    _stats_of(b1, d1, x)
+    # the form the engine calls in every bottleneck: the producer BN's backward finalize in the prologue (bn=...,
+    # x3d_dw333_bwd_stats, one split).  The finalize reads fp32 partials only: cb, dgamma and dbeta cannot depend on the storage
+    spb = torch.stack([_g(N, C, 3, seed=13, dev=dev), 2 * _g(N, C, 3, seed=14, dev=dev)], -1).contiguous()
+    save = torch.stack([0.1 * _g(1, C, seed=15, dev=dev), 1 + 0.1 * _g(1, C, seed=16, dev=dev).abs()], 0).contiguous()
+    runs = []
+    for gg, aa, xx in ((g, a, x), (g.to(BF), a.to(BF), x.to(BF))):
+        dgamma, dbeta = torch.full((C,), float("nan"), device=dev), torch.full((C,), float("nan"), device=dev)
+        runs.append(ops.dw333_bwd(gg, aa, None, w, xx, stride=s, pre=pre, pre_act=1,
+                                  bn=(spb, T * Ho * Wo, gamma, save, dgamma, dbeta)) + (dgamma, dbeta))
+    (d0, w0, b0, dg0, db0), (d1, w1, b1, dg1, db1) = runs
+    assert d1.dtype == BF and _same(d1, d0.to(BF)) and _same(w1, w0)
+    assert bool(torch.isfinite(dg0).all()) and _same(dg1, dg0) and _same(db1, db0)
     _stats_of(b1, d1, x)
 
 
