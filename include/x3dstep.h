@@ -1,0 +1,133 @@
+/*
+ * x3dstep.h -- C ABI of libx3dstep.so: HIP kernels (gfx950 / MI355X) that look at the flat gradient between the
+ * all-reduce and the fused SGD kernel: per-tensor statistics (fp64 sum of squares, count of non-finite elements, a 64-bit
+ * hash of the bits), a record of them in a device-resident ring, and clipping by the global norm (the rule of
+ * torch.nn.utils.clip_grad_norm_).
+ *
+ * A separate library from libx3dhip.so on purpose: tools/stamp.py and the gradient-hash record hash the training library's
+ * sources, and nothing here changes them.
+ *
+ * Conventions (as include/x3deval.h)
+ *   - plain pointers and sizes; the caller (torch) owns every buffer; every kernel is enqueued on the hipStream_t passed
+ *     as `stream`; x3dstep_observe never allocates and never synchronises (it may be captured into a graph)
+ *   - return 0 on success, negative X3DSTEP_E* on failure; x3dstep_last_error() gives the message (thread-local)
+ *   - deterministic bit for bit: no float atomics, every sum in a fixed order, every output element written once
+ *   - the *_host entry points take host pointers only and run the same per-item and per-tensor code (step_core.h)
+ *
+ * Tables (built once per flat buffer)
+ *   seg_off   int64 [S + 1]        tensor s is g[seg_off[s] .. seg_off[s + 1]); seg_off[0] = 0, every tensor has between 1
+ *                                  and 2^31 - 1 elements, seg_off[S] = n
+ *   items     X3DStepItem [nitems] a tensor cut into pieces of at most X3DSTEP_ITEM elements, the pieces of one tensor
+ *                                  consecutive and in order; one wave of launch 1 takes one item
+ *   seg_item  int32 [S + 1]        the items of tensor s are items[seg_item[s] .. seg_item[s + 1])
+ *
+ * The statistics of tensor s with elements x_0 .. x_{k-1}
+ *   sumsq      fp64: per item, lane l = ((start mod 4 + j) / 4) mod 64 adds (double) x_j * (double) x_j (an exact product) of
+ *              its elements in rising j (start: the item's first element in g, j: the index within the item); the 64 lanes
+ *              are summed by halving (l += l + 32, l += l + 16, ..); the items of the tensor are added in item order by one
+ *              thread, as the tensors are for the total: both with a compensated (Neumaier) sum, which a step that leaves
+ *              the finite numbers drops out of, so that Inf and NaN stay what plain addition gives
+ *   nonfinite  int32: elements whose exponent bits are all ones (NaN, +Inf, -Inf)
+ *   hash       uint64: sum mod 2^64 over j of splitmix64((j << 32) | bits(x_j)), j the index within the TENSOR;
+ *              splitmix64(z): z += 0x9e3779b97f4a7c15; z = (z ^ z >> 30) * 0xbf58476d1ce4e5b9;
+ *              z = (z ^ z >> 27) * 0x94d049bb133111eb; z ^ z >> 31
+ *
+ * The record of one step (x3dstep_record_bytes(S) bytes, 8-byte aligned, little-endian)
+ *   offset 0                     X3DStepHeader (40 bytes)
+ *   offset 40                    fp64   sumsq[S]
+ *   offset 40 + 8 S              uint64 hash[S]
+ *   offset 40 + 16 S             int32  nonfinite[S]
+ *   padded to a multiple of 8
+ * The ring holds R records; the step with counter c is written to slot c mod R.
+ *
+ * The state (int64 [X3DSTEP_STATE_WORDS] on the device; the caller sets it to {0, -1, -1, 0, ..} before the first step)
+ *   [X3DSTEP_S_STEP]      steps observed so far (the counter the next record carries)
+ *   [X3DSTEP_S_BAD_STEP]  sticky: the first step that had a non-finite element, -1 while there was none
+ *   [X3DSTEP_S_BAD_SEG]   sticky: the lowest tensor with a non-finite element at that step, -1 likewise
+ *   [X3DSTEP_S_NORM]      the bits of the fp64 norm of the latest step
+ *   [X3DSTEP_S_COEF]      low 32 bits: the bits of the fp32 coefficient of the latest step (launch 3 reads it here)
+ */
+#ifndef X3DSTEP_H
+#define X3DSTEP_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define X3DSTEP_ABI_VERSION 1
+
+#define X3DSTEP_OK 0
+#define X3DSTEP_EINVAL (-1)   /* bad size / null or unaligned pointer / inconsistent table */
+#define X3DSTEP_ELAUNCH (-2)  /* hipLaunch error */
+
+/* Elements per item.  X3D-M (316 tensors, 3.79 M elements) gives about 2000 items, X3DSTEP_ITEMS_PER_GROUP to a
+ * workgroup: about 500 workgroups for the 256 CUs of the card. */
+#define X3DSTEP_ITEM 2048
+#define X3DSTEP_ITEMS_PER_GROUP 4
+
+#define X3DSTEP_S_STEP 0
+#define X3DSTEP_S_BAD_STEP 1
+#define X3DSTEP_S_BAD_SEG 2
+#define X3DSTEP_S_NORM 3
+#define X3DSTEP_S_COEF 4
+#define X3DSTEP_STATE_WORDS 8
+
+#define X3DSTEP_MAX_SEGMENTS (1 << 20)
+#define X3DSTEP_MAX_ITEMS 0x7fffff00
+
+typedef struct {
+    int64_t start;  /* first element in g */
+    int32_t seg;    /* tensor */
+    int32_t len;    /* 1 .. X3DSTEP_ITEM */
+} X3DStepItem;
+
+typedef struct {
+    int64_t step;       /* the counter of this step */
+    double total;       /* sum over the tensors, in tensor order, of sumsq[s] */
+    double norm;        /* sqrt(total) * inv_world */
+    float coef;         /* (float) min(1, max_norm / (norm + 1e-6)) computed in fp64; 1 when max_norm <= 0 */
+    int32_t nonfinite;  /* sum of nonfinite[s] */
+    int32_t first_bad;  /* the lowest s with nonfinite[s] > 0, or -1 */
+    int32_t nseg;       /* S */
+} X3DStepHeader;
+
+int x3dstep_abi_version(void);
+const char* x3dstep_last_error(void);
+size_t x3dstep_item_bytes(void);
+size_t x3dstep_header_bytes(void);
+size_t x3dstep_record_bytes(int S);
+
+/* Items the table of this segment table has (host only); negative X3DSTEP_E* when the table is refused. */
+int64_t x3dstep_item_count(const int64_t* seg_off, int S);
+/* Writes the item table and seg_item [S + 1] (host only, host pointers); `cap`: items the caller allocated.  Returns the
+ * count, or negative X3DSTEP_E*. */
+int64_t x3dstep_build_items(const int64_t* seg_off, int S, X3DStepItem* items, int64_t cap, int32_t* seg_item);
+
+/* Bytes of the scratch the partials of `nitems` items take (host only): fp64 [nitems], uint64 [nitems], int32 [nitems]. */
+size_t x3dstep_workspace_bytes(int64_t nitems);
+
+/*
+ * One step: launch 1 (partials: a wave per item), launch 2 (finalize: one workgroup; the record, the state) and, when
+ * max_norm > 0, launch 3 (g[i] = g[i] * coef, one fp32 multiply; it leaves at once when coef == 1.0f).
+ *   g fp32 [n], 4-byte aligned (16-byte aligned for the vector loads of launch 1; launch 3 vectorises by address);
+ *   workspace: x3dstep_workspace_bytes(nitems) bytes, 8-byte aligned; ring: R * x3dstep_record_bytes(S) bytes, 8-byte aligned
+ *   inv_world: 1 / world, what the SGD kernel multiplies the summed gradient by
+ * coef: NaN and Inf are left as the arithmetic gives them (a NaN norm gives a NaN coefficient, an infinite one 0).
+ */
+int x3dstep_observe(float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items, const int32_t* seg_item,
+                    int64_t nitems, void* workspace, int64_t* state, void* ring, int R, double max_norm, double inv_world,
+                    void* stream);
+
+/* The CPU twin: host pointers, the same code item by item and tensor by tensor, the same bytes. */
+int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                         const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring, int R,
+                         double max_norm, double inv_world);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* X3DSTEP_H */

@@ -196,7 +196,7 @@ def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
 
 def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
-        device=None, process_group=None, rank=0, world=1, base_bn_splits=1):
+        device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -204,7 +204,9 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     table and the reference's hard-coded 224).  Returns a dict: 'steps', 'epochs', 'phases' (one record per phase),
     'checkpoints', 'lr'.  process_group / rank / world: data parallel over that group, one rank per GPU (see the
     module docstring; batch_size is the GLOBAL batch and must be a multiple of world).  base_bn_splits: the BatchNorm
-    splits of a training batch (a single process with `world` splits normalises as `world` ranks do)."""
+    splits of a training batch (a single process with `world` splits normalises as `world` ranks do).
+    clip_grad_norm / monitor: Trainer(clip_grad_norm=, monitor=); with either, the training log line gains `gnorm` and
+    `clip` (of the latest update) and rank 0 reports the first non-finite gradient when the run ends, also on an exception."""
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
     ddp = process_group is not None and world > 1
@@ -253,7 +255,9 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     say('INIT LR: %f' % lr)
     optimizer = Trainer(x3d, lr=lr, momentum=0.9, weight_decay=1e-5, objective='loc' if loc else 'bce',
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update,
+                        clip_grad_norm=clip_grad_norm, monitor=monitor,
                         **(dict(process_group=process_group, world_size=world) if ddp else {}))
+    mon = getattr(optimizer, 'monitor', None)
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
     if ck is not None:
         optimizer.load_state_dict(ck['optimizer_state_dict'])
@@ -304,13 +308,15 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                                 tr_map = float(tr_apm.value().mean())
                             tr_apm.reset()
                             n = s_times * num_steps_per_update
+                            gline = '' if mon is None else ' gnorm {:.4e} clip {:.4f}'.format(float(mon.last_norm()),
+                                                                                              float(mon.last_coef()))
                             if loc:
-                                say(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'
+                                say(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}{}'
                                       .format(epochs, phase, steps, float(tot_loc_loss) / n, float(tot_cls_loss) / n,
-                                              float(tot_loss) / s_times, tr_map))
+                                              float(tot_loss) / s_times, tr_map, gline))
                             else:
-                                say(' Epoch:{} {} steps: {} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
-                                    epochs, phase, steps, float(tot_cls_loss) / n, float(tot_loss) / s_times, tr_map))
+                                say(' Epoch:{} {} steps: {} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}{}'.format(
+                                    epochs, phase, steps, float(tot_cls_loss) / n, float(tot_loss) / s_times, tr_map, gline))
                             rec['maps'].append(tr_map)
                             rec['losses'].append(float(tot_loss) / s_times)
                             tot_loss, tot_loc_loss, tot_cls_loss = zero.clone(), zero.clone(), zero.clone()
@@ -342,5 +348,8 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                                        lr=optimizer.param_groups[0]['lr'], steps=steps))
     finally:
         torch.cuda.synchronize()
+        bad = mon.first_nonfinite() if mon is not None else None
+        if bad is not None:
+            say(' first non-finite gradient: step {} parameter {}'.format(*bad))
     return dict(steps=steps, epochs=epochs, phases=phases, checkpoints=checkpoints, lr=optimizer.param_groups[0]['lr'],
                 scheduler=lr_sched, optimizer=optimizer, model=x3d)

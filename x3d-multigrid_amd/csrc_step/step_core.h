@@ -1,0 +1,217 @@
+// The arithmetic of libx3dstep (include/x3dstep.h) item by item and tensor by tensor, compiled into step.hip (the kernels)
+// and step_host.cpp (the CPU twin): what a lane adds and in which order, the sum of a tensor's items, the coefficient rule,
+// the record's layout and what the one finishing thread writes.  No HIP call, no global state.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/x3dstep.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define STEP_HD __host__ __device__ static inline
+#define STEP_HD_MEMBER __host__ __device__ inline
+#else
+#define STEP_HD static inline
+#define STEP_HD_MEMBER inline
+#endif
+
+namespace x3ds {
+
+constexpr int kLanes = 64;                 // lanes of a wave: the partial sums of an item
+constexpr int kFinalThreads = 1024;        // tensors per round of the finalize step
+
+struct Part {
+    double sumsq;
+    uint64_t hash;
+    int32_t nf;
+};
+
+struct alignas(16) Vec4 {
+    float v[4];
+};
+
+STEP_HD uint64_t splitmix64(uint64_t z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+STEP_HD uint32_t float_bits(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    return u;
+}
+
+// one element: idx is its index within the tensor
+STEP_HD void part_add(Part& p, uint64_t idx, float x) {
+    const uint32_t u = float_bits(x);
+    const double d = (double)x;
+    p.sumsq = p.sumsq + d * d;     // the product of two widened fp32 values is exact
+    p.nf += (u & 0x7f800000u) == 0x7f800000u ? 1 : 0;
+    p.hash += splitmix64((idx << 32) | (uint64_t)u);
+}
+
+// What lane `lane` of the wave that owns an item accumulates: the groups of four elements q = lane, lane + 64, ..; group q
+// holds the elements j of the item with (start mod 4 + j) / 4 == q, so that a whole group is one aligned 16-byte load when
+// g itself is 16-byte aligned (`vec`).  `first`: the index within the tensor of the item's first element.
+STEP_HD Part lane_part(const float* g, int64_t start, int len, uint64_t first, int lane, bool vec) {
+    Part p = {0.0, 0, 0};
+    const int m = (int)(start & 3);
+    const int groups = (m + len + 3) >> 2;
+    for (int q = lane; q < groups; q += kLanes) {
+        const int j0 = 4 * q - m;
+        if (vec && j0 >= 0 && j0 + 4 <= len) {
+            const Vec4 x = *(const Vec4*)(g + start + j0);
+            for (int e = 0; e < 4; ++e) part_add(p, first + (uint64_t)(j0 + e), x.v[e]);
+        } else {
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + e;
+                if (j >= 0 && j < len) part_add(p, first + (uint64_t)j, g[start + j]);
+            }
+        }
+    }
+    return p;
+}
+
+STEP_HD void part_merge(Part& a, const Part& b) {
+    a.sumsq = a.sumsq + b.sumsq;
+    a.hash += b.hash;
+    a.nf += b.nf;
+}
+
+// the scratch of the partials: fp64 [nitems], uint64 [nitems], int32 [nitems]
+struct Scratch {
+    double* sumsq;
+    uint64_t* hash;
+    int32_t* nf;
+};
+
+STEP_HD size_t scratch_bytes(int64_t nitems) { return (((size_t)nitems * 20) + 7) & ~(size_t)7; }
+
+STEP_HD Scratch scratch_at(void* ws, int64_t nitems) {
+    Scratch s;
+    s.sumsq = (double*)ws;
+    s.hash = (uint64_t*)((char*)ws + 8 * (size_t)nitems);
+    s.nf = (int32_t*)((char*)ws + 16 * (size_t)nitems);
+    return s;
+}
+
+// The two sums one thread adds term after term (a tensor's items, the tensors of the buffer) are compensated (Neumaier):
+// some hundred terms in a row would otherwise cost several ulp of the norm.  A step that leaves the finite numbers is not
+// compensated, so that an infinite or NaN sum stays what plain addition gives (no Inf - Inf).
+struct Sum {
+    double s, c;
+};
+
+STEP_HD void sum_add(Sum& a, double x) {
+    const double t = a.s + x;
+    if (fabs(t) <= 1.7976931348623157e308) a.c = a.c + (fabs(a.s) >= fabs(x) ? (a.s - t) + x : (x - t) + a.s);
+    a.s = t;
+}
+
+STEP_HD double sum_value(const Sum& a) { return a.s + a.c; }
+
+// a tensor: its items in item order.  Src gives the partials of item i: the scratch itself (ScratchSource), or the kernel's
+// copy of its head in LDS.
+struct ScratchSource {
+    Scratch w;
+    STEP_HD_MEMBER int near_end(int a, int) const { return a; }      // nothing nearer than the scratch
+    STEP_HD_MEMBER Part near(int i) const { return far(i); }
+    STEP_HD_MEMBER Part far(int i) const {
+        const Part p = {w.sumsq[i], w.hash[i], w.nf[i]};
+        return p;
+    }
+};
+
+// Items [a, near_end) come from the source's near copy and the rest from the scratch: two plain loops, in item order, so
+// that the loads of the near loop (LDS in the kernel) can be issued several iterations ahead of the sum that needs them.
+template <class Src>
+STEP_HD Part tensor_part(const Src& src, int a, int b) {
+    Sum sq = {0.0, 0.0};
+    Part p = {0.0, 0, 0};
+    const int mid = src.near_end(a, b);
+#pragma unroll 8
+    for (int i = a; i < mid; ++i) {
+        const Part q = src.near(i);
+        sum_add(sq, q.sumsq);
+        p.hash += q.hash;
+        p.nf += q.nf;
+    }
+    for (int i = mid; i < b; ++i) {
+        const Part q = src.far(i);
+        sum_add(sq, q.sumsq);
+        p.hash += q.hash;
+        p.nf += q.nf;
+    }
+    p.sumsq = sum_value(sq);
+    return p;
+}
+
+struct Record {
+    X3DStepHeader* head;
+    double* sumsq;
+    uint64_t* hash;
+    int32_t* nf;
+};
+
+STEP_HD size_t record_bytes(int S) { return ((sizeof(X3DStepHeader) + (size_t)S * 20) + 7) & ~(size_t)7; }
+
+STEP_HD Record record_at(void* ring, int R, int S, int64_t step) {
+    const int64_t slot = ((step % (int64_t)R) + R) % R;      // inside the ring whatever the counter holds
+    char* base = (char*)ring + (size_t)slot * record_bytes(S);
+    Record r;
+    r.head = (X3DStepHeader*)base;
+    r.sumsq = (double*)(base + sizeof(X3DStepHeader));
+    r.hash = (uint64_t*)(base + sizeof(X3DStepHeader) + 8 * (size_t)S);
+    r.nf = (int32_t*)(base + sizeof(X3DStepHeader) + 16 * (size_t)S);
+    return r;
+}
+
+// torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped from above at 1 (a NaN stays a NaN)
+STEP_HD float coef_rule(double total, double inv_world, double max_norm, double* norm_out) {
+    const double norm = sqrt(total) * inv_world;
+    *norm_out = norm;
+    if (!(max_norm > 0.0)) return 1.0f;
+    double c = max_norm / (norm + 1e-6);
+    if (c > 1.0) c = 1.0;
+    return (float)c;
+}
+
+// what the one finishing thread writes after the per-tensor part of the record: the header and the state
+STEP_HD void finish_step(const Record& r, int64_t* state, int64_t step, int S, double total, int32_t nf, int32_t first_bad,
+                         double max_norm, double inv_world) {
+    double norm;
+    const float coef = coef_rule(total, inv_world, max_norm, &norm);
+    X3DStepHeader h;
+    h.step = step;
+    h.total = total;
+    h.norm = norm;
+    h.coef = coef;
+    h.nonfinite = nf;
+    h.first_bad = first_bad;
+    h.nseg = S;
+    *r.head = h;
+    if (nf > 0 && state[X3DSTEP_S_BAD_STEP] < 0) {
+        state[X3DSTEP_S_BAD_STEP] = step;
+        state[X3DSTEP_S_BAD_SEG] = first_bad;
+    }
+    int64_t nb;
+    memcpy(&nb, &norm, 8);
+    state[X3DSTEP_S_NORM] = nb;
+    state[X3DSTEP_S_COEF] = (int64_t)float_bits(coef);
+    state[X3DSTEP_S_STEP] = step + 1;
+}
+
+STEP_HD float state_coef(const int64_t* state) {
+    const uint32_t u = (uint32_t)state[X3DSTEP_S_COEF];
+    float c;
+    memcpy(&c, &u, 4);
+    return c;
+}
+
+STEP_HD float scale_one(float x, float coef) { return x * coef; }
+
+}  // namespace x3ds

@@ -1,0 +1,149 @@
+// The host's part of libx3dstep (include/x3dstep.h): error text, sizes, the item-table builder and x3dstep_observe_host,
+// the three launches of step.hip run serially through the same step_core.h.  Plain C++, no HIP call.
+#include <stdarg.h>
+#include <stdio.h>
+
+#include "step_core.h"
+
+static thread_local char g_err[512] = "";
+
+void x3dstep_set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+
+extern "C" const char* x3dstep_last_error(void) { return g_err; }
+extern "C" int x3dstep_abi_version(void) { return X3DSTEP_ABI_VERSION; }
+extern "C" size_t x3dstep_item_bytes(void) { return sizeof(X3DStepItem); }
+extern "C" size_t x3dstep_header_bytes(void) { return sizeof(X3DStepHeader); }
+extern "C" size_t x3dstep_record_bytes(int S) { return S < 1 || S > X3DSTEP_MAX_SEGMENTS ? 0 : x3ds::record_bytes(S); }
+extern "C" size_t x3dstep_workspace_bytes(int64_t nitems) {
+    return nitems < 1 || nitems > X3DSTEP_MAX_ITEMS ? 0 : x3ds::scratch_bytes(nitems);
+}
+
+// counts (items == nullptr) or writes the item table; -1 when the segment table is refused
+static int64_t walk_items(const int64_t* seg_off, int S, X3DStepItem* items, int64_t cap, int32_t* seg_item) {
+    if (!seg_off || S < 1 || S > X3DSTEP_MAX_SEGMENTS || seg_off[0] != 0) return -1;
+    int64_t count = 0;
+    for (int s = 0; s < S; ++s) {
+        const int64_t len = seg_off[s + 1] - seg_off[s];
+        if (len < 1 || len > 0x7fffffff) return -1;
+        if (seg_item) seg_item[s] = (int32_t)count;
+        for (int64_t at = 0; at < len; at += X3DSTEP_ITEM) {
+            if (count >= X3DSTEP_MAX_ITEMS) return -1;
+            if (items) {
+                if (count >= cap) return -1;
+                items[count].start = seg_off[s] + at;
+                items[count].seg = s;
+                items[count].len = (int32_t)(len - at < X3DSTEP_ITEM ? len - at : X3DSTEP_ITEM);
+            }
+            ++count;
+        }
+    }
+    if (seg_item) seg_item[S] = (int32_t)count;
+    return count;
+}
+
+extern "C" int64_t x3dstep_item_count(const int64_t* seg_off, int S) {
+    const int64_t c = walk_items(seg_off, S, nullptr, 0, nullptr);
+    if (c < 0) {
+        x3dstep_set_error("x3dstep_item_count: S %d outside 1 .. %d, seg_off[0] != 0 or a tensor outside 1 .. 2^31 - 1 elements",
+                          S, X3DSTEP_MAX_SEGMENTS);
+        return X3DSTEP_EINVAL;
+    }
+    return c;
+}
+
+extern "C" int64_t x3dstep_build_items(const int64_t* seg_off, int S, X3DStepItem* items, int64_t cap, int32_t* seg_item) {
+    if (!items || !seg_item || cap < 1) {
+        x3dstep_set_error("x3dstep_build_items: null table or no capacity");
+        return X3DSTEP_EINVAL;
+    }
+    const int64_t c = walk_items(seg_off, S, items, cap, seg_item);
+    if (c < 0) {
+        x3dstep_set_error("x3dstep_build_items: the segment table is refused (see x3dstep_item_count) or needs more than "
+                          "%lld items", (long long)cap);
+        return X3DSTEP_EINVAL;
+    }
+    return c;
+}
+
+// the argument checks x3dstep_observe and its twin share (step.hip calls it too)
+int x3dstep_check_observe(const char* who, const float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                          const int32_t* seg_item, int64_t nitems, const void* workspace, const int64_t* state,
+                          const void* ring, int R) {
+    if (!g || !seg_off || !items || !seg_item || !workspace || !state || !ring || n < 1 || S < 1 ||
+        S > X3DSTEP_MAX_SEGMENTS || nitems < S || nitems > X3DSTEP_MAX_ITEMS || R < 1 || ((uintptr_t)g & 3) != 0 ||
+        (((uintptr_t)seg_off | (uintptr_t)items | (uintptr_t)workspace | (uintptr_t)state | (uintptr_t)ring) & 7) != 0 ||
+        ((uintptr_t)seg_item & 3) != 0) {
+        x3dstep_set_error("%s: null or unaligned pointer, n %lld < 1, S %d outside 1 .. %d, nitems %lld outside S .. %d or "
+                          "R %d < 1", who, (long long)n, S, X3DSTEP_MAX_SEGMENTS, (long long)nitems, X3DSTEP_MAX_ITEMS, R);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                                    const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring,
+                                    int R, double max_norm, double inv_world) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_observe("x3dstep_observe_host", g, n, seg_off, S, items, seg_item, nitems, workspace, state,
+                                         ring, R);
+    if (rc) return rc;
+    // the tables are host memory here: refuse what would read or write outside g, the scratch or the record
+    if (seg_off[0] != 0 || seg_off[S] != n || seg_item[0] != 0 || seg_item[S] != nitems) {
+        x3dstep_set_error("x3dstep_observe_host: the tables do not cover n %lld elements and %lld items", (long long)n,
+                          (long long)nitems);
+        return X3DSTEP_EINVAL;
+    }
+    for (int s = 0; s < S; ++s) {
+        bool ok = seg_off[s + 1] > seg_off[s] && seg_item[s + 1] > seg_item[s];
+        int64_t at = seg_off[s];
+        for (int i = seg_item[s]; ok && i < seg_item[s + 1]; ++i) {
+            ok = items[i].seg == s && items[i].start == at && items[i].len >= 1 && items[i].len <= X3DSTEP_ITEM;
+            at += items[i].len;
+        }
+        if (!ok || at != seg_off[s + 1]) {
+            x3dstep_set_error("x3dstep_observe_host: the items of tensor %d do not cover it", s);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    // launch 1
+    const Scratch w = scratch_at(workspace, nitems);
+    const bool vec = ((uintptr_t)g & 15) == 0;
+    for (int64_t i = 0; i < nitems; ++i) {
+        const X3DStepItem it = items[i];
+        const uint64_t first = (uint64_t)(it.start - seg_off[it.seg]);
+        Part lanes[kLanes];
+        for (int l = 0; l < kLanes; ++l) lanes[l] = lane_part(g, it.start, it.len, first, l, vec);
+        for (int off = kLanes / 2; off > 0; off >>= 1)
+            for (int l = 0; l < off; ++l) part_merge(lanes[l], lanes[l + off]);
+        w.sumsq[i] = lanes[0].sumsq;
+        w.hash[i] = lanes[0].hash;
+        w.nf[i] = lanes[0].nf;
+    }
+    // launch 2
+    const int64_t step = state[X3DSTEP_S_STEP];
+    const Record r = record_at(ring, R, S, step);
+    Sum total = {0.0, 0.0};
+    int32_t nf = 0, first_bad = -1;
+    for (int s = 0; s < S; ++s) {
+        const Part p = tensor_part(ScratchSource{w}, seg_item[s], seg_item[s + 1]);
+        r.sumsq[s] = p.sumsq;
+        r.hash[s] = p.hash;
+        r.nf[s] = p.nf;
+        sum_add(total, p.sumsq);
+        nf += p.nf;
+        if (first_bad < 0 && p.nf > 0) first_bad = s;
+    }
+    finish_step(r, state, step, S, sum_value(total), nf, first_bad, max_norm, inv_world);
+    // launch 3
+    if (max_norm > 0.0) {
+        const float coef = state_coef(state);
+        if (coef != 1.0f)
+            for (int64_t i = 0; i < n; ++i) g[i] = scale_one(g[i], coef);
+    }
+    return X3DSTEP_OK;
+}

@@ -201,7 +201,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
-        frames_root=None, val_frames=None):
+        frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -213,7 +213,10 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     sharded over the ranks and scored by `validate_topk` (top-1, top-5 and the loss, reduced over the ranks).
     num_steps_per_update: gradient accumulation over that many micro-batches per optimizer step (train...:119,267-273;
     the schedule then counts iterations and lr_schedule is divided by it, :130).  clip_size overrides the crop size of
-    the shape table (tests: the default batch arithmetic at a tiny resolution)."""
+    the shape table (tests: the default batch arithmetic at a tiny resolution).
+    clip_grad_norm / monitor: Trainer(clip_grad_norm=, monitor=) -- clip the global gradient norm; record per-tensor
+    gradient statistics in a device ring (True or the ring's size).  With either, the log line gains `gnorm` and `clip`, and
+    rank 0 reports the first non-finite gradient (step, parameter) when the run ends, also when it ends in an exception."""
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -261,7 +264,9 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
 
     lr = init_lr
     optimizer = Trainer(model, lr=lr, momentum=0.9, weight_decay=5e-5, process_group=pg, world_size=world,
-                        use_graph=use_graph, num_steps_per_update=num_steps_per_update)
+                        use_graph=use_graph, num_steps_per_update=num_steps_per_update, clip_grad_norm=clip_grad_norm,
+                        monitor=monitor)
+    mon = getattr(optimizer, 'monitor', None)
     lr_sched = MultiStepLR(optimizer, lr_schedule)
     if ck is not None:
         optimizer.load_state_dict(ck['optimizer_state_dict'])
@@ -359,10 +364,13 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                 tot_loss = float(loss)
                 preds = logits.argmax(1)
                 acc = float((preds == labels).float().mean())
+                gline = '' if mon is None else ' gnorm {:.4e} clip {:.4f}'.format(float(mon.last_norm()),
+                                                                                  float(mon.last_coef()))
                 if rank == 0:
                     dt = time.time() - t0
-                    print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s'.format(
-                        steps, long_ind, B, T, H, tot_loss, acc, optimizer.param_groups[0]['lr'], clips / dt), flush=True)
+                    print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s{}'.format(
+                        steps, long_ind, B, T, H, tot_loss, acc, optimizer.param_groups[0]['lr'], clips / dt, gline),
+                        flush=True)
             if val_every and done % val_every == 0 and val_ds is not None:
                 res = validate_topk(model, val_ds.batches(val_batch_size, rank, world), process_group=pg)
                 model.train(True)                                   # train...:199-200
@@ -386,6 +394,9 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     finally:
         # runs on errors too: a rank that raised must not leave the others waiting inside a collective
         torch.cuda.synchronize()
+        bad = mon.first_nonfinite() if (mon is not None and rank == 0) else None
+        if bad is not None:
+            print(' first non-finite gradient: step {} parameter {}'.format(*bad), flush=True)
         if world > 1:
             import torch.distributed as dist
             dist.destroy_process_group()
@@ -433,6 +444,11 @@ if __name__ == '__main__':
                              'bits of scan, and Huffman decode through it in one pass (x3djpeg_entropy_decode_indexed); no '
                              'value: the library\'s default.  A pack with its index beside it (PACK.idx) is used indexed '
                              'without this')
+    parser.add_argument('--clip-grad-norm', type=float, default=None,
+                        help='clip the global gradient norm to this value before every update (off by default)')
+    parser.add_argument('--monitor', type=int, nargs='?', const=64, default=None, metavar='RING',
+                        help='record per-tensor gradient statistics of the last RING updates on the GPU (default 64); the log '
+                             'line gains gnorm and clip, and the first non-finite gradient is reported at the end')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -459,4 +475,5 @@ if __name__ == '__main__':
         iterations_per_epoch=args.iters_per_epoch, load_ckpt=args.load, save_every=args.save_every,
         use_graph=not args.no_graph, x3d_version=args.version,
         act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root, val_every=args.val_every,
-        val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames)
+        val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames,
+        clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False)

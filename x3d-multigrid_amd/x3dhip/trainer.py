@@ -120,7 +120,7 @@ class Trainer:
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
-                 objective="ce"):
+                 objective="ce", clip_grad_norm=None, monitor=False):
         """overlap: multi-rank steps are captured as two graphs around the first gradient bucket (False: single graph,
         all-reduce after the whole backward); force_split: the two-graph form on a single rank too (tests);
         force_collectives: all-reduce on a one-rank process group (the single-GPU RCCL test).  Round 4: constructor
@@ -134,6 +134,13 @@ class Trainer:
                  labels float [B, n_classes, TL] at any TL (train_x3d_charades_loc.py:168-189); `last_losses` holds
                  (cls_loss, loc_loss) of the latest step as device tensors.
         The loss returned by train_step is the micro-batch objective; num_steps_per_update divides the gradient only.
+
+        clip_grad_norm / monitor: either creates a gradmonitor.GradMonitor (`self.monitor`) that records per-tensor
+        statistics of the gradient every update, after the all-reduce and `pre_step` and right before the SGD kernel, and,
+        with clip_grad_norm = c, scales the gradient by min(1, c / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; the norm
+        is that of the all-reduced gradient / world, so every rank computes the same coefficient).  monitor: True (a ring of
+        64 records) or the ring's size.  Both off (the default): no attribute, not one extra launch.  The ring is
+        diagnostics, not optimizer state: state_dict() is the same either way.
 
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
@@ -167,6 +174,11 @@ class Trainer:
         model._direct_grads = True      # engine writes parameter gradients straight into fp.grad
         self.reducer = GradReducer(self.fp.grad, self.fp.head_first_buckets(model), world_size, process_group,
                                    force_collectives=force_collectives)
+        if clip_grad_norm is not None or monitor:
+            from .gradmonitor import GradMonitor
+            ring = 64 if (monitor is True or not monitor) else int(monitor)
+            self.monitor = GradMonitor(self.fp, [k for k, _ in model.named_parameters()], ring=ring,
+                                       max_norm=clip_grad_norm, inv_world=1.0 / world_size)
 
     @property
     def lr(self):
@@ -261,6 +273,9 @@ class Trainer:
         self.reducer.reduce()
 
     def _sgd(self, grad=None):
+        mon = getattr(self, "monitor", None)
+        if mon is not None:                  # statistics (and clipping) of exactly what the SGD kernel is about to apply
+            mon.observe(grad)
         g = self.param_groups[0]
         ops.sgd_fused(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, g['lr'], g['momentum'],
                       g['weight_decay'], 1.0 / self.world, first=self.first)
