@@ -46,6 +46,10 @@
  *   [X3DSTEP_S_BAD_SEG]   sticky: the lowest tensor with a non-finite element at that step, -1 likewise
  *   [X3DSTEP_S_NORM]      the bits of the fp64 norm of the latest step
  *   [X3DSTEP_S_COEF]      low 32 bits: the bits of the fp32 coefficient of the latest step (launch 3 reads it here)
+ *   [X3DSTEP_S_SKIP]      1 if the latest x3dstep_apply left the parameters alone, else 0 (x3dstep_keep reads it)
+ *   [X3DSTEP_S_SKIPPED]   updates x3dstep_apply skipped so far
+ *   [X3DSTEP_S_RUN]       updates skipped in a row; an applied update sets it to 0
+ * x3dstep_observe / x3dstep_measure never touch the last three words; only x3dstep_apply writes them.
  */
 #ifndef X3DSTEP_H
 #define X3DSTEP_H
@@ -73,7 +77,13 @@ extern "C" {
 #define X3DSTEP_S_BAD_SEG 2
 #define X3DSTEP_S_NORM 3
 #define X3DSTEP_S_COEF 4
+#define X3DSTEP_S_SKIP 5
+#define X3DSTEP_S_SKIPPED 6
+#define X3DSTEP_S_RUN 7
 #define X3DSTEP_STATE_WORDS 8
+
+#define X3DSTEP_KEEP_SAVE 0
+#define X3DSTEP_KEEP_RESTORE 1
 
 #define X3DSTEP_MAX_SEGMENTS (1 << 20)
 #define X3DSTEP_MAX_ITEMS 0x7fffff00
@@ -94,9 +104,18 @@ typedef struct {
     int32_t nseg;       /* S */
 } X3DStepHeader;
 
+/* One small buffer x3dstep_keep saves and restores (24 bytes). */
+typedef struct {
+    int64_t addr;    /* the live buffer: the address of fp32 [len], 4-byte aligned, not null */
+    int64_t offset;  /* its first element in snap */
+    int32_t len;     /* elements, >= 1 */
+    int32_t pad;
+} X3DStepKeep;
+
 int x3dstep_abi_version(void);
 const char* x3dstep_last_error(void);
 size_t x3dstep_item_bytes(void);
+size_t x3dstep_keep_bytes(void);
 size_t x3dstep_header_bytes(void);
 size_t x3dstep_record_bytes(int S);
 
@@ -125,6 +144,56 @@ int x3dstep_observe(float* g, int64_t n, const int64_t* seg_off, int S, const X3
 int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
                          const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring, int R,
                          double max_norm, double inv_world);
+
+/*
+ * Launches 1 and 2 of x3dstep_observe with the same arguments: the record, the norm and the coefficient for max_norm are
+ * written as x3dstep_observe writes them, and launch 3 is never issued: g is only read.  x3dstep_observe is x3dstep_measure
+ * followed by the scale launch.
+ */
+int x3dstep_measure(const float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                    const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring, int R,
+                    double max_norm, double inv_world, void* stream);
+int x3dstep_measure_host(const float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                         const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring, int R,
+                         double max_norm, double inv_world);
+
+/*
+ * The guarded update: one launch in place of launch 3 and the SGD kernel of libx3dhip.so, after x3dstep_measure on the
+ * same state and ring (R records of S tensors).  Every thread reads state[X3DSTEP_S_STEP] = c, the `nonfinite` field of the
+ * header in slot (c - 1) mod R and the coefficient word.  When nonfinite > 0 the whole grid leaves without a store to w, g
+ * or m.  Otherwise, per element, in fp32 with every operation rounded once (no contraction):
+ *     gi = coef == 1.0f ? g[i] : g[i] * coef          (the multiply of launch 3)
+ *     t  = gi * grad_scale;  gi' = fmaf(weight_decay, w[i], t)
+ *     m' = first ? gi' : fmaf(momentum, m[i], gi');   w' = w[i] - lr * m'
+ * which is the SGD kernel's arithmetic on the gradient launch 3 would have left.  g is NOT written: the scaled gradient
+ * exists in registers only, and g holds the unscaled gradient afterwards.
+ * Thread 0 of workgroup 0 then writes state[X3DSTEP_S_SKIP], [X3DSTEP_S_SKIPPED] and [X3DSTEP_S_RUN]; no other thread reads them.
+ *   w, g, m fp32 [n], distinct, 4-byte aligned; 16-byte accesses when the three addresses are congruent mod 16 (head and
+ *   tail element by element), element accesses otherwise.  No atomics, no allocation, no synchronisation: capturable.
+ * A state whose counter is 0 (nothing measured): x3dstep_apply_host refuses it; the kernel, which alone can read the device's
+ * counter, leaves without any store, the three words included.
+ */
+int x3dstep_apply(float* w, const float* g, float* m, int64_t n, int64_t* state, const void* ring, int R, int S, float lr,
+                  float momentum, float weight_decay, float grad_scale, int first, void* stream);
+int x3dstep_apply_host(float* w, const float* g, float* m, int64_t n, int64_t* state, const void* ring, int R, int S, float lr,
+                       float momentum, float weight_decay, float grad_scale, int first);
+
+/*
+ * Saves and restores small buffers that a forward pass overwrites (the running statistics of batch normalisation).
+ *   table  X3DStepKeep [nbuf]: the live buffers and where each lies in snap (fp32 [snap_n]); the ranges do not overlap
+ *   items  the item table x3dstep_build_items gives for a segment table of snap (tensor s is buffer s; a tensor may be
+ *          longer than table[s].len, e.g. padded to a multiple of four elements: what lies past len is left alone)
+ *   mode   X3DSTEP_KEEP_SAVE: snap <- live, always.  X3DSTEP_KEEP_RESTORE: live <- snap when state[X3DSTEP_S_SKIP] == 1,
+ *          and otherwise every workgroup leaves at once.
+ * One launch, one wave per item, every element stored once; 16-byte accesses where both addresses of an item allow.
+ * x3dstep_keep_host refuses a table with a null or unaligned address, a range outside snap or an item outside its buffer's
+ * range; the kernel cannot be refused for the contents of device memory and makes the same tests per item: an item that
+ * fails them is not copied.
+ */
+int x3dstep_keep(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap, int64_t snap_n,
+                 const int64_t* state, int mode, void* stream);
+int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
+                      int64_t snap_n, const int64_t* state, int mode);
 
 #ifdef __cplusplus
 }

@@ -196,7 +196,8 @@ def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
 
 def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
-        device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False):
+        device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
+        skip_nonfinite=False, max_skip_run=8):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -206,7 +207,10 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     module docstring; batch_size is the GLOBAL batch and must be a multiple of world).  base_bn_splits: the BatchNorm
     splits of a training batch (a single process with `world` splits normalises as `world` ranks do).
     clip_grad_norm / monitor: Trainer(clip_grad_norm=, monitor=); with either, the training log line gains `gnorm` and
-    `clip` (of the latest update) and rank 0 reports the first non-finite gradient when the run ends, also on an exception."""
+    `clip` (of the latest update) and rank 0 reports the first non-finite gradient when the run ends, also on an exception.
+    skip_nonfinite / max_skip_run: Trainer(skip_nonfinite=True) drops an update whose gradient has a NaN or an Inf; the log
+    line gains `skipped N`, and when max_skip_run updates in a row were skipped the run stops with
+    gradmonitor.SkippedRunError, which names the first non-finite gradient (checked where the losses are read)."""
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
     ddp = process_group is not None and world > 1
@@ -255,7 +259,7 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     say('INIT LR: %f' % lr)
     optimizer = Trainer(x3d, lr=lr, momentum=0.9, weight_decay=1e-5, objective='loc' if loc else 'bce',
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update,
-                        clip_grad_norm=clip_grad_norm, monitor=monitor,
+                        clip_grad_norm=clip_grad_norm, monitor=monitor, skip_nonfinite=skip_nonfinite,
                         **(dict(process_group=process_group, world_size=world) if ddp else {}))
     mon = getattr(optimizer, 'monitor', None)
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
@@ -310,6 +314,8 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                             n = s_times * num_steps_per_update
                             gline = '' if mon is None else ' gnorm {:.4e} clip {:.4f}'.format(float(mon.last_norm()),
                                                                                               float(mon.last_coef()))
+                            if skip_nonfinite:
+                                gline += ' skipped {}'.format(mon.skip_report(max_skip_run))
                             if loc:
                                 say(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}{}'
                                       .format(epochs, phase, steps, float(tot_loc_loss) / n, float(tot_cls_loss) / n,

@@ -214,4 +214,117 @@ STEP_HD float state_coef(const int64_t* state) {
 
 STEP_HD float scale_one(float x, float coef) { return x * coef; }
 
+// -- the guarded update (x3dstep_apply) ------------------------------------------------------------------------------------
+struct ApplyArgs {
+    float lr, mu, wd, gs;
+    int first;
+};
+
+// What every thread of the apply kernel reads before anything else: the decision and the coefficient of the step measured
+// last.  go: the counter is not 0 (something was measured); skip: that step's gradient had a non-finite element.
+struct Decision {
+    bool go, skip;
+    float coef;
+};
+
+STEP_HD Decision apply_decision(const int64_t* state, const void* ring, int R, int S) {
+    Decision d;
+    const int64_t step = state[X3DSTEP_S_STEP];
+    d.go = step != 0;
+    d.skip = record_at((void*)ring, R, S, step - 1).head->nonfinite > 0;
+    d.coef = state_coef(state);
+    return d;
+}
+
+// one element: the multiply of the scale launch, then the arithmetic of the SGD kernel of libx3dhip.so (csrc/bn.hip
+// sgd_kernel), each operation rounded once (both libraries compile with -ffp-contract=off)
+STEP_HD void apply_one(float& w, float g, float& m, float coef, const ApplyArgs& a) {
+    const float gi = coef == 1.0f ? g : scale_one(g, coef);
+    const float t = gi * a.gs;
+    const float gg = fmaf(a.wd, w, t);
+    const float mi = a.first ? gg : fmaf(a.mu, m, gg);
+    const float step = a.lr * mi;
+    m = mi;
+    w = w - step;
+}
+
+// what the one counting thread writes
+STEP_HD void apply_counters(int64_t* state, bool skip) {
+    state[X3DSTEP_S_SKIP] = skip ? 1 : 0;
+    if (skip) {
+        state[X3DSTEP_S_SKIPPED] = state[X3DSTEP_S_SKIPPED] + 1;
+        state[X3DSTEP_S_RUN] = state[X3DSTEP_S_RUN] + 1;
+    } else {
+        state[X3DSTEP_S_RUN] = 0;
+    }
+}
+
+// How the flat buffers are walked: `head` elements one by one, `groups` 16-byte groups, then the tail, when the three
+// addresses are congruent mod 16; otherwise n elements one by one (groups = 0, head = n is never used: vec says which).
+struct ApplyPlan {
+    bool vec;
+    int64_t head, groups, tail;      // tail: the index of the first element after the groups
+};
+
+STEP_HD ApplyPlan apply_plan(const void* w, const void* g, const void* m, int64_t n) {
+    ApplyPlan p;
+    const uintptr_t a = (uintptr_t)w & 15;
+    p.vec = a == ((uintptr_t)g & 15) && a == ((uintptr_t)m & 15);
+    p.head = (int64_t)(((16 - a) & 15) >> 2);
+    if (p.head > n) p.head = n;
+    p.groups = (n - p.head) >> 2;
+    p.tail = p.head + 4 * p.groups;
+    return p;
+}
+
+// -- the kept buffers (x3dstep_keep) ---------------------------------------------------------------------------------------
+constexpr int kKeepPieces = X3DSTEP_ITEM / (4 * kLanes);      // 16-byte groups of a full item per lane: 8
+
+struct KeepCopy {
+    float* dst;
+    const float* src;
+    int len;                         // 0: the item is refused or lies past its buffer's end, nothing is copied
+};
+
+// Item i resolved against the table: both ends of the copy, or len 0.  The tests are those x3dstep_keep_host refuses a
+// call for; the kernel makes them per item, since the table it reads is device memory nobody has checked.
+STEP_HD KeepCopy keep_resolve(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t i, float* snap,
+                              int64_t snap_n, int mode, bool* bad) {
+    KeepCopy c = {nullptr, nullptr, 0};
+    const X3DStepItem it = items[i];
+    *bad = true;
+    if (it.seg < 0 || it.seg >= nbuf || it.len < 1 || it.len > X3DSTEP_ITEM || it.start < 0 || it.start > snap_n - it.len)
+        return c;
+    const X3DStepKeep b = table[it.seg];
+    const int64_t rel = it.start - b.offset;
+    if (b.addr == 0 || (b.addr & 3) != 0 || b.len < 1 || b.offset < 0 || b.offset > snap_n - b.len || rel < 0) return c;
+    *bad = false;
+    const int64_t left = (int64_t)b.len - rel;               // elements of the buffer from this item's start on
+    if (left < 1) return c;                                  // padding past the buffer's end
+    float* live = (float*)(uintptr_t)b.addr + rel;
+    c.len = left < it.len ? (int)left : it.len;
+    c.dst = mode == X3DSTEP_KEEP_SAVE ? snap + it.start : live;
+    c.src = mode == X3DSTEP_KEEP_SAVE ? live : snap + it.start;
+    return c;
+}
+
+// What lane `lane` of the item's wave copies: the 16-byte groups q = lane, lane + 64, .. when both addresses are 16-byte
+// aligned (all loads before the first store), the elements j = lane, lane + 64, .. otherwise and for the last len mod 4.
+STEP_HD void keep_lane(const KeepCopy& c, int lane) {
+    const bool vec = (((uintptr_t)c.dst | (uintptr_t)c.src) & 15) == 0;
+    const int groups = vec ? c.len >> 2 : 0;
+    Vec4 v[kKeepPieces];
+#pragma unroll
+    for (int k = 0; k < kKeepPieces; ++k) {
+        const int q = lane + k * kLanes;
+        if (q < groups) v[k] = ((const Vec4*)c.src)[q];
+    }
+#pragma unroll
+    for (int k = 0; k < kKeepPieces; ++k) {
+        const int q = lane + k * kLanes;
+        if (q < groups) ((Vec4*)c.dst)[q] = v[k];
+    }
+    for (int j = 4 * groups + lane; j < c.len; j += kLanes) c.dst[j] = c.src[j];
+}
+
 }  // namespace x3ds

@@ -1,5 +1,5 @@
-// The host's part of libx3dstep (include/x3dstep.h): error text, sizes, the item-table builder and x3dstep_observe_host,
-// the three launches of step.hip run serially through the same step_core.h.  Plain C++, no HIP call.
+// The host's part of libx3dstep (include/x3dstep.h): error text, sizes, the item-table builder and the *_host twins: the
+// launches of step.hip run serially through the same step_core.h.  Plain C++, no HIP call.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -85,17 +85,16 @@ int x3dstep_check_observe(const char* who, const float* g, int64_t n, const int6
     return X3DSTEP_OK;
 }
 
-extern "C" int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
-                                    const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring,
-                                    int R, double max_norm, double inv_world) {
+// launches 1 and 2 on the host: what x3dstep_measure_host and x3dstep_observe_host share
+static int measure_host(const char* who, const float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                        const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring, int R,
+                        double max_norm, double inv_world) {
     using namespace x3ds;
-    const int rc = x3dstep_check_observe("x3dstep_observe_host", g, n, seg_off, S, items, seg_item, nitems, workspace, state,
-                                         ring, R);
+    const int rc = x3dstep_check_observe(who, g, n, seg_off, S, items, seg_item, nitems, workspace, state, ring, R);
     if (rc) return rc;
     // the tables are host memory here: refuse what would read or write outside g, the scratch or the record
     if (seg_off[0] != 0 || seg_off[S] != n || seg_item[0] != 0 || seg_item[S] != nitems) {
-        x3dstep_set_error("x3dstep_observe_host: the tables do not cover n %lld elements and %lld items", (long long)n,
-                          (long long)nitems);
+        x3dstep_set_error("%s: the tables do not cover n %lld elements and %lld items", who, (long long)n, (long long)nitems);
         return X3DSTEP_EINVAL;
     }
     for (int s = 0; s < S; ++s) {
@@ -106,7 +105,7 @@ extern "C" int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off,
             at += items[i].len;
         }
         if (!ok || at != seg_off[s + 1]) {
-            x3dstep_set_error("x3dstep_observe_host: the items of tensor %d do not cover it", s);
+            x3dstep_set_error("%s: the items of tensor %d do not cover it", who, s);
             return X3DSTEP_EINVAL;
         }
     }
@@ -139,11 +138,121 @@ extern "C" int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off,
         if (first_bad < 0 && p.nf > 0) first_bad = s;
     }
     finish_step(r, state, step, S, sum_value(total), nf, first_bad, max_norm, inv_world);
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_measure_host(const float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                                    const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring,
+                                    int R, double max_norm, double inv_world) {
+    return measure_host("x3dstep_measure_host", g, n, seg_off, S, items, seg_item, nitems, workspace, state, ring, R, max_norm,
+                        inv_world);
+}
+
+extern "C" int x3dstep_observe_host(float* g, int64_t n, const int64_t* seg_off, int S, const X3DStepItem* items,
+                                    const int32_t* seg_item, int64_t nitems, void* workspace, int64_t* state, void* ring,
+                                    int R, double max_norm, double inv_world) {
+    using namespace x3ds;
+    const int rc = measure_host("x3dstep_observe_host", g, n, seg_off, S, items, seg_item, nitems, workspace, state, ring, R,
+                                max_norm, inv_world);
+    if (rc) return rc;
     // launch 3
     if (max_norm > 0.0) {
         const float coef = state_coef(state);
         if (coef != 1.0f)
             for (int64_t i = 0; i < n; ++i) g[i] = scale_one(g[i], coef);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" size_t x3dstep_keep_bytes(void) { return sizeof(X3DStepKeep); }
+
+// the argument checks x3dstep_apply and its twin share (no pointer is followed)
+int x3dstep_check_apply(const char* who, const float* w, const float* g, const float* m, int64_t n, const int64_t* state,
+                        const void* ring, int R, int S) {
+    if (!w || !g || !m || !state || !ring || n < 1 || n > ((int64_t)1 << 40) || R < 1 || S < 1 || S > X3DSTEP_MAX_SEGMENTS ||
+        (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m) & 3) != 0 || (((uintptr_t)state | (uintptr_t)ring) & 7) != 0 ||
+        w == g || w == m || g == m) {
+        x3dstep_set_error("%s: null, unaligned or repeated pointer, n %lld outside 1 .. 2^40, R %d < 1 or S %d outside 1 .. %d",
+                          who, (long long)n, R, S, X3DSTEP_MAX_SEGMENTS);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_apply_host(float* w, const float* g, float* m, int64_t n, int64_t* state, const void* ring, int R, int S,
+                                  float lr, float momentum, float weight_decay, float grad_scale, int first) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_apply("x3dstep_apply_host", w, g, m, n, state, ring, R, S);
+    if (rc) return rc;
+    const Decision d = apply_decision(state, ring, R, S);
+    if (!d.go) {
+        x3dstep_set_error("x3dstep_apply_host: the state's step counter is 0: nothing has been measured");
+        return X3DSTEP_EINVAL;
+    }
+    apply_counters(state, d.skip);
+    if (d.skip) return X3DSTEP_OK;
+    const ApplyArgs a = {lr, momentum, weight_decay, grad_scale, first ? 1 : 0};
+    // the kernel's walk: the plan decides which element goes through a 16-byte group; the arithmetic is per element
+    const ApplyPlan plan = apply_plan(w, g, m, n);
+    if (plan.vec) {
+        for (int64_t i = 0; i < plan.head; ++i) apply_one(w[i], g[i], m[i], d.coef, a);
+        for (int64_t q = 0; q < plan.groups; ++q) {
+            Vec4 wv = *(Vec4*)(w + plan.head + 4 * q), mv = *(Vec4*)(m + plan.head + 4 * q);
+            const Vec4 gv = *(const Vec4*)(g + plan.head + 4 * q);
+            for (int e = 0; e < 4; ++e) apply_one(wv.v[e], gv.v[e], mv.v[e], d.coef, a);
+            *(Vec4*)(m + plan.head + 4 * q) = mv;
+            *(Vec4*)(w + plan.head + 4 * q) = wv;
+        }
+        for (int64_t i = plan.tail; i < n; ++i) apply_one(w[i], g[i], m[i], d.coef, a);
+    } else {
+        for (int64_t i = 0; i < n; ++i) apply_one(w[i], g[i], m[i], d.coef, a);
+    }
+    return X3DSTEP_OK;
+}
+
+// the argument checks x3dstep_keep and its twin share (no pointer is followed: the tables may be device memory)
+int x3dstep_check_keep(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
+                       const float* snap, int64_t snap_n, const int64_t* state, int mode) {
+    if (!table || !items || !snap || !state || nbuf < 1 || nbuf > X3DSTEP_MAX_SEGMENTS || nitems < nbuf ||
+        nitems > X3DSTEP_MAX_ITEMS || snap_n < 1 || (mode != X3DSTEP_KEEP_SAVE && mode != X3DSTEP_KEEP_RESTORE) ||
+        (((uintptr_t)table | (uintptr_t)items | (uintptr_t)state) & 7) != 0 || ((uintptr_t)snap & 3) != 0) {
+        x3dstep_set_error("%s: null or unaligned pointer, nbuf %d outside 1 .. %d, nitems %lld outside nbuf .. %d, snap_n %lld "
+                          "< 1 or mode %d", who, nbuf, X3DSTEP_MAX_SEGMENTS, (long long)nitems, X3DSTEP_MAX_ITEMS,
+                          (long long)snap_n, mode);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
+                                 int64_t snap_n, const int64_t* state, int mode) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_keep("x3dstep_keep_host", table, nbuf, items, nitems, snap, snap_n, state, mode);
+    if (rc) return rc;
+    // the tables are host memory here: refuse the call for what the kernel would leave out item by item
+    for (int b = 0; b < nbuf; ++b) {
+        const X3DStepKeep k = table[b];
+        if (k.addr == 0 || (k.addr & 3) != 0 || k.len < 1 || k.offset < 0 || k.offset > snap_n - k.len ||
+            (b > 0 && k.offset < table[b - 1].offset + table[b - 1].len)) {
+            x3dstep_set_error("x3dstep_keep_host: buffer %d: a null or unaligned address, or a range outside snap or over the "
+                              "buffer before it", b);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    for (int64_t i = 0; i < nitems; ++i) {
+        bool bad;
+        (void)keep_resolve(table, nbuf, items, i, snap, snap_n, mode, &bad);
+        if (bad) {
+            x3dstep_set_error("x3dstep_keep_host: item %lld lies outside snap or outside its buffer's range", (long long)i);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    if (mode == X3DSTEP_KEEP_RESTORE && state[X3DSTEP_S_SKIP] != 1) return X3DSTEP_OK;
+    for (int64_t i = 0; i < nitems; ++i) {
+        bool bad;
+        const KeepCopy c = keep_resolve(table, nbuf, items, i, snap, snap_n, mode, &bad);
+        if (c.len > 0)
+            for (int l = 0; l < kLanes; ++l) keep_lane(c, l);
     }
     return X3DSTEP_OK;
 }

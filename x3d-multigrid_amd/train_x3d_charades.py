@@ -39,7 +39,8 @@ SAVE_MODEL = 'models/x3d_charades_rgb_sgd_'
 def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_UPSCALE, videos=None,
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
-        process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False):
+        process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
+        skip_nonfinite=False, max_skip_run=8):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
     every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
@@ -54,7 +55,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               load_ckpt=load_ckpt, resume=resume, save_every=save_every, use_graph=use_graph,
                               num_steps_per_update=num_steps_per_update, crop_size=crop_size, c_size=c_size,
                               dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
-                              world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor)
+                              world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor,
+                              skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run)
 
 
 def init_distributed():
@@ -108,6 +110,11 @@ def main(run_fn, default_save):
     parser.add_argument('--monitor', type=int, nargs='?', const=64, default=None, metavar='RING',
                         help='record per-tensor gradient statistics of the last RING updates on the GPU (default 64); the log '
                              'line gains gnorm and clip, and the first non-finite gradient is reported at the end')
+    parser.add_argument('--skip-nonfinite', action='store_true',
+                        help='drop an update whose gradient has a NaN or an Inf (decided on the GPU; implies --monitor); the '
+                             'log line gains skipped')
+    parser.add_argument('--max-skip-run', type=int, default=8, metavar='K',
+                        help='with --skip-nonfinite: stop when K updates in a row were skipped (default 8)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -123,7 +130,8 @@ def main(run_fn, default_save):
         run_fn(max_epochs=args.epochs, anno=args.anno, batch_size=args.batch, x3d_version=args.version,
                load_ckpt=args.load, resume=args.resume, save_model=args.save, save_every=args.save_every,
                use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,
-               rank=rank, world=world, clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, **size)
+               rank=rank, world=world, clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False,
+               skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, **size)
     finally:
         if pg is not None:
             import torch.distributed as dist

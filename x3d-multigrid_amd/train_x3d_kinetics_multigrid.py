@@ -201,7 +201,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
-        frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False):
+        frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -216,7 +216,10 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     the shape table (tests: the default batch arithmetic at a tiny resolution).
     clip_grad_norm / monitor: Trainer(clip_grad_norm=, monitor=) -- clip the global gradient norm; record per-tensor
     gradient statistics in a device ring (True or the ring's size).  With either, the log line gains `gnorm` and `clip`, and
-    rank 0 reports the first non-finite gradient (step, parameter) when the run ends, also when it ends in an exception."""
+    rank 0 reports the first non-finite gradient (step, parameter) when the run ends, also when it ends in an exception.
+    skip_nonfinite: Trainer(skip_nonfinite=True) -- an update whose gradient has a NaN or an Inf is dropped on the GPU; the
+    log line gains `skipped N`, and when max_skip_run updates in a row were skipped the run stops with
+    gradmonitor.SkippedRunError, which names the first non-finite gradient (checked where the loss is read)."""
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -265,7 +268,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     lr = init_lr
     optimizer = Trainer(model, lr=lr, momentum=0.9, weight_decay=5e-5, process_group=pg, world_size=world,
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update, clip_grad_norm=clip_grad_norm,
-                        monitor=monitor)
+                        monitor=monitor, skip_nonfinite=skip_nonfinite)
     mon = getattr(optimizer, 'monitor', None)
     lr_sched = MultiStepLR(optimizer, lr_schedule)
     if ck is not None:
@@ -366,6 +369,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                 acc = float((preds == labels).float().mean())
                 gline = '' if mon is None else ' gnorm {:.4e} clip {:.4f}'.format(float(mon.last_norm()),
                                                                                   float(mon.last_coef()))
+                if skip_nonfinite:
+                    gline += ' skipped {}'.format(mon.skip_report(max_skip_run))
                 if rank == 0:
                     dt = time.time() - t0
                     print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s{}'.format(
@@ -449,6 +454,11 @@ if __name__ == '__main__':
     parser.add_argument('--monitor', type=int, nargs='?', const=64, default=None, metavar='RING',
                         help='record per-tensor gradient statistics of the last RING updates on the GPU (default 64); the log '
                              'line gains gnorm and clip, and the first non-finite gradient is reported at the end')
+    parser.add_argument('--skip-nonfinite', action='store_true',
+                        help='drop an update whose gradient has a NaN or an Inf (decided on the GPU; implies --monitor); the '
+                             'log line gains skipped')
+    parser.add_argument('--max-skip-run', type=int, default=8, metavar='K',
+                        help='with --skip-nonfinite: stop when K updates in a row were skipped (default 8)')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -476,4 +486,5 @@ if __name__ == '__main__':
         use_graph=not args.no_graph, x3d_version=args.version,
         act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root, val_every=args.val_every,
         val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames,
-        clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False)
+        clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, skip_nonfinite=args.skip_nonfinite,
+        max_skip_run=args.max_skip_run)

@@ -19,11 +19,14 @@ ABI_VERSION = 1
 ITEM = 2048
 ITEMS_PER_GROUP = 4
 S_STEP, S_BAD_STEP, S_BAD_SEG, S_NORM, S_COEF = 0, 1, 2, 3, 4
+S_SKIP, S_SKIPPED, S_RUN = 5, 6, 7
+KEEP_SAVE, KEEP_RESTORE = 0, 1
 STATE_WORDS = 8
 MAX_SEGMENTS = 1 << 20
 MAX_ITEMS = 0x7fffff00
 
 ITEM_DT = np.dtype([("start", "<i8"), ("seg", "<i4"), ("len", "<i4")])
+KEEP_DT = np.dtype([("addr", "<i8"), ("offset", "<i8"), ("len", "<i4"), ("pad", "<i4")])
 HEADER_DT = np.dtype([("step", "<i8"), ("total", "<f8"), ("norm", "<f8"), ("coef", "<f4"), ("nonfinite", "<i4"),
                       ("first_bad", "<i4"), ("nseg", "<i4")])
 
@@ -32,6 +35,7 @@ _I = ctypes.c_int
 _L = ctypes.c_int64
 _D = ctypes.c_double
 _Z = ctypes.c_size_t
+_F = ctypes.c_float
 
 # name -> (restype, argtypes).  Every symbol include/x3dstep.h declares is listed here; tests/test_step_host.py checks the
 # two against each other and against the library's exports.
@@ -46,6 +50,13 @@ SIGNATURES = {
     "x3dstep_workspace_bytes": (_Z, [_L]),
     "x3dstep_observe": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _P, _P, _I, _D, _D, _P]),
     "x3dstep_observe_host": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _P, _P, _I, _D, _D]),
+    "x3dstep_keep_bytes": (_Z, []),
+    "x3dstep_measure": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _P, _P, _I, _D, _D, _P]),
+    "x3dstep_measure_host": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _P, _P, _I, _D, _D]),
+    "x3dstep_apply": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P]),
+    "x3dstep_apply_host": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _F, _F, _I]),
+    "x3dstep_keep": (_I, [_P, _I, _P, _L, _P, _L, _P, _I, _P]),
+    "x3dstep_keep_host": (_I, [_P, _I, _P, _L, _P, _L, _P, _I]),
 }
 
 _lib = None

@@ -11,6 +11,10 @@ import torch
 from . import _steplib, stepops
 
 
+class SkippedRunError(RuntimeError):
+    """Too many updates in a row were skipped for a non-finite gradient (GradMonitor.skip_report)."""
+
+
 class GradMonitor:
     def __init__(self, flat_params, names, ring=64, max_norm=None, inv_world=1.0):
         """flat_params: trainer.FlatParams (its .grad is observed unless observe() is given another buffer of the same
@@ -51,6 +55,32 @@ class GradMonitor:
         """Record the statistics of `grad` (default: the flat gradient) and, with max_norm, scale it in place."""
         stepops.observe(self.fp.grad if grad is None else grad, self.tables, self.workspace, self.state, self.ring, self.R,
                         self.max_norm, self.inv_world)
+
+    def measure(self, grad=None):
+        """Record the statistics of `grad` and the coefficient for max_norm, as `observe` does, and leave the gradient as it
+        is: the two launches before stepops.apply, which reads the decision and the coefficient from the state."""
+        stepops.measure(self.fp.grad if grad is None else grad, self.tables, self.workspace, self.state, self.ring, self.R,
+                        self.max_norm, self.inv_world)
+
+    def skipped(self):
+        """Updates stepops.apply skipped so far: an int64 device scalar (a view of the state, no copy, no sync)."""
+        return self.state[_steplib.S_SKIPPED]
+
+    def skip_run(self):
+        """Updates skipped in a row, 0 after an applied one: an int64 device scalar (a view of the state, no sync)."""
+        return self.state[_steplib.S_RUN]
+
+    def skip_report(self, max_skip_run=None):
+        """Where a training loop already waits for the loss (synchronises): the number of skipped updates, after
+        raising SkippedRunError when `max_skip_run` updates in a row were skipped."""
+        st = self.state.cpu().numpy()
+        run = int(st[_steplib.S_RUN])
+        if max_skip_run is not None and max_skip_run > 0 and run >= max_skip_run:
+            bad = self.first_nonfinite()
+            raise SkippedRunError("%d updates in a row were skipped for a non-finite gradient (limit %d); the first "
+                                  "non-finite gradient was at step %d in parameter %s"
+                                  % (run, max_skip_run, bad[0], bad[1]))
+        return int(st[_steplib.S_SKIPPED])
 
     def last_norm(self):
         """The norm of the latest observed step: a float64 device scalar (a view of the state, no copy, no sync)."""

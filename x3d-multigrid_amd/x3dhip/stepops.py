@@ -79,22 +79,50 @@ class StepTables:
             self.d_seg_item = torch.from_numpy(self.seg_item).to(self.device)
 
 
+def _check_device(who, g, tables, workspace, state, ring, R):
+    dev = tables.device
+    if dev is None or dev.type != "cuda":
+        raise ValueError("%s: the tables are not on a GPU (%s_host is the CPU twin)" % (who, who))
+    if g.device != dev or g.dtype != torch.float32 or g.dim() != 1 or not g.is_contiguous() or g.numel() != tables.n:
+        raise ValueError("%s: g must be a contiguous float32 [%d] on %s" % (who, tables.n, dev))
+    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
+        raise ValueError("%s: state must be int64 [%d] on %s" % (who, STATE_WORDS, dev))
+    for name, t, need in (("workspace", workspace, tables.workspace_bytes), ("ring", ring, R * tables.record_bytes)):
+        if t is None:
+            continue
+        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < need or R < 1:
+            raise ValueError("%s: %s must be a contiguous uint8 tensor of at least %d bytes on %s" % (who, name, need, dev))
+
+
+def _check_host(who, g, tables, workspace, state, ring, R, writeable=True):
+    if (g.dtype != np.float32 or g.ndim != 1 or g.size != tables.n or not g.flags.c_contiguous
+            or (writeable and not g.flags.writeable)):
+        raise ValueError("%s: g must be a %scontiguous float32 [%d]" % (who, "writeable " if writeable else "", tables.n))
+    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
+        raise ValueError("%s: state must be int64 [%d]" % (who, STATE_WORDS))
+    for name, a, need in (("workspace", workspace, tables.workspace_bytes), ("ring", ring, R * tables.record_bytes)):
+        if a is None:
+            continue
+        if a.dtype != np.uint8 or not a.flags.c_contiguous or a.size < need or R < 1:
+            raise ValueError("%s: %s must be a contiguous uint8 array of at least %d bytes" % (who, name, need))
+
+
 def observe(g, tables, workspace, state, ring, R, max_norm=0.0, inv_world=1.0):
     """The three launches on the current stream (two when max_norm <= 0): statistics of g into slot state[0] mod R of
     `ring`, then g *= the coefficient.  g float32 [n]; workspace / ring uint8; state int64 [STATE_WORDS]; all on the
     tables' device."""
-    dev = tables.device
-    if dev is None or dev.type != "cuda":
-        raise ValueError("observe: the tables are not on a GPU (observe_host is the CPU twin)")
-    if g.device != dev or g.dtype != torch.float32 or g.dim() != 1 or not g.is_contiguous() or g.numel() != tables.n:
-        raise ValueError("observe: g must be a contiguous float32 [%d] on %s" % (tables.n, dev))
-    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
-        raise ValueError("observe: state must be int64 [%d] on %s" % (STATE_WORDS, dev))
     R = int(R)
-    for name, t, need in (("workspace", workspace, tables.workspace_bytes), ("ring", ring, R * tables.record_bytes)):
-        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < need or R < 1:
-            raise ValueError("observe: %s must be a contiguous uint8 tensor of at least %d bytes on %s" % (name, need, dev))
+    _check_device("observe", g, tables, workspace, state, ring, R)
     check(_steplib.lib().x3dstep_observe(ptr(g), tables.n, ptr(tables.d_seg_off), tables.S, ptr(tables.d_items),
+                                         ptr(tables.d_seg_item), tables.nitems, ptr(workspace), ptr(state), ptr(ring), R,
+                                         float(max_norm), float(inv_world), stream()))
+
+
+def measure(g, tables, workspace, state, ring, R, max_norm=0.0, inv_world=1.0):
+    """The first two launches of `observe`: the record, the norm and the coefficient for max_norm; g is only read."""
+    R = int(R)
+    _check_device("measure", g, tables, workspace, state, ring, R)
+    check(_steplib.lib().x3dstep_measure(ptr(g), tables.n, ptr(tables.d_seg_off), tables.S, ptr(tables.d_items),
                                          ptr(tables.d_seg_item), tables.nitems, ptr(workspace), ptr(state), ptr(ring), R,
                                          float(max_norm), float(inv_world), stream()))
 
@@ -102,17 +130,113 @@ def observe(g, tables, workspace, state, ring, R, max_norm=0.0, inv_world=1.0):
 def observe_host(g, tables, workspace, state, ring, R, max_norm=0.0, inv_world=1.0):
     """The CPU twin on numpy arrays (g float32 [n] is scaled in place; state int64; workspace / ring uint8)."""
     R = int(R)
-    if g.dtype != np.float32 or g.ndim != 1 or g.size != tables.n or not g.flags.c_contiguous or not g.flags.writeable:
-        raise ValueError("observe_host: g must be a writeable contiguous float32 [%d]" % tables.n)
-    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
-        raise ValueError("observe_host: state must be int64 [%d]" % STATE_WORDS)
-    for name, a, need in (("workspace", workspace, tables.workspace_bytes), ("ring", ring, R * tables.record_bytes)):
-        if a.dtype != np.uint8 or not a.flags.c_contiguous or a.size < need or R < 1:
-            raise ValueError("observe_host: %s must be a contiguous uint8 array of at least %d bytes" % (name, need))
+    _check_host("observe_host", g, tables, workspace, state, ring, R)
     check(_steplib.lib().x3dstep_observe_host(_np_ptr(g), tables.n, _np_ptr(tables.seg_off), tables.S,
                                               _np_ptr(tables.items), _np_ptr(tables.seg_item), tables.nitems,
                                               _np_ptr(workspace), _np_ptr(state), _np_ptr(ring), R, float(max_norm),
                                               float(inv_world)))
+
+
+def measure_host(g, tables, workspace, state, ring, R, max_norm=0.0, inv_world=1.0):
+    """The CPU twin of `measure` (g is only read)."""
+    R = int(R)
+    _check_host("measure_host", g, tables, workspace, state, ring, R, writeable=False)
+    check(_steplib.lib().x3dstep_measure_host(_np_ptr(g), tables.n, _np_ptr(tables.seg_off), tables.S,
+                                              _np_ptr(tables.items), _np_ptr(tables.seg_item), tables.nitems,
+                                              _np_ptr(workspace), _np_ptr(state), _np_ptr(ring), R, float(max_norm),
+                                              float(inv_world)))
+
+
+def apply(w, g, m, tables, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, grad_scale=1.0, first=False):
+    """The guarded update, one launch on the current stream after `measure` on the same state and ring: nothing is stored
+    to w, g or m when the measured gradient had a non-finite element; otherwise ops.sgd_fused's arithmetic on g times the
+    measured coefficient (g itself is left unscaled).  Counts the skips in state[S_SKIP / S_SKIPPED / S_RUN]."""
+    R = int(R)
+    _check_device("apply", g, tables, None, state, ring, R)
+    for name, t in (("w", w), ("m", m)):
+        if t.device != g.device or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != tables.n:
+            raise ValueError("apply: %s must be a contiguous float32 [%d] on %s" % (name, tables.n, g.device))
+    check(_steplib.lib().x3dstep_apply(ptr(w), ptr(g), ptr(m), tables.n, ptr(state), ptr(ring), R, tables.S, float(lr),
+                                       float(momentum), float(weight_decay), float(grad_scale), 1 if first else 0, stream()))
+
+
+def apply_host(w, g, m, tables, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, grad_scale=1.0, first=False):
+    """The CPU twin of `apply` on numpy arrays (w and m are updated in place)."""
+    R = int(R)
+    _check_host("apply_host", g, tables, None, state, ring, R, writeable=False)
+    for name, a in (("w", w), ("m", m)):
+        if a.dtype != np.float32 or a.ndim != 1 or a.size != tables.n or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("apply_host: %s must be a writeable contiguous float32 [%d]" % (name, tables.n))
+    check(_steplib.lib().x3dstep_apply_host(_np_ptr(w), _np_ptr(g), _np_ptr(m), tables.n, _np_ptr(state), _np_ptr(ring), R,
+                                            tables.S, float(lr), float(momentum), float(weight_decay), float(grad_scale),
+                                            1 if first else 0))
+
+
+class KeepTable:
+    """The table `keep` takes for a list of small float32 buffers: where each lies in the snapshot (every buffer starts on
+    a multiple of four elements, so that a 16-byte aligned buffer is copied in 16-byte groups), the item table of the
+    snapshot (the cut of build_items) and the snapshot itself.
+
+    buffers: contiguous float32 torch tensors on one GPU, which the table keeps alive -- or, for the CPU twin, numpy arrays
+    (`device` None)."""
+
+    def __init__(self, buffers, device=None):
+        self.buffers = list(buffers)
+        if not self.buffers:
+            raise ValueError("KeepTable: no buffers")
+        self.device = None if device is None else torch.device(device)
+        lens, addrs = [], []
+        for b in self.buffers:
+            if self.device is None:
+                ok = (isinstance(b, np.ndarray) and b.dtype == np.float32 and b.ndim == 1 and b.flags.c_contiguous
+                      and b.flags.writeable and b.size >= 1)
+                addr = b.ctypes.data if ok else 0
+                k = b.size if ok else 0
+            else:
+                ok = (b.device == self.device and b.dtype == torch.float32 and b.is_contiguous() and b.numel() >= 1)
+                addr = b.data_ptr() if ok else 0
+                k = b.numel() if ok else 0
+            if not ok:
+                raise ValueError("KeepTable: every buffer must be a non-empty contiguous float32 %s"
+                                 % ("array" if self.device is None else "tensor on %s" % self.device))
+            lens.append(k)
+            addrs.append(addr)
+        padded = [(k + 3) // 4 * 4 for k in lens]
+        self.seg_off = segment_table(padded)
+        self.items, _ = build_items(self.seg_off)
+        self.table = np.zeros(len(lens), dtype=_steplib.KEEP_DT)
+        self.table["addr"], self.table["offset"], self.table["len"] = addrs, self.seg_off[:-1], lens
+        self.nbuf, self.nitems, self.snap_n = len(lens), int(self.items.size), int(self.seg_off[-1])
+        if self.device is None:
+            self.snap = aligned_bytes(4 * self.snap_n).view(np.float32)
+        else:
+            self.snap = torch.zeros(self.snap_n, dtype=torch.float32, device=self.device)
+            self.d_table = torch.from_numpy(self.table.view(np.uint8).copy()).to(self.device)
+            self.d_items = torch.from_numpy(self.items.view(np.uint8).copy()).to(self.device)
+
+
+def keep(kt, state, mode):
+    """One launch on the current stream: mode KEEP_SAVE copies the table's buffers into its snapshot; KEEP_RESTORE copies
+    them back when state[S_SKIP] == 1 (the latest `apply` skipped) and does nothing otherwise."""
+    dev = kt.device
+    if dev is None or dev.type != "cuda":
+        raise ValueError("keep: the table is not on a GPU (keep_host is the CPU twin)")
+    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
+        raise ValueError("keep: state must be int64 [%d] on %s" % (STATE_WORDS, dev))
+    if mode not in (_steplib.KEEP_SAVE, _steplib.KEEP_RESTORE):
+        raise ValueError("keep: mode must be KEEP_SAVE or KEEP_RESTORE (got %r)" % (mode,))
+    check(_steplib.lib().x3dstep_keep(ptr(kt.d_table), kt.nbuf, ptr(kt.d_items), kt.nitems, ptr(kt.snap), kt.snap_n,
+                                      ptr(state), int(mode), stream()))
+
+
+def keep_host(kt, state, mode):
+    """The CPU twin of `keep` (a KeepTable of numpy arrays; state int64 [STATE_WORDS])."""
+    if kt.device is not None:
+        raise ValueError("keep_host: the table is on a GPU")
+    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
+        raise ValueError("keep_host: state must be int64 [%d]" % STATE_WORDS)
+    check(_steplib.lib().x3dstep_keep_host(_np_ptr(kt.table), kt.nbuf, _np_ptr(kt.items), kt.nitems, _np_ptr(kt.snap),
+                                           kt.snap_n, _np_ptr(state), int(mode)))
 
 
 def aligned_bytes(nbytes, align=16):

@@ -120,7 +120,7 @@ class Trainer:
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
-                 objective="ce", clip_grad_norm=None, monitor=False):
+                 objective="ce", clip_grad_norm=None, monitor=False, skip_nonfinite=False):
         """overlap: multi-rank steps are captured as two graphs around the first gradient bucket (False: single graph,
         all-reduce after the whole backward); force_split: the two-graph form on a single rank too (tests);
         force_collectives: all-reduce on a one-rank process group (the single-GPU RCCL test).  Round 4: constructor
@@ -141,6 +141,20 @@ class Trainer:
         is that of the all-reduced gradient / world, so every rank computes the same coefficient).  monitor: True (a ring of
         64 records) or the ring's size.  Both off (the default): no attribute, not one extra launch.  The ring is
         diagnostics, not optimizer state: state_dict() is the same either way.
+
+        skip_nonfinite: drop an update whose gradient (after the all-reduce and `pre_step`) has a NaN or an Inf, decided and
+        carried out on the device with no host sync.  Implies a monitor (a ring of 64 unless monitor= says otherwise).  The
+        update becomes monitor.measure (two launches) and stepops.apply (one launch: the clipping multiply and the SGD
+        arithmetic of ops.sgd_fused, bit for bit, or no store at all), in every form of the step (eager, graph, split
+        graph, accumulation, data parallel: every rank measures the same all-reduced gradient and decides alike).  A
+        skipped update leaves the parameters, the momentum and every split_bn.running_mean / running_var as they were
+        before the step: the running statistics are saved by one launch before the forward pass of the update's first
+        micro-batch and put back by one launch after `apply` (each rank its own).  num_batches_tracked is not rolled
+        back: it counts forward passes, skipped ones included, and nothing reads it (the BN momentum is the fixed 0.1).
+        `first` stays a host value: when the very first update is skipped, the next one runs with first=False on a
+        momentum buffer of zeros, which gives the same values (fmaf(mu, 0, g) == g) and can differ only in the sign of a
+        zero.  monitor.skipped() / skip_run() count on the device.  The snapshot and the counters are not optimizer state:
+        state_dict() is unchanged.  Off (the default): not one launch is added.
 
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
@@ -174,7 +188,9 @@ class Trainer:
         model._direct_grads = True      # engine writes parameter gradients straight into fp.grad
         self.reducer = GradReducer(self.fp.grad, self.fp.head_first_buckets(model), world_size, process_group,
                                    force_collectives=force_collectives)
-        if clip_grad_norm is not None or monitor:
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._keep = self._keep_old = None
+        if clip_grad_norm is not None or monitor or self.skip_nonfinite:
             from .gradmonitor import GradMonitor
             ring = 64 if (monitor is True or not monitor) else int(monitor)
             self.monitor = GradMonitor(self.fp, [k for k, _ in model.named_parameters()], ring=ring,
@@ -272,11 +288,43 @@ class Trainer:
     def _allreduce(self):
         self.reducer.reduce()
 
+    def _keep_table(self):
+        """The keep table over split_bn.running_mean / running_var of every SubBatchNorm3d, rebuilt when the long-cycle
+        switch re-created those buffers.  The table before stays referenced until the next rebuild: every launch that
+        names it was enqueued on this stream before the first launch on the new one."""
+        from . import stepops
+        ver = self.model._bn_version
+        if self._keep is None or self._keep_version != ver:
+            bufs = []
+            for mod in self.model.modules():
+                sb = getattr(mod, "split_bn", None)
+                if sb is not None:
+                    bufs += [sb.running_mean, sb.running_var]
+            self._keep_old = self._keep
+            self._keep = stepops.KeepTable(bufs, self.fp.grad.device)
+            self._keep_version = ver
+        return self._keep
+
+    def _keep_save(self):
+        """Before the forward pass of an update's first micro-batch, outside every graph: the running statistics as they
+        are now, whoever wrote them last."""
+        if self.skip_nonfinite:
+            from . import _steplib, stepops
+            stepops.keep(self._keep_table(), self.monitor.state, _steplib.KEEP_SAVE)
+
     def _sgd(self, grad=None):
         mon = getattr(self, "monitor", None)
+        g = self.param_groups[0]
+        if self.skip_nonfinite:
+            from . import _steplib, stepops
+            mon.measure(grad)                # the decision and the coefficient stay on the device
+            stepops.apply(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, mon.tables, mon.state,
+                          mon.ring, mon.R, g['lr'], g['momentum'], g['weight_decay'], 1.0 / self.world, first=self.first)
+            stepops.keep(self._keep_table(), mon.state, _steplib.KEEP_RESTORE)
+            self.first = False
+            return
         if mon is not None:                  # statistics (and clipping) of exactly what the SGD kernel is about to apply
             mon.observe(grad)
-        g = self.param_groups[0]
         ops.sgd_fused(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, g['lr'], g['momentum'],
                       g['weight_decay'], 1.0 / self.world, first=self.first)
         self.first = False
@@ -296,6 +344,7 @@ class Trainer:
         if self.num_steps_per_update > 1:
             return self._train_step_accum(x, y, pre_step)
         self.stepped = True
+        self._keep_save()
         if self.use_graph and self._overlap():
             loss, logits = self._graphed_split(x, y)        # all-reduce issued inside, overlapped with the early layers
         else:
@@ -351,6 +400,8 @@ class Trainer:
 
     def _train_step_accum(self, x, y, pre_step):
         K = self.num_steps_per_update
+        if self._micro == 0:
+            self._keep_save()
         loss, logits = self._graphed_fwd_bwd(x, y) if self.use_graph else self._fwd_bwd(x, y)
         ops.grad_accumulate(self.accum, self.fp.grad, 1.0 / K, first=self._micro == 0)
         self._micro += 1
