@@ -50,6 +50,13 @@
  *   [X3DSTEP_S_SKIPPED]   updates x3dstep_apply skipped so far
  *   [X3DSTEP_S_RUN]       updates skipped in a row; an applied update sets it to 0
  * x3dstep_observe / x3dstep_measure never touch the last three words; only x3dstep_apply writes them.
+ *
+ * The weight average (x3dstep_ema, x3dstep_ema_keep; the exchange x3dstep_swap, x3dstep_swap_keep)
+ *   An exponential moving average of the parameters and of the kept buffers, updated after every applied update by
+ *   launches that read the state and never write it: S_STEP - S_SKIPPED is the number of updates applied so far, so the
+ *   average needs no counter of its own, skips what x3dstep_apply skipped, and warms its decay up by the count of updates
+ *   that were really averaged.  Scoring with the average exchanges it with the live buffers in place, bit for bit, so
+ *   that no address a captured graph holds moves.
  */
 #ifndef X3DSTEP_H
 #define X3DSTEP_H
@@ -194,6 +201,51 @@ int x3dstep_keep(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, i
                  const int64_t* state, int mode, void* stream);
 int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
                       int64_t snap_n, const int64_t* state, int mode);
+
+/*
+ * The weight average: e <- d * e + (1 - d) * w after an update of w.
+ *   count rule   k = count + (state ? state[X3DSTEP_S_STEP] - state[X3DSTEP_S_SKIPPED] : 0), computed by every thread.  With a
+ *                state, S_STEP - S_SKIPPED is the number of updates applied so far, this one included (x3dstep_measure /
+ *                x3dstep_observe and x3dstep_apply wrote both words in earlier launches), and count is an offset that may be
+ *                negative.  state may be null: count is then the host's own count of updates, this one included.
+ *   skip rule    state non-null and state[X3DSTEP_S_SKIP] == 1 (the latest x3dstep_apply skipped): the whole grid leaves
+ *                without a store.  k <= 0: the twin refuses with X3DSTEP_EINVAL; the kernel, which alone can read the
+ *                device's words, leaves without a store.
+ *   decay rule   fp64, rounded once per value: d = (float)(warmup ? min((double)decay, (1 + k) / (10.0 + k)) : (double)decay),
+ *                omd = (float)(1.0 - (double)d)
+ *   element rule fp32, each operation rounded once: p = omd * w[i]; e'[i] = fmaf(d, e[i], p)
+ * No thread of these launches writes a word another thread of the same launch reads; w is only read.  Refused: null or
+ * 4-byte-unaligned pointers, n < 1, decay outside [0, 1) or NaN, e overlapping w.
+ *   x3dstep_ema: e, w fp32 [n]; one launch shaped like x3dstep_apply: 16-byte groups when e and w are congruent mod 16 (at
+ *   most three head and three tail elements one by one in workgroup 0), an element kernel otherwise; a lane's loads are
+ *   issued before its first store; every element of e stored once.  No LDS, no atomics, no allocation, no
+ *   synchronisation: capturable (count is then part of the captured launch).
+ */
+int x3dstep_ema(float* e, const float* w, int64_t n, const int64_t* state, int64_t count, float decay, int warmup, void* stream);
+int x3dstep_ema_host(float* e, const float* w, int64_t n, const int64_t* state, int64_t count, float decay, int warmup);
+
+/*
+ * The same rules over a keep table (x3dstep_keep's table and items), esnap in the place of snap: one wave per item,
+ * esnap[offset + j] <- fmaf(d, esnap[offset + j], omd * live[j]).  The per-item tests are x3dstep_keep's: an item that fails
+ * them is not touched, and what lies past len in a padded tensor is left alone.  The live buffers are only read.
+ */
+int x3dstep_ema_keep(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* esnap, int64_t snap_n,
+                     const int64_t* state, int64_t count, float decay, int warmup, void* stream);
+int x3dstep_ema_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* esnap,
+                          int64_t snap_n, const int64_t* state, int64_t count, float decay, int warmup);
+
+/*
+ * The exchange: a <-> b (fp32 [n], 4-byte aligned, not overlapping), or the live buffers of a table <-> their snapshot, in
+ * place and bit for bit (the values are moved as 32-bit words: NaN payloads and the sign of zero are kept).  One launch
+ * each, both sides of a lane loaded before its first store, every element of both sides stored once, the vectorisation
+ * rules of x3dstep_ema / x3dstep_keep.  Two exchanges are the identity.
+ */
+int x3dstep_swap(float* a, float* b, int64_t n, void* stream);
+int x3dstep_swap_host(float* a, float* b, int64_t n);
+int x3dstep_swap_keep(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap, int64_t snap_n,
+                      void* stream);
+int x3dstep_swap_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
+                           int64_t snap_n);
 
 #ifdef __cplusplus
 }

@@ -185,9 +185,12 @@ def _rank_mean(values, process_group, world):
 
 
 def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
-    """The reference's checkpoint record (train_x3d_charades.py:203-207)."""
+    """The reference's checkpoint record (train_x3d_charades.py:203-207); with a weight average (Trainer(ema_decay=)) also
+    'ema_state_dict'."""
     ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
             'scheduler_state_dict': lr_sched.state_dict()}
+    if getattr(optimizer, 'ema', None) is not None:
+        ckpt['ema_state_dict'] = optimizer.ema.state_dict()
     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
     path = save_model + str(steps).zfill(6) + '.pt'
     torch.save(ckpt, path)
@@ -197,7 +200,7 @@ def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
 def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
         device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -210,7 +213,14 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     `clip` (of the latest update) and rank 0 reports the first non-finite gradient when the run ends, also on an exception.
     skip_nonfinite / max_skip_run: Trainer(skip_nonfinite=True) drops an update whose gradient has a NaN or an Inf; the log
     line gains `skipped N`, and when max_skip_run updates in a row were skipped the run stops with
-    gradmonitor.SkippedRunError, which names the first non-finite gradient (checked where the losses are read)."""
+    gradmonitor.SkippedRunError, which names the first non-finite gradient (checked where the losses are read).
+    ema_decay / ema_warmup: Trainer(ema_decay=, ema_warmup=) keeps an exponential moving average of the weights and the
+    split-BN running statistics on the GPU.  Every 'val' phase is then run a second time inside `optimizer.ema.applied()`
+    -- the broadcast of rank 0's buffers and the aggregation of the statistics included, so that every rank's averaged
+    statistics are rank 0's afterwards, as the live ones are; the live statistics are aggregated again after the block --
+    and printed with the prefix EMA (the phase record gains
+    'ema_map' and 'ema_loss'; the learning-rate schedule follows the live loss alone).  Checkpoints gain
+    'ema_state_dict', which `resume` restores when it is there (otherwise the average starts from the loaded weights)."""
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
     ddp = process_group is not None and world > 1
@@ -260,12 +270,16 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     optimizer = Trainer(x3d, lr=lr, momentum=0.9, weight_decay=1e-5, objective='loc' if loc else 'bce',
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update,
                         clip_grad_norm=clip_grad_norm, monitor=monitor, skip_nonfinite=skip_nonfinite,
+                        ema_decay=ema_decay, ema_warmup=ema_warmup,
                         **(dict(process_group=process_group, world_size=world) if ddp else {}))
     mon = getattr(optimizer, 'monitor', None)
+    ema = getattr(optimizer, 'ema', None)
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
     if ck is not None:
         optimizer.load_state_dict(ck['optimizer_state_dict'])
         lr_sched.load_state_dict(ck['scheduler_state_dict'])
+        if ema is not None and 'ema_state_dict' in ck:
+            ema.load_state_dict(ck['ema_state_dict'])
 
     val_apm = APMeter(track_segments=ddp)
     tr_apm = APMeter(track_segments=ddp)
@@ -352,6 +366,22 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                             epochs, phase, res['cls_loss'], (tot_loss * num_steps_per_update) / num_iter, val_map))
                     phases.append(dict(phase=phase, epoch=epochs, map=val_map, loss=tot_loss, rows=res['rows'],
                                        lr=optimizer.param_groups[0]['lr'], steps=steps))
+                    if ema is not None:
+                        with ema.applied():              # the same phase on the averaged weights and statistics
+                            if ddp:
+                                _broadcast(list(x3d.buffers()), process_group)
+                            gen = (val_dataset.test_batch(idx) for idx in (vb[rank::world] if ddp else vb))
+                            res = (charades_eval.validate_loc if loc else charades_eval.validate_cls)(
+                                x3d, gen, val_apm, **(dict(process_group=process_group) if ddp else {}))
+                        x3d.aggregate_sub_bn_stats()     # bn.* belong to the live statistics again
+                        val_apm.reset()
+                        if loc:
+                            say(' EMA Epoch:{} {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                                epochs, phase, res['loc_loss'], res['cls_loss'], res['loss'], res['map']))
+                        else:
+                            say(' EMA Epoch:{} {} Loc Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                                epochs, phase, res['cls_loss'], res['loss'], res['map']))
+                        phases[-1].update(ema_map=res['map'], ema_loss=res['loss'] * num_iter / num_steps_per_update)
     finally:
         torch.cuda.synchronize()
         bad = mon.first_nonfinite() if mon is not None else None

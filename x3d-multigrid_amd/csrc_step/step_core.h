@@ -327,4 +327,110 @@ STEP_HD void keep_lane(const KeepCopy& c, int lane) {
     for (int j = 4 * groups + lane; j < c.len; j += kLanes) c.dst[j] = c.src[j];
 }
 
+// -- the weight average (x3dstep_ema, x3dstep_ema_keep) --------------------------------------------------------------------
+// The number of the update being averaged: the host's `count`, plus (with a state) the updates applied so far, which
+// x3dstep_measure / x3dstep_observe and x3dstep_apply counted in earlier launches.  The EMA launches only read the words.
+STEP_HD int64_t ema_count(const int64_t* state, int64_t count) {
+    return count + (state ? state[X3DSTEP_S_STEP] - state[X3DSTEP_S_SKIPPED] : 0);
+}
+
+// the latest x3dstep_apply left the parameters alone: there is nothing new to average
+STEP_HD bool ema_skips(const int64_t* state) { return state && state[X3DSTEP_S_SKIP] == 1; }
+
+struct EmaCoef {
+    float d, omd;
+};
+
+// the decay of update k (k >= 1) and one minus it: fp64, each rounded to fp32 once
+STEP_HD EmaCoef ema_coef(int64_t k, float decay, int warmup) {
+    double d = (double)decay;
+    if (warmup) {
+        const double r = (double)(1 + k) / (10.0 + (double)k);
+        if (r < d) d = r;
+    }
+    EmaCoef c;
+    c.d = (float)d;
+    c.omd = (float)(1.0 - (double)c.d);
+    return c;
+}
+
+// one element, fp32, each operation rounded once
+STEP_HD void ema_one(float& e, float w, const EmaCoef& c) {
+    const float p = c.omd * w;
+    e = fmaf(c.d, e, p);
+}
+
+// the plan of two flat buffers (x3dstep_ema, x3dstep_swap): 16-byte groups when both addresses are congruent mod 16
+STEP_HD ApplyPlan pair_plan(const void* a, const void* b, int64_t n) {
+    ApplyPlan p;
+    const uintptr_t r = (uintptr_t)a & 15;
+    p.vec = r == ((uintptr_t)b & 15);
+    p.head = (int64_t)(((16 - r) & 15) >> 2);
+    if (p.head > n) p.head = n;
+    p.groups = (n - p.head) >> 2;
+    p.tail = p.head + 4 * p.groups;
+    return p;
+}
+
+// What lane `lane` of the item's wave averages: c.dst is the averaged snapshot's part of the item and c.src the live
+// buffer's (keep_resolve with X3DSTEP_KEEP_SAVE).  The walk of keep_lane: all loads of the groups before the first store.
+STEP_HD void ema_lane(const KeepCopy& c, int lane, const EmaCoef& k) {
+    const bool vec = (((uintptr_t)c.dst | (uintptr_t)c.src) & 15) == 0;
+    const int groups = vec ? c.len >> 2 : 0;
+    Vec4 e[kKeepPieces], w[kKeepPieces];
+#pragma unroll
+    for (int i = 0; i < kKeepPieces; ++i) {
+        const int q = lane + i * kLanes;
+        if (q < groups) {
+            e[i] = ((const Vec4*)c.dst)[q];
+            w[i] = ((const Vec4*)c.src)[q];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kKeepPieces; ++i) {
+        const int q = lane + i * kLanes;
+        if (q < groups) {
+            for (int x = 0; x < 4; ++x) ema_one(e[i].v[x], w[i].v[x], k);
+            ((Vec4*)c.dst)[q] = e[i];
+        }
+    }
+    for (int j = 4 * groups + lane; j < c.len; j += kLanes) ema_one(c.dst[j], c.src[j], k);
+}
+
+// -- the exchange (x3dstep_swap, x3dstep_swap_keep) ------------------------------------------------------------------------
+// Bits, not floats: no operation that could quieten a NaN or lose a payload ever sees the values.
+typedef uint32_t Bits4 __attribute__((vector_size(16)));      // one 16-byte load or store, in registers
+
+STEP_HD void swap_one(uint32_t& a, uint32_t& b) {
+    const uint32_t t = a;
+    a = b;
+    b = t;
+}
+
+// what lane `lane` of the item's wave exchanges: the walk of keep_lane, both sides loaded before the first store
+STEP_HD void swap_lane(const KeepCopy& c, int lane) {
+    const bool vec = (((uintptr_t)c.dst | (uintptr_t)c.src) & 15) == 0;
+    const int groups = vec ? c.len >> 2 : 0;
+    uint32_t* a = (uint32_t*)c.dst;
+    uint32_t* b = (uint32_t*)c.src;
+    Bits4 x[kKeepPieces], y[kKeepPieces];
+#pragma unroll
+    for (int i = 0; i < kKeepPieces; ++i) {
+        const int q = lane + i * kLanes;
+        if (q < groups) {
+            x[i] = ((const Bits4*)a)[q];
+            y[i] = ((const Bits4*)b)[q];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < kKeepPieces; ++i) {
+        const int q = lane + i * kLanes;
+        if (q < groups) {
+            ((Bits4*)a)[q] = y[i];
+            ((Bits4*)b)[q] = x[i];
+        }
+    }
+    for (int j = 4 * groups + lane; j < c.len; j += kLanes) swap_one(a[j], b[j]);
+}
+
 }  // namespace x3ds

@@ -224,35 +224,172 @@ int x3dstep_check_keep(const char* who, const X3DStepKeep* table, int nbuf, cons
     return X3DSTEP_OK;
 }
 
-extern "C" int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
-                                 int64_t snap_n, const int64_t* state, int mode) {
+// The tables are host memory in a twin: refuse the call for what the kernel would leave out item by item.
+static int table_host_ok(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
+                         float* snap, int64_t snap_n) {
     using namespace x3ds;
-    const int rc = x3dstep_check_keep("x3dstep_keep_host", table, nbuf, items, nitems, snap, snap_n, state, mode);
-    if (rc) return rc;
-    // the tables are host memory here: refuse the call for what the kernel would leave out item by item
     for (int b = 0; b < nbuf; ++b) {
         const X3DStepKeep k = table[b];
         if (k.addr == 0 || (k.addr & 3) != 0 || k.len < 1 || k.offset < 0 || k.offset > snap_n - k.len ||
             (b > 0 && k.offset < table[b - 1].offset + table[b - 1].len)) {
-            x3dstep_set_error("x3dstep_keep_host: buffer %d: a null or unaligned address, or a range outside snap or over the "
-                              "buffer before it", b);
+            x3dstep_set_error("%s: buffer %d: a null or unaligned address, or a range outside snap or over the buffer before "
+                              "it", who, b);
             return X3DSTEP_EINVAL;
         }
     }
     for (int64_t i = 0; i < nitems; ++i) {
         bool bad;
-        (void)keep_resolve(table, nbuf, items, i, snap, snap_n, mode, &bad);
+        (void)keep_resolve(table, nbuf, items, i, snap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
         if (bad) {
-            x3dstep_set_error("x3dstep_keep_host: item %lld lies outside snap or outside its buffer's range", (long long)i);
+            x3dstep_set_error("%s: item %lld lies outside snap or outside its buffer's range", who, (long long)i);
             return X3DSTEP_EINVAL;
         }
     }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
+                                 int64_t snap_n, const int64_t* state, int mode) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_keep("x3dstep_keep_host", table, nbuf, items, nitems, snap, snap_n, state, mode);
+    if (rc) return rc;
+    const int rt = table_host_ok("x3dstep_keep_host", table, nbuf, items, nitems, snap, snap_n);
+    if (rt) return rt;
     if (mode == X3DSTEP_KEEP_RESTORE && state[X3DSTEP_S_SKIP] != 1) return X3DSTEP_OK;
     for (int64_t i = 0; i < nitems; ++i) {
         bool bad;
         const KeepCopy c = keep_resolve(table, nbuf, items, i, snap, snap_n, mode, &bad);
         if (c.len > 0)
             for (int l = 0; l < kLanes; ++l) keep_lane(c, l);
+    }
+    return X3DSTEP_OK;
+}
+
+// -- the weight average and the exchange ----------------------------------------------------------------------------------
+static bool ranges_overlap(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+    return x < y + bytes && y < x + bytes;
+}
+
+// the argument checks x3dstep_ema and its twin share (no pointer is followed)
+int x3dstep_check_ema(const char* who, const float* e, const float* w, int64_t n, const int64_t* state, float decay) {
+    if (!e || !w || n < 1 || n > ((int64_t)1 << 40) || (((uintptr_t)e | (uintptr_t)w) & 3) != 0 || ((uintptr_t)state & 7) != 0 ||
+        !(decay >= 0.0f && decay < 1.0f) || ranges_overlap(e, w, n)) {
+        x3dstep_set_error("%s: null, unaligned or overlapping pointers, n %lld outside 1 .. 2^40 or decay %g outside [0, 1)", who,
+                          (long long)n, (double)decay);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+int x3dstep_check_swap(const char* who, const float* a, const float* b, int64_t n) {
+    if (!a || !b || n < 1 || n > ((int64_t)1 << 40) || (((uintptr_t)a | (uintptr_t)b) & 3) != 0 || ranges_overlap(a, b, n)) {
+        x3dstep_set_error("%s: null, unaligned or overlapping pointers or n %lld outside 1 .. 2^40", who, (long long)n);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+// the argument checks of the table forms (state may be null; x3dstep_swap_keep passes decay 0)
+int x3dstep_check_table(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
+                        const float* snap, int64_t snap_n, const int64_t* state, float decay) {
+    if (!table || !items || !snap || nbuf < 1 || nbuf > X3DSTEP_MAX_SEGMENTS || nitems < nbuf || nitems > X3DSTEP_MAX_ITEMS ||
+        snap_n < 1 || (((uintptr_t)table | (uintptr_t)items | (uintptr_t)state) & 7) != 0 || ((uintptr_t)snap & 3) != 0 ||
+        !(decay >= 0.0f && decay < 1.0f)) {
+        x3dstep_set_error("%s: null or unaligned pointer, nbuf %d outside 1 .. %d, nitems %lld outside nbuf .. %d, snap_n %lld "
+                          "< 1 or decay %g outside [0, 1)", who, nbuf, X3DSTEP_MAX_SEGMENTS, (long long)nitems,
+                          X3DSTEP_MAX_ITEMS, (long long)snap_n, (double)decay);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+// k of this call, or 0 with the refusal's text: the twin can read the words the kernel alone can read on the device
+static int64_t ema_count_host(const char* who, const int64_t* state, int64_t count) {
+    const int64_t k = x3ds::ema_count(state, count);
+    if (k <= 0) x3dstep_set_error("%s: the count of applied updates is %lld: nothing to average", who, (long long)k);
+    return k <= 0 ? 0 : k;
+}
+
+extern "C" int x3dstep_ema_host(float* e, const float* w, int64_t n, const int64_t* state, int64_t count, float decay,
+                                int warmup) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_ema("x3dstep_ema_host", e, w, n, state, decay);
+    if (rc) return rc;
+    const int64_t k = ema_count_host("x3dstep_ema_host", state, count);
+    if (k == 0) return X3DSTEP_EINVAL;
+    if (ema_skips(state)) return X3DSTEP_OK;
+    const EmaCoef c = ema_coef(k, decay, warmup ? 1 : 0);
+    // the kernel's walk: the plan decides which element goes through a 16-byte group; the arithmetic is per element
+    const ApplyPlan plan = pair_plan(e, w, n);
+    if (plan.vec) {
+        for (int64_t i = 0; i < plan.head; ++i) ema_one(e[i], w[i], c);
+        for (int64_t q = 0; q < plan.groups; ++q) {
+            Vec4 ev = *(Vec4*)(e + plan.head + 4 * q);
+            const Vec4 wv = *(const Vec4*)(w + plan.head + 4 * q);
+            for (int x = 0; x < 4; ++x) ema_one(ev.v[x], wv.v[x], c);
+            *(Vec4*)(e + plan.head + 4 * q) = ev;
+        }
+        for (int64_t i = plan.tail; i < n; ++i) ema_one(e[i], w[i], c);
+    } else {
+        for (int64_t i = 0; i < n; ++i) ema_one(e[i], w[i], c);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_ema_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* esnap,
+                                     int64_t snap_n, const int64_t* state, int64_t count, float decay, int warmup) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_table("x3dstep_ema_keep_host", table, nbuf, items, nitems, esnap, snap_n, state, decay);
+    if (rc) return rc;
+    const int rt = table_host_ok("x3dstep_ema_keep_host", table, nbuf, items, nitems, esnap, snap_n);
+    if (rt) return rt;
+    const int64_t k = ema_count_host("x3dstep_ema_keep_host", state, count);
+    if (k == 0) return X3DSTEP_EINVAL;
+    if (ema_skips(state)) return X3DSTEP_OK;
+    const EmaCoef c = ema_coef(k, decay, warmup ? 1 : 0);
+    for (int64_t i = 0; i < nitems; ++i) {
+        bool bad;
+        const KeepCopy kc = keep_resolve(table, nbuf, items, i, esnap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
+        if (kc.len > 0)
+            for (int l = 0; l < kLanes; ++l) ema_lane(kc, l, c);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_swap_host(float* a, float* b, int64_t n) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_swap("x3dstep_swap_host", a, b, n);
+    if (rc) return rc;
+    uint32_t* x = (uint32_t*)a;
+    uint32_t* y = (uint32_t*)b;
+    const ApplyPlan plan = pair_plan(a, b, n);
+    if (plan.vec) {
+        for (int64_t i = 0; i < plan.head; ++i) swap_one(x[i], y[i]);
+        for (int64_t q = 0; q < plan.groups; ++q) {
+            const Bits4 xv = *(const Bits4*)(x + plan.head + 4 * q), yv = *(const Bits4*)(y + plan.head + 4 * q);
+            *(Bits4*)(x + plan.head + 4 * q) = yv;
+            *(Bits4*)(y + plan.head + 4 * q) = xv;
+        }
+        for (int64_t i = plan.tail; i < n; ++i) swap_one(x[i], y[i]);
+    } else {
+        for (int64_t i = 0; i < n; ++i) swap_one(x[i], y[i]);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_swap_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
+                                      int64_t snap_n) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_table("x3dstep_swap_keep_host", table, nbuf, items, nitems, snap, snap_n, nullptr, 0.0f);
+    if (rc) return rc;
+    const int rt = table_host_ok("x3dstep_swap_keep_host", table, nbuf, items, nitems, snap, snap_n);
+    if (rt) return rt;
+    for (int64_t i = 0; i < nitems; ++i) {
+        bool bad;
+        const KeepCopy kc = keep_resolve(table, nbuf, items, i, snap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
+        if (kc.len > 0)
+            for (int l = 0; l < kLanes; ++l) swap_lane(kc, l);
     }
     return X3DSTEP_OK;
 }

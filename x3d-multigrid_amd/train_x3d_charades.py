@@ -40,7 +40,7 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
     every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
@@ -56,7 +56,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               num_steps_per_update=num_steps_per_update, crop_size=crop_size, c_size=c_size,
                               dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
                               world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor,
-                              skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run)
+                              skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
+                              ema_warmup=ema_warmup)
 
 
 def init_distributed():
@@ -115,6 +116,12 @@ def main(run_fn, default_save):
                              'log line gains skipped')
     parser.add_argument('--max-skip-run', type=int, default=8, metavar='K',
                         help='with --skip-nonfinite: stop when K updates in a row were skipped (default 8)')
+    parser.add_argument('--ema-decay', type=float, default=None, metavar='D',
+                        help='keep an exponential moving average of the weights and the split-BN statistics with this decay on '
+                             'the GPU; every validation is also run with it (a line prefixed EMA) and checkpoints gain '
+                             'ema_state_dict (off by default)')
+    parser.add_argument('--no-ema-warmup', action='store_true',
+                        help='with --ema-decay: use D from the first update on instead of min(D, (1 + k) / (10 + k))')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -131,7 +138,8 @@ def main(run_fn, default_save):
                load_ckpt=args.load, resume=args.resume, save_model=args.save, save_every=args.save_every,
                use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,
                rank=rank, world=world, clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False,
-               skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, **size)
+               skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, ema_decay=args.ema_decay,
+               ema_warmup=not args.no_ema_warmup, **size)
     finally:
         if pg is not None:
             import torch.distributed as dist

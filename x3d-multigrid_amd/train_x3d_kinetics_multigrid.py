@@ -171,9 +171,12 @@ def val_line(res):
 
 
 def _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps):
-    """The reference's checkpoint record (train_x3d_kinetics_multigrid.py:286-291)."""
+    """The reference's checkpoint record (train_x3d_kinetics_multigrid.py:286-291); with a weight average
+    (Trainer(ema_decay=)) also 'ema_state_dict'."""
     ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
             'scheduler_state_dict': lr_sched.state_dict(), 'long_ind': long_ind}
+    if getattr(optimizer, 'ema', None) is not None:
+        ckpt['ema_state_dict'] = optimizer.ema.state_dict()
     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
     torch.save(ckpt, save_model + str(steps).zfill(6) + '.pt')
 
@@ -201,7 +204,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
-        frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8):
+        frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8,
+        ema_decay=None, ema_warmup=True):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -219,7 +223,12 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     rank 0 reports the first non-finite gradient (step, parameter) when the run ends, also when it ends in an exception.
     skip_nonfinite: Trainer(skip_nonfinite=True) -- an update whose gradient has a NaN or an Inf is dropped on the GPU; the
     log line gains `skipped N`, and when max_skip_run updates in a row were skipped the run stops with
-    gradmonitor.SkippedRunError, which names the first non-finite gradient (checked where the loss is read)."""
+    gradmonitor.SkippedRunError, which names the first non-finite gradient (checked where the loss is read).
+    ema_decay / ema_warmup: Trainer(ema_decay=, ema_warmup=) -- an exponential moving average of the weights and the split-BN
+    running statistics on the GPU.  Every validation is then run a second time inside `optimizer.ema.applied()` (the
+    aggregation of the statistics included; the live ones are aggregated again afterwards, so that bn.* in a checkpoint are
+    the live model's) and printed with the prefix EMA; checkpoints gain 'ema_state_dict', which
+    load_ckpt restores when it is there (otherwise the average starts from the loaded weights)."""
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -268,13 +277,16 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     lr = init_lr
     optimizer = Trainer(model, lr=lr, momentum=0.9, weight_decay=5e-5, process_group=pg, world_size=world,
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update, clip_grad_norm=clip_grad_norm,
-                        monitor=monitor, skip_nonfinite=skip_nonfinite)
+                        monitor=monitor, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
     mon = getattr(optimizer, 'monitor', None)
+    ema = getattr(optimizer, 'ema', None)
     lr_sched = MultiStepLR(optimizer, lr_schedule)
     if ck is not None:
         optimizer.load_state_dict(ck['optimizer_state_dict'])
         lr_sched.load_state_dict(ck['scheduler_state_dict'])
         lr = optimizer.param_groups[0]['lr']
+        if ema is not None and 'ema_state_dict' in ck:
+            ema.load_state_dict(ck['ema_state_dict'])
 
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
@@ -381,6 +393,13 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                 model.train(True)                                   # train...:199-200
                 if rank == 0:
                     print(' val after step {}: {}'.format(steps, val_line(res)), flush=True)
+                if ema is not None:
+                    with ema.applied():                             # each rank scores its shard with its own statistics
+                        res = validate_topk(model, val_ds.batches(val_batch_size, rank, world), process_group=pg)
+                    model.aggregate_sub_bn_stats()                  # bn.* belong to the live statistics again
+                    model.train(True)
+                    if rank == 0:
+                        print(' EMA val after step {}: {}'.format(steps, val_line(res)), flush=True)
             elif val_every and done % val_every == 0:
                 Tv, Hv = frames // gamma_tau, crop_size
                 vb = []
@@ -392,6 +411,14 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                 if rank == 0:
                     print(' val after step {}: Cls Loss: {:.4f} Acc: {:.4f} ({} videos)'.format(steps, v_loss, v_acc, v_seen),
                           flush=True)
+                if ema is not None:
+                    with ema.applied():
+                        v_loss, v_acc, v_seen = validate(model, vb)
+                    model.aggregate_sub_bn_stats()                  # bn.* belong to the live statistics again
+                    model.train(True)
+                    if rank == 0:
+                        print(' EMA val after step {}: Cls Loss: {:.4f} Acc: {:.4f} ({} videos)'.format(
+                            steps, v_loss, v_acc, v_seen), flush=True)
             if save_every and steps % save_every == 0 and rank == 0:
                 _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps)
         if save_every and rank == 0 and steps >= total_steps and done > 0 and steps % save_every != 0:
@@ -459,6 +486,12 @@ if __name__ == '__main__':
                              'log line gains skipped')
     parser.add_argument('--max-skip-run', type=int, default=8, metavar='K',
                         help='with --skip-nonfinite: stop when K updates in a row were skipped (default 8)')
+    parser.add_argument('--ema-decay', type=float, default=None, metavar='D',
+                        help='keep an exponential moving average of the weights and the split-BN statistics with this decay on '
+                             'the GPU; every validation is also run with it (lines prefixed EMA) and checkpoints gain '
+                             'ema_state_dict (off by default)')
+    parser.add_argument('--no-ema-warmup', action='store_true',
+                        help='with --ema-decay: use D from the first update on instead of min(D, (1 + k) / (10 + k))')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -487,4 +520,4 @@ if __name__ == '__main__':
         act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root, val_every=args.val_every,
         val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames,
         clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, skip_nonfinite=args.skip_nonfinite,
-        max_skip_run=args.max_skip_run)
+        max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)

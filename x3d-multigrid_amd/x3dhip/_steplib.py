@@ -57,6 +57,14 @@ SIGNATURES = {
     "x3dstep_apply_host": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _F, _F, _I]),
     "x3dstep_keep": (_I, [_P, _I, _P, _L, _P, _L, _P, _I, _P]),
     "x3dstep_keep_host": (_I, [_P, _I, _P, _L, _P, _L, _P, _I]),
+    "x3dstep_ema": (_I, [_P, _P, _L, _P, _L, _F, _I, _P]),
+    "x3dstep_ema_host": (_I, [_P, _P, _L, _P, _L, _F, _I]),
+    "x3dstep_ema_keep": (_I, [_P, _I, _P, _L, _P, _L, _P, _L, _F, _I, _P]),
+    "x3dstep_ema_keep_host": (_I, [_P, _I, _P, _L, _P, _L, _P, _L, _F, _I]),
+    "x3dstep_swap": (_I, [_P, _P, _L, _P]),
+    "x3dstep_swap_host": (_I, [_P, _P, _L]),
+    "x3dstep_swap_keep": (_I, [_P, _I, _P, _L, _P, _L, _P]),
+    "x3dstep_swap_keep_host": (_I, [_P, _I, _P, _L, _P, _L]),
 }
 
 _lib = None

@@ -239,6 +239,123 @@ def keep_host(kt, state, mode):
                                            kt.snap_n, _np_ptr(state), int(mode)))
 
 
+def _check_decay(who, decay):
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError("%s: decay must lie in [0, 1) (got %r)" % (who, decay))
+    return decay
+
+
+def _check_flat_pair(who, a, b, dev):
+    for t in (a, b):
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.dim() != 1
+                or not t.is_contiguous() or t.numel() != a.numel() or t.numel() < 1):
+            raise ValueError("%s: both buffers must be contiguous float32 [n] on %s" % (who, dev))
+
+
+def _check_state(who, state, dev):
+    if state is None:
+        return
+    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
+        raise ValueError("%s: state must be int64 [%d] on %s, or None" % (who, STATE_WORDS, dev))
+
+
+def _check_keep_device(who, kt, snap):
+    dev = kt.device
+    if dev is None or dev.type != "cuda":
+        raise ValueError("%s: the table is not on a GPU (%s_host is the CPU twin)" % (who, who))
+    if (snap.device != dev or snap.dtype != torch.float32 or snap.dim() != 1 or not snap.is_contiguous()
+            or snap.numel() != kt.snap_n):
+        raise ValueError("%s: the snapshot must be a contiguous float32 [%d] on %s" % (who, kt.snap_n, dev))
+    return dev
+
+
+def _check_keep_host(who, kt, snap):
+    if kt.device is not None:
+        raise ValueError("%s: the table is on a GPU" % who)
+    if snap.dtype != np.float32 or snap.ndim != 1 or snap.size != kt.snap_n or not snap.flags.c_contiguous:
+        raise ValueError("%s: the snapshot must be a contiguous float32 [%d]" % (who, kt.snap_n))
+
+
+def _host_state_ptr(who, state):
+    if state is None:
+        return None
+    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
+        raise ValueError("%s: state must be int64 [%d], or None" % (who, STATE_WORDS))
+    return _np_ptr(state)
+
+
+def ema(e, w, state, count, decay, warmup=True):
+    """One launch on the current stream: e <- d * e + (1 - d) * w for update k = count + (state: the updates applied so far),
+    d = min(decay, (1 + k) / (10 + k)) with `warmup`; nothing is stored when the latest `apply` skipped (include/x3dstep.h).
+    state: the monitor's int64 [STATE_WORDS], or None (count is then the number of updates, this one included)."""
+    dev = e.device
+    if dev.type != "cuda":
+        raise ValueError("ema: e is not on a GPU (ema_host is the CPU twin)")
+    _check_flat_pair("ema", e, w, dev)
+    _check_state("ema", state, dev)
+    check(_steplib.lib().x3dstep_ema(ptr(e), ptr(w), e.numel(), None if state is None else ptr(state), int(count),
+                                     _check_decay("ema", decay), 1 if warmup else 0, stream()))
+
+
+def ema_host(e, w, state, count, decay, warmup=True):
+    """The CPU twin of `ema` on numpy arrays (e is updated in place)."""
+    for a in (e, w):
+        if a.dtype != np.float32 or a.ndim != 1 or a.size != e.size or not a.flags.c_contiguous:
+            raise ValueError("ema_host: e and w must be contiguous float32 [n]")
+    check(_steplib.lib().x3dstep_ema_host(_np_ptr(e), _np_ptr(w), e.size, _host_state_ptr("ema_host", state), int(count),
+                                          float(decay), 1 if warmup else 0))
+
+
+def ema_keep(kt, esnap, state, count, decay, warmup=True):
+    """One launch: the rule of `ema` over the table's live buffers, into `esnap` (float32 [kt.snap_n], laid out as the
+    table's own snapshot; the padding past a buffer's length is left alone)."""
+    dev = _check_keep_device("ema_keep", kt, esnap)
+    _check_state("ema_keep", state, dev)
+    check(_steplib.lib().x3dstep_ema_keep(ptr(kt.d_table), kt.nbuf, ptr(kt.d_items), kt.nitems, ptr(esnap), kt.snap_n,
+                                          None if state is None else ptr(state), int(count),
+                                          _check_decay("ema_keep", decay), 1 if warmup else 0, stream()))
+
+
+def ema_keep_host(kt, esnap, state, count, decay, warmup=True):
+    """The CPU twin of `ema_keep` (a KeepTable of numpy arrays)."""
+    _check_keep_host("ema_keep_host", kt, esnap)
+    check(_steplib.lib().x3dstep_ema_keep_host(_np_ptr(kt.table), kt.nbuf, _np_ptr(kt.items), kt.nitems, _np_ptr(esnap),
+                                               kt.snap_n, _host_state_ptr("ema_keep_host", state), int(count),
+                                               float(decay), 1 if warmup else 0))
+
+
+def swap(a, b):
+    """One launch: exchange two flat float32 buffers in place, bit for bit."""
+    dev = a.device
+    if dev.type != "cuda":
+        raise ValueError("swap: a is not on a GPU (swap_host is the CPU twin)")
+    _check_flat_pair("swap", a, b, dev)
+    check(_steplib.lib().x3dstep_swap(ptr(a), ptr(b), a.numel(), stream()))
+
+
+def swap_host(a, b):
+    """The CPU twin of `swap`."""
+    for x in (a, b):
+        if x.dtype != np.float32 or x.ndim != 1 or x.size != a.size or not x.flags.c_contiguous or not x.flags.writeable:
+            raise ValueError("swap_host: a and b must be writeable contiguous float32 [n]")
+    check(_steplib.lib().x3dstep_swap_host(_np_ptr(a), _np_ptr(b), a.size))
+
+
+def swap_keep(kt, snap):
+    """One launch: exchange the table's live buffers with their ranges of `snap`, in place and bit for bit."""
+    _check_keep_device("swap_keep", kt, snap)
+    check(_steplib.lib().x3dstep_swap_keep(ptr(kt.d_table), kt.nbuf, ptr(kt.d_items), kt.nitems, ptr(snap), kt.snap_n,
+                                           stream()))
+
+
+def swap_keep_host(kt, snap):
+    """The CPU twin of `swap_keep`."""
+    _check_keep_host("swap_keep_host", kt, snap)
+    check(_steplib.lib().x3dstep_swap_keep_host(_np_ptr(kt.table), kt.nbuf, _np_ptr(kt.items), kt.nitems, _np_ptr(snap),
+                                                kt.snap_n))
+
+
 def aligned_bytes(nbytes, align=16):
     """A zeroed uint8 numpy array of nbytes whose address is a multiple of `align` (the tables of the twin are 8-byte
     aligned, g 16-byte aligned for the vector loads)."""

@@ -120,7 +120,8 @@ class Trainer:
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
-                 objective="ce", clip_grad_norm=None, monitor=False, skip_nonfinite=False):
+                 objective="ce", clip_grad_norm=None, monitor=False, skip_nonfinite=False, ema_decay=None,
+                 ema_warmup=True):
         """overlap: multi-rank steps are captured as two graphs around the first gradient bucket (False: single graph,
         all-reduce after the whole backward); force_split: the two-graph form on a single rank too (tests);
         force_collectives: all-reduce on a one-rank process group (the single-GPU RCCL test).  Round 4: constructor
@@ -155,6 +156,16 @@ class Trainer:
         momentum buffer of zeros, which gives the same values (fmaf(mu, 0, g) == g) and can differ only in the sign of a
         zero.  monitor.skipped() / skip_run() count on the device.  The snapshot and the counters are not optimizer state:
         state_dict() is unchanged.  Off (the default): not one launch is added.
+
+        ema_decay / ema_warmup: ema_decay = d in [0, 1) creates a weightema.WeightEMA (`self.ema`): an exponential moving
+        average of the flat parameters and of every split_bn.running_mean / running_var, updated by two launches after the
+        SGD kernel (on the guarded path: after `apply` and the restore), outside every graph, in every form of the step
+        (under accumulation on the updating call only; under data parallelism every rank averages the same weights, so
+        the averaged weights are the same bits on every rank, and each rank averages its own statistics).  ema_warmup: the
+        decay of update k is min(d, (1 + k) / (10 + k)).  With skip_nonfinite a skipped update leaves the average and its
+        count untouched; without the guard a non-finite update poisons the average for good.  `with trainer.ema.applied():`
+        exchanges the average with the live weights and statistics in place for validation.  The average is not part of
+        state_dict(): trainer.ema.state_dict() is its own.  None (the default): no attribute, not one launch.
 
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
@@ -195,6 +206,9 @@ class Trainer:
             ring = 64 if (monitor is True or not monitor) else int(monitor)
             self.monitor = GradMonitor(self.fp, [k for k, _ in model.named_parameters()], ring=ring,
                                        max_norm=clip_grad_norm, inv_world=1.0 / world_size)
+        if ema_decay is not None:
+            from .weightema import WeightEMA
+            self.ema = WeightEMA(self.fp, model, ema_decay, warmup=ema_warmup, monitor=getattr(self, "monitor", None))
 
     @property
     def lr(self):
@@ -295,24 +309,29 @@ class Trainer:
         from . import stepops
         ver = self.model._bn_version
         if self._keep is None or self._keep_version != ver:
-            bufs = []
-            for mod in self.model.modules():
-                sb = getattr(mod, "split_bn", None)
-                if sb is not None:
-                    bufs += [sb.running_mean, sb.running_var]
+            from .weightema import running_stat_buffers
             self._keep_old = self._keep
-            self._keep = stepops.KeepTable(bufs, self.fp.grad.device)
+            self._keep = stepops.KeepTable([b for _, b in running_stat_buffers(self.model)], self.fp.grad.device)
             self._keep_version = ver
         return self._keep
 
     def _keep_save(self):
         """Before the forward pass of an update's first micro-batch, outside every graph: the running statistics as they
         are now, whoever wrote them last."""
+        ema = getattr(self, "ema", None)
+        if ema is not None:
+            ema.sync_layout()                # a long-cycle switch: the average restarts from the statistics while fresh
         if self.skip_nonfinite:
             from . import _steplib, stepops
             stepops.keep(self._keep_table(), self.monitor.state, _steplib.KEEP_SAVE)
 
     def _sgd(self, grad=None):
+        self._update(grad)
+        ema = getattr(self, "ema", None)
+        if ema is not None:
+            ema.update()                     # two launches; a skipped update is left out on the device
+
+    def _update(self, grad=None):
         mon = getattr(self, "monitor", None)
         g = self.param_groups[0]
         if self.skip_nonfinite:
