@@ -247,6 +247,66 @@ int x3dstep_swap_keep(const X3DStepKeep* table, int nbuf, const X3DStepItem* ite
 int x3dstep_swap_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
                            int64_t snap_n);
 
+/*
+ * Precise BN statistics: the running statistics of batch normalisation recomputed over K batches, S splits and W ranks.
+ * A cell is one split of one batch on one rank: for a channel it has a mean mu and an unbiased variance v, which a forward
+ * pass in training mode with BN momentum 1 leaves in the live buffers (split j of channel c at [j * C + c]).  Over n cells
+ *     mean = sum mu / n,   var = sum v / n + sum (mu - mean)^2 / n
+ * computed in fp64, streaming, in a fixed order, every operation rounded once.  One accumulator per channel: four doubles
+ * {n, mean, m2, vsum} (X3DSTEP_PBN_ACC_DOUBLES; all zero before the first cell).
+ *   cell    n' = n + 1; d = mu - mean; mean' = mean + d / n'; m2' = m2 + d * (mu - mean'); vsum' = vsum + v
+ *   merge   of A then B (rank order): nB == 0 keeps A, nA == 0 takes B, otherwise n = nA + nB; d = meanB - meanA;
+ *           mean = meanA + d * (nB / n); m2 = (m2A + m2B) + (d * d) * (nA * nB / n); vsum = vsumA + vsumB
+ *   result  mean32 = (float) mean; var32 = (float) ((vsum + m2) / n); both a NaN when n != expect_n
+ * Tables (host builders below; the kernels read them from device memory)
+ *   layers  X3DStepPbnLayer [nlayers]: `first` of layer l is the sum of C over the layers before it, so the accumulator
+ *           array has x3dstep_pbn_build_layers' return value T channels: fp64 [4 * T], 8-byte aligned
+ *   work    X3DStepItem [nwork]: a layer cut into runs of at most X3DSTEP_PBN_RUN channels; seg: the layer, start: the run's
+ *           first channel in the accumulator array, len: its channels.  One workgroup per run, one thread per channel.
+ * Both launches: the grid comes from the tables alone, every output element is stored once, no atomics, no LDS, no
+ * allocation, no synchronisation: capturable.  A work item that fails the per-item tests (a null or unaligned address,
+ * C < 1, S < 1, a run outside its layer, a range outside snap) is not touched.  The twins refuse with X3DSTEP_EINVAL what
+ * the kernels leave out, and also ranges of snap that overlap a neighbour's and work items that overlap or are out of order.
+ */
+#define X3DSTEP_PBN_RUN 256
+#define X3DSTEP_PBN_ACC_DOUBLES 4
+#define X3DSTEP_PBN_MAX_CHANNELS (1 << 28)
+
+typedef struct {
+    int64_t mean_addr;  /* the live buffer of the means: the address of fp32 [S * C], 4-byte aligned, not null */
+    int64_t var_addr;   /* the live buffer of the variances, likewise */
+    int64_t mean_off;   /* the first element of the means' buffer in a keep table's snapshot */
+    int64_t var_off;    /* ... and of the variances' */
+    int64_t first;      /* the layer's first channel in the accumulator array */
+    int32_t C;          /* channels, >= 1 */
+    int32_t S;          /* splits, >= 1 */
+} X3DStepPbnLayer;
+
+size_t x3dstep_pbn_layer_bytes(void);
+
+/* Writes the layer table of a keep table whose buffers come in pairs (means, variances) of splits[l] * C_l elements each
+ * (host only, host pointers; nbuf == 2 * nlayers).  Returns the total number of channels T, or negative X3DSTEP_E*. */
+int64_t x3dstep_pbn_build_layers(const X3DStepKeep* table, int nbuf, const int32_t* splits, int nlayers,
+                                 X3DStepPbnLayer* layers);
+/* Runs the work table of these layers has; then the table itself (`cap`: items the caller allocated).  Host only. */
+int64_t x3dstep_pbn_work_count(const X3DStepPbnLayer* layers, int nlayers);
+int64_t x3dstep_pbn_build_work(const X3DStepPbnLayer* layers, int nlayers, X3DStepItem* work, int64_t cap);
+
+/* One cell update per split, splits in order j = 0 .. S - 1, for every channel: reads the live buffers, updates acc. */
+int x3dstep_pbn_accum(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork, double* acc,
+                      void* stream);
+int x3dstep_pbn_accum_host(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork, double* acc);
+
+/*
+ * Merges the W accumulators of every channel in rank order (acc_all: fp64 [W][4 * T], only read) and writes mean32 into
+ * all S slots of the layer's means in snap (fp32 [snap_n]) and var32 into all S slots of its variances.  What lies between
+ * the buffers in snap (padding) is not touched; the live buffers are neither read nor written.  expect_n >= 1.
+ */
+int x3dstep_pbn_finish(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
+                       const double* acc_all, int W, int64_t expect_n, float* snap, int64_t snap_n, void* stream);
+int x3dstep_pbn_finish_host(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
+                            const double* acc_all, int W, int64_t expect_n, float* snap, int64_t snap_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,13 +184,14 @@ def _rank_mean(values, process_group, world):
     return [float(x) / world for x in wire.cpu()]
 
 
-def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
+def _save_ckpt(model, optimizer, lr_sched, save_model, steps, pbn_ckpt=None):
     """The reference's checkpoint record (train_x3d_charades.py:203-207); with a weight average (Trainer(ema_decay=)) also
-    'ema_state_dict'."""
+    'ema_state_dict'; pbn_ckpt: the precise-BN records of the latest 'val' phase."""
     ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
             'scheduler_state_dict': lr_sched.state_dict()}
     if getattr(optimizer, 'ema', None) is not None:
         ckpt['ema_state_dict'] = optimizer.ema.state_dict()
+    ckpt.update(pbn_ckpt or {})
     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
     path = save_model + str(steps).zfill(6) + '.pt'
     torch.save(ckpt, path)
@@ -200,7 +201,7 @@ def _save_ckpt(model, optimizer, lr_sched, save_model, steps):
 def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
         device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -220,7 +221,14 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     statistics are rank 0's afterwards, as the live ones are; the live statistics are aggregated again after the block --
     and printed with the prefix EMA (the phase record gains
     'ema_map' and 'ema_loss'; the learning-rate schedule follows the live loss alone).  Checkpoints gain
-    'ema_state_dict', which `resume` restores when it is there (otherwise the average starts from the loaded weights)."""
+    'ema_state_dict', which `resume` restores when it is there (otherwise the average starts from the loaded weights).
+    precise_bn: K -- before every 'val' phase the BN statistics are recomputed over K training batches under the weights as
+    they are (x3dhip.precisebn: pooled over batches, splits and ranks on the GPU) and the phase is run once more with them
+    (line prefixed PBN, the record gains 'pbn_map' and 'pbn_loss'); with ema_decay the same inside
+    `optimizer.ema.applied()` (prefix EMA PBN, 'ema_pbn_map' and 'ema_pbn_loss').  The K batches are drawn with a generator
+    of their own: the training draws and every printed training loss are the same bits with and without it.  Checkpoints
+    gain 'precise_bn_state_dict' (and 'ema_precise_bn_state_dict') once a 'val' phase has run; nothing loads them: they are
+    derived data, recomputed at the next validation."""
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
     ddp = process_group is not None and world > 1
@@ -283,6 +291,43 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
 
     val_apm = APMeter(track_segments=ddp)
     tr_apm = APMeter(track_segments=ddp)
+    pbn_rng = random.Random(seed + 7919)         # the precise-BN batches never touch the training draws
+    pbn_ckpt = {}
+
+    def pbn_batches():
+        """precise_bn training batches of the global batch size, every rank its chunk, drawn with pbn_rng alone (the
+        same on every rank, as `rng` is)."""
+        for _ in range(precise_bn):
+            own, dataset.rng = dataset.rng, pbn_rng
+            try:
+                idx = [pbn_rng.randrange(len(dataset)) for _ in range(batch_size)]
+                if ddp:
+                    mine, params = _rank_share(dataset.draw, idx, rank, world)
+                    data = dataset.batch(mine, params=params)
+                else:
+                    data = dataset.batch(idx)
+            finally:
+                dataset.rng = own
+            yield data[0]
+
+    def pbn_phase(vb, key, prefix, tag):
+        """The 'val' phase once more on precise BN statistics of the weights as they are.  No broadcast of rank 0's
+        buffers here: after the all-gather inside compute() every rank holds the same pooled statistics."""
+        pbn = optimizer.precise_bn.compute(pbn_batches())
+        with pbn.applied():
+            gen = (val_dataset.test_batch(idx) for idx in (vb[rank::world] if ddp else vb))
+            res = (charades_eval.validate_loc if loc else charades_eval.validate_cls)(
+                x3d, gen, val_apm, **(dict(process_group=process_group) if ddp else {}))
+        pbn_ckpt[key] = pbn.state_dict()         # derived data: saved, never loaded
+        x3d.aggregate_sub_bn_stats()             # bn.* belong to the statistics outside the block again
+        val_apm.reset()
+        if loc:
+            say(' {} Epoch:{} {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                prefix, epochs, phase, res['loc_loss'], res['cls_loss'], res['loss'], res['map']))
+        else:
+            say(' {} Epoch:{} {} Loc Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
+                prefix, epochs, phase, res['cls_loss'], res['loss'], res['map']))
+        phases[-1].update({tag + 'map': res['map'], tag + 'loss': res['loss'] * len(vb) / num_steps_per_update})
     phases, checkpoints = [], []
     s_times = max(1, iterations_per_epoch // 2)
     zero = torch.zeros((), device=dev)
@@ -341,7 +386,7 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                             rec['losses'].append(float(tot_loss) / s_times)
                             tot_loss, tot_loc_loss, tot_cls_loss = zero.clone(), zero.clone(), zero.clone()
                         if save_every and steps % save_every == 0 and rank == 0:
-                            checkpoints.append(_save_ckpt(x3d, optimizer, lr_sched, save_model, steps))
+                            checkpoints.append(_save_ckpt(x3d, optimizer, lr_sched, save_model, steps, pbn_ckpt))
                     rec['steps'] = steps
                     phases.append(rec)
                 else:
@@ -366,6 +411,8 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                             epochs, phase, res['cls_loss'], (tot_loss * num_steps_per_update) / num_iter, val_map))
                     phases.append(dict(phase=phase, epoch=epochs, map=val_map, loss=tot_loss, rows=res['rows'],
                                        lr=optimizer.param_groups[0]['lr'], steps=steps))
+                    if precise_bn:
+                        pbn_phase(vb, 'precise_bn_state_dict', 'PBN', 'pbn_')
                     if ema is not None:
                         with ema.applied():              # the same phase on the averaged weights and statistics
                             if ddp:
@@ -382,6 +429,9 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                             say(' EMA Epoch:{} {} Loc Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}'.format(
                                 epochs, phase, res['cls_loss'], res['loss'], res['map']))
                         phases[-1].update(ema_map=res['map'], ema_loss=res['loss'] * num_iter / num_steps_per_update)
+                        if precise_bn:
+                            with ema.applied():          # the statistics of the averaged weights
+                                pbn_phase(vb, 'ema_precise_bn_state_dict', 'EMA PBN', 'ema_pbn_')
     finally:
         torch.cuda.synchronize()
         bad = mon.first_nonfinite() if mon is not None else None

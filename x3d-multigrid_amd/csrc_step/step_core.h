@@ -433,4 +433,131 @@ STEP_HD void swap_lane(const KeepCopy& c, int lane) {
     for (int j = 4 * groups + lane; j < c.len; j += kLanes) swap_one(a[j], b[j]);
 }
 
+// -- precise BN statistics (x3dstep_pbn_accum, x3dstep_pbn_finish) ---------------------------------------------------------
+// One accumulator per channel: the count of cells, the running mean of the cell means, the sum of squared deviations of
+// the cell means from it (Welford) and the sum of the cell variances.  fp64, every operation rounded once.
+struct PbnAcc {
+    double n, mean, m2, vsum;
+};
+
+// one cell: the mean and the unbiased variance of one split of one batch
+STEP_HD void pbn_cell(PbnAcc& a, float mu32, float v32) {
+    const double mu = (double)mu32;
+    const double v = (double)v32;
+    const double n1 = a.n + 1.0;
+    const double d = mu - a.mean;
+    const double q = d / n1;
+    const double mean1 = a.mean + q;
+    const double r = mu - mean1;
+    const double p = d * r;
+    a.m2 = a.m2 + p;
+    a.vsum = a.vsum + v;
+    a.mean = mean1;
+    a.n = n1;
+}
+
+// a <- a then b (the accumulators of two ranks, in rank order)
+STEP_HD void pbn_merge(PbnAcc& a, const PbnAcc& b) {
+    if (b.n == 0.0) return;
+    if (a.n == 0.0) {
+        a = b;
+        return;
+    }
+    const double n = a.n + b.n;
+    const double d = b.mean - a.mean;
+    const double f = b.n / n;
+    const double t = d * f;
+    const double dd = d * d;
+    const double ab = a.n * b.n;
+    const double g = ab / n;
+    const double u = dd * g;
+    const double s = a.m2 + b.m2;
+    a.mean = a.mean + t;
+    a.m2 = s + u;
+    a.vsum = a.vsum + b.vsum;
+    a.n = n;
+}
+
+// the pooled mean and variance, each rounded to fp32 once; NaN in both when the count is not the expected one
+STEP_HD void pbn_result(const PbnAcc& a, int64_t expect_n, float* mean32, float* var32) {
+    if (!(a.n == (double)expect_n)) {
+        uint32_t u = 0x7fc00000u;
+        float q;
+        memcpy(&q, &u, 4);
+        *mean32 = q;
+        *var32 = q;
+        return;
+    }
+    const double s = a.vsum + a.m2;
+    *mean32 = (float)a.mean;
+    *var32 = (float)(s / a.n);
+}
+
+// Work item i resolved against the layer table: the layer, the first channel within it, the count of channels (0: the
+// item is refused, nothing is touched) and the first accumulator.  The tests are those the twins refuse a call for; the
+// kernels make them per item, since the tables they read are device memory nobody has checked.  snap_n < 0: x3dstep_pbn_accum,
+// which does not touch the snapshot.
+struct PbnRun {
+    X3DStepPbnLayer layer;
+    int64_t c0, acc0;
+    int len;
+};
+
+STEP_HD int64_t pbn_channels(const X3DStepPbnLayer* layers, int nlayers) {
+    const X3DStepPbnLayer last = layers[nlayers - 1];
+    return last.first + (int64_t)last.C;
+}
+
+STEP_HD PbnRun pbn_resolve(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t i, int64_t snap_n) {
+    PbnRun r;
+    r.len = 0;
+    r.c0 = r.acc0 = 0;
+    const X3DStepItem it = work[i];
+    if (it.seg < 0 || it.seg >= nlayers || it.len < 1 || it.len > X3DSTEP_PBN_RUN) return r;
+    r.layer = layers[it.seg];
+    const X3DStepPbnLayer& L = r.layer;
+    if (L.mean_addr == 0 || L.var_addr == 0 || ((L.mean_addr | L.var_addr) & 3) != 0 || L.C < 1 || L.S < 1 || L.first < 0 ||
+        L.first > X3DSTEP_PBN_MAX_CHANNELS - L.C || it.start < L.first || it.start - L.first > (int64_t)L.C - it.len)
+        return r;
+    const int64_t total = pbn_channels(layers, nlayers);
+    if (total > X3DSTEP_PBN_MAX_CHANNELS || L.first + (int64_t)L.C > total) return r;
+    if (snap_n >= 0) {
+        const int64_t span = (int64_t)L.S * (int64_t)L.C;
+        if (L.mean_off < 0 || L.var_off < 0 || span > snap_n || L.mean_off > snap_n - span || L.var_off > snap_n - span)
+            return r;
+    }
+    r.c0 = it.start - L.first;
+    r.acc0 = it.start;
+    r.len = it.len;
+    return r;
+}
+
+// what the thread of channel c0 + t of a run does in x3dstep_pbn_accum: one cell update per split, splits in order
+STEP_HD void pbn_accum_one(const PbnRun& r, int t, double* acc) {
+    const float* mean = (const float*)(uintptr_t)r.layer.mean_addr;
+    const float* var = (const float*)(uintptr_t)r.layer.var_addr;
+    const int64_t c = r.c0 + t;
+    PbnAcc a = *(const PbnAcc*)(acc + 4 * (r.acc0 + t));
+    for (int j = 0; j < r.layer.S; ++j) {
+        const int64_t at = (int64_t)j * r.layer.C + c;
+        pbn_cell(a, mean[at], var[at]);
+    }
+    *(PbnAcc*)(acc + 4 * (r.acc0 + t)) = a;
+}
+
+// ... and in x3dstep_pbn_finish: the W accumulators of the channel merged in rank order, the result into all S slots
+STEP_HD void pbn_finish_one(const PbnRun& r, int t, const double* acc_all, int W, int64_t total, int64_t expect_n,
+                            float* snap) {
+    const int64_t c = r.c0 + t;
+    PbnAcc a = *(const PbnAcc*)(acc_all + 4 * (r.acc0 + t));
+    for (int w = 1; w < W; ++w) pbn_merge(a, *(const PbnAcc*)(acc_all + 4 * ((int64_t)w * total + r.acc0 + t)));
+    float m32, v32;
+    pbn_result(a, expect_n, &m32, &v32);
+    for (int j = 0; j < r.layer.S; ++j) {
+        const int64_t at = (int64_t)j * r.layer.C + c;
+        snap[r.layer.mean_off + at] = m32;
+        snap[r.layer.var_off + at] = v32;
+    }
+}
+
 }  // namespace x3ds

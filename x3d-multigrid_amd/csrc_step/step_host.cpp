@@ -393,3 +393,169 @@ extern "C" int x3dstep_swap_keep_host(const X3DStepKeep* table, int nbuf, const 
     }
     return X3DSTEP_OK;
 }
+
+// -- precise BN statistics ----------------------------------------------------------------------------------------------------
+extern "C" size_t x3dstep_pbn_layer_bytes(void) { return sizeof(X3DStepPbnLayer); }
+
+extern "C" int64_t x3dstep_pbn_build_layers(const X3DStepKeep* table, int nbuf, const int32_t* splits, int nlayers,
+                                            X3DStepPbnLayer* layers) {
+    if (!table || !splits || !layers || nlayers < 1 || nlayers > X3DSTEP_MAX_SEGMENTS / 2 || nbuf != 2 * nlayers) {
+        x3dstep_set_error("x3dstep_pbn_build_layers: null table, nlayers %d outside 1 .. %d or nbuf %d != 2 * nlayers", nlayers,
+                          X3DSTEP_MAX_SEGMENTS / 2, nbuf);
+        return X3DSTEP_EINVAL;
+    }
+    int64_t first = 0;
+    for (int l = 0; l < nlayers; ++l) {
+        const X3DStepKeep m = table[2 * l], v = table[2 * l + 1];
+        const int32_t S = splits[l];
+        if (S < 1 || m.len < 1 || m.len != v.len || m.len % S != 0 || first > X3DSTEP_PBN_MAX_CHANNELS - m.len / S) {
+            x3dstep_set_error("x3dstep_pbn_build_layers: layer %d: %d splits, buffers of %d and %d elements, or more than %d "
+                              "channels in all", l, S, m.len, v.len, X3DSTEP_PBN_MAX_CHANNELS);
+            return X3DSTEP_EINVAL;
+        }
+        X3DStepPbnLayer L;
+        L.mean_addr = m.addr;
+        L.var_addr = v.addr;
+        L.mean_off = m.offset;
+        L.var_off = v.offset;
+        L.first = first;
+        L.C = m.len / S;
+        L.S = S;
+        layers[l] = L;
+        first += L.C;
+    }
+    return first;
+}
+
+// counts (work == nullptr) or writes the work table; -1 when the layer table is refused
+static int64_t walk_work(const X3DStepPbnLayer* layers, int nlayers, X3DStepItem* work, int64_t cap) {
+    if (!layers || nlayers < 1 || nlayers > X3DSTEP_MAX_SEGMENTS) return -1;
+    int64_t count = 0, first = 0;
+    for (int l = 0; l < nlayers; ++l) {
+        const X3DStepPbnLayer L = layers[l];
+        if (L.C < 1 || L.first != first || first > X3DSTEP_PBN_MAX_CHANNELS - L.C) return -1;
+        for (int32_t at = 0; at < L.C; at += X3DSTEP_PBN_RUN) {
+            if (work) {
+                if (count >= cap) return -1;
+                work[count].start = first + at;
+                work[count].seg = l;
+                work[count].len = L.C - at < X3DSTEP_PBN_RUN ? L.C - at : X3DSTEP_PBN_RUN;
+            }
+            ++count;
+        }
+        first += L.C;
+    }
+    return count;
+}
+
+extern "C" int64_t x3dstep_pbn_work_count(const X3DStepPbnLayer* layers, int nlayers) {
+    const int64_t c = walk_work(layers, nlayers, nullptr, 0);
+    if (c < 0) {
+        x3dstep_set_error("x3dstep_pbn_work_count: null table, nlayers %d outside 1 .. %d, a layer with C < 1 or whose first "
+                          "channel is not the sum of C before it", nlayers, X3DSTEP_MAX_SEGMENTS);
+        return X3DSTEP_EINVAL;
+    }
+    return c;
+}
+
+extern "C" int64_t x3dstep_pbn_build_work(const X3DStepPbnLayer* layers, int nlayers, X3DStepItem* work, int64_t cap) {
+    if (!work || cap < 1) {
+        x3dstep_set_error("x3dstep_pbn_build_work: null table or no capacity");
+        return X3DSTEP_EINVAL;
+    }
+    const int64_t c = walk_work(layers, nlayers, work, cap);
+    if (c < 0) {
+        x3dstep_set_error("x3dstep_pbn_build_work: the layer table is refused (see x3dstep_pbn_work_count) or needs more than "
+                          "%lld items", (long long)cap);
+        return X3DSTEP_EINVAL;
+    }
+    return c;
+}
+
+// the argument checks the launches and their twins share (no pointer is followed: the tables may be device memory);
+// finish: snap, snap_n, W and expect_n are checked too
+int x3dstep_check_pbn(const char* who, const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
+                      const double* acc, bool finish, int W, int64_t expect_n, const float* snap, int64_t snap_n) {
+    if (!layers || !work || !acc || nlayers < 1 || nlayers > X3DSTEP_MAX_SEGMENTS || nwork < nlayers ||
+        nwork > X3DSTEP_MAX_ITEMS || (((uintptr_t)layers | (uintptr_t)work | (uintptr_t)acc) & 7) != 0) {
+        x3dstep_set_error("%s: null or unaligned pointer, nlayers %d outside 1 .. %d or nwork %lld outside nlayers .. %d", who,
+                          nlayers, X3DSTEP_MAX_SEGMENTS, (long long)nwork, X3DSTEP_MAX_ITEMS);
+        return X3DSTEP_EINVAL;
+    }
+    if (finish && (!snap || ((uintptr_t)snap & 3) != 0 || snap_n < 1 || W < 1 || W > 65536 || expect_n < 1)) {
+        x3dstep_set_error("%s: null or unaligned snap, snap_n %lld < 1, W %d outside 1 .. 65536 or expect_n %lld < 1", who,
+                          (long long)snap_n, W, (long long)expect_n);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+// The tables are host memory in a twin: refuse the call for what the kernel would leave out item by item, and for what
+// would make two threads store the same element.
+static int pbn_host_ok(const char* who, const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
+                       int64_t snap_n) {
+    using namespace x3ds;
+    int64_t first = 0, end = 0;
+    for (int l = 0; l < nlayers; ++l) {
+        const X3DStepPbnLayer L = layers[l];
+        if (L.mean_addr == 0 || L.var_addr == 0 || ((L.mean_addr | L.var_addr) & 3) != 0 || L.C < 1 || L.S < 1) {
+            x3dstep_set_error("%s: layer %d: a null or unaligned address, C %d < 1 or S %d < 1", who, l, L.C, L.S);
+            return X3DSTEP_EINVAL;
+        }
+        if (L.first != first || first > X3DSTEP_PBN_MAX_CHANNELS - L.C) {
+            x3dstep_set_error("%s: layer %d: its first channel is not the sum of C before it, or more than %d channels", who, l,
+                              X3DSTEP_PBN_MAX_CHANNELS);
+            return X3DSTEP_EINVAL;
+        }
+        first += L.C;
+        if (snap_n >= 0) {
+            const int64_t span = (int64_t)L.S * (int64_t)L.C;
+            if (span > snap_n || L.mean_off < end || L.mean_off > snap_n - span || L.var_off < L.mean_off + span ||
+                L.var_off > snap_n - span) {
+                x3dstep_set_error("%s: layer %d: a range outside snap or over the range before it", who, l);
+                return X3DSTEP_EINVAL;
+            }
+            end = L.var_off + span;
+        }
+    }
+    int64_t next = 0;
+    for (int64_t i = 0; i < nwork; ++i) {
+        const PbnRun r = pbn_resolve(layers, nlayers, work, i, snap_n);
+        if (r.len < 1 || work[i].start < next) {
+            x3dstep_set_error("%s: work item %lld lies outside its layer or over the item before it", who, (long long)i);
+            return X3DSTEP_EINVAL;
+        }
+        next = work[i].start + work[i].len;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_pbn_accum_host(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
+                                      double* acc) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_pbn("x3dstep_pbn_accum_host", layers, nlayers, work, nwork, acc, false, 1, 1, nullptr, 0);
+    if (rc) return rc;
+    const int rt = pbn_host_ok("x3dstep_pbn_accum_host", layers, nlayers, work, nwork, -1);
+    if (rt) return rt;
+    for (int64_t i = 0; i < nwork; ++i) {
+        const PbnRun r = pbn_resolve(layers, nlayers, work, i, -1);
+        for (int t = 0; t < r.len; ++t) pbn_accum_one(r, t, acc);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_pbn_finish_host(const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
+                                       const double* acc_all, int W, int64_t expect_n, float* snap, int64_t snap_n) {
+    using namespace x3ds;
+    const int rc = x3dstep_check_pbn("x3dstep_pbn_finish_host", layers, nlayers, work, nwork, acc_all, true, W, expect_n, snap,
+                                     snap_n);
+    if (rc) return rc;
+    const int rt = pbn_host_ok("x3dstep_pbn_finish_host", layers, nlayers, work, nwork, snap_n);
+    if (rt) return rt;
+    const int64_t total = pbn_channels(layers, nlayers);
+    for (int64_t i = 0; i < nwork; ++i) {
+        const PbnRun r = pbn_resolve(layers, nlayers, work, i, snap_n);
+        for (int t = 0; t < r.len; ++t) pbn_finish_one(r, t, acc_all, W, total, expect_n, snap);
+    }
+    return X3DSTEP_OK;
+}

@@ -40,7 +40,7 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
     every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
@@ -57,7 +57,7 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
                               world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor,
                               skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
-                              ema_warmup=ema_warmup)
+                              ema_warmup=ema_warmup, precise_bn=precise_bn)
 
 
 def init_distributed():
@@ -122,6 +122,10 @@ def main(run_fn, default_save):
                              'ema_state_dict (off by default)')
     parser.add_argument('--no-ema-warmup', action='store_true',
                         help='with --ema-decay: use D from the first update on instead of min(D, (1 + k) / (10 + k))')
+    parser.add_argument('--precise-bn', type=int, default=None, metavar='K',
+                        help='before every validation recompute the BN statistics over K training batches on the GPU and '
+                             'validate once more with them (a line prefixed PBN; with --ema-decay also EMA PBN); checkpoints '
+                             'gain precise_bn_state_dict (off by default)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -139,7 +143,7 @@ def main(run_fn, default_save):
                use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,
                rank=rank, world=world, clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False,
                skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, ema_decay=args.ema_decay,
-               ema_warmup=not args.no_ema_warmup, **size)
+               ema_warmup=not args.no_ema_warmup, precise_bn=args.precise_bn, **size)
     finally:
         if pg is not None:
             import torch.distributed as dist

@@ -170,13 +170,14 @@ def val_line(res):
                                                                           res['videos'])
 
 
-def _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps):
+def _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps, pbn_ckpt=None):
     """The reference's checkpoint record (train_x3d_kinetics_multigrid.py:286-291); with a weight average
-    (Trainer(ema_decay=)) also 'ema_state_dict'."""
+    (Trainer(ema_decay=)) also 'ema_state_dict'; pbn_ckpt: the precise-BN records of the latest validation."""
     ckpt = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
             'scheduler_state_dict': lr_sched.state_dict(), 'long_ind': long_ind}
     if getattr(optimizer, 'ema', None) is not None:
         ckpt['ema_state_dict'] = optimizer.ema.state_dict()
+    ckpt.update(pbn_ckpt or {})
     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
     torch.save(ckpt, save_model + str(steps).zfill(6) + '.pt')
 
@@ -205,7 +206,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
         frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8,
-        ema_decay=None, ema_warmup=True):
+        ema_decay=None, ema_warmup=True, precise_bn=None):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -228,7 +229,14 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     running statistics on the GPU.  Every validation is then run a second time inside `optimizer.ema.applied()` (the
     aggregation of the statistics included; the live ones are aggregated again afterwards, so that bn.* in a checkpoint are
     the live model's) and printed with the prefix EMA; checkpoints gain 'ema_state_dict', which
-    load_ckpt restores when it is there (otherwise the average starts from the loaded weights)."""
+    load_ckpt restores when it is there (otherwise the average starts from the loaded weights).
+    precise_bn: K -- before every validation the BN statistics are recomputed over K training batches at the current long
+    cycle's base shape under the weights as they are (x3dhip.precisebn: pooled over batches, splits and ranks on the GPU), and
+    the validation is run once more with them, printed with the prefix PBN; with ema_decay the same inside
+    `optimizer.ema.applied()`: the statistics of the averaged weights, prefix EMA PBN.  The K batches come from a generator
+    of their own, so the training draws -- and every printed training loss -- are the same bits with and without it.
+    Checkpoints gain 'precise_bn_state_dict' (and 'ema_precise_bn_state_dict'); nothing loads them: they are derived data,
+    recomputed at the next validation."""
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -290,6 +298,9 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
 
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
+    pbn_gen = torch.Generator(device=dev)        # the precise-BN batches never touch the training draws
+    pbn_gen.manual_seed(987654 + rank)
+    pbn_state, pbn_ckpt = {}, {}
     folder_ds = tasks = sampler = None
     if frames_root is not None:
         import random
@@ -331,6 +342,30 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                     val_crops, sharded=(rank, world))
         else:
             val_ds = val_frames
+
+    def pbn_batches():
+        """precise_bn training batches at the current long cycle's base shape (the short cycle's last task: batch
+        multiplier 1, the full crop), drawn with generators of their own."""
+        import random
+        base_task = 1 if long_ind in (0, 1) else 2
+        Tb, Hb = cbs.step_clip_shape(long_ind, base_task, frames, gamma_tau)
+        if clip_size is not None:
+            Hb = max(8, Hb * clip_size // {'S': 160, 'M': 224, 'XL': 312, 'L': 312}[x3d_version])
+        Bb = batch_size * LONG_CYCLE[long_ind] // world
+        if 'rng' not in pbn_state:
+            pbn_state['rng'], pbn_state['sampler'] = random.Random(8765 + rank), random.Random(5678 + rank)
+        for _ in range(precise_bn):
+            if folder_ds is None:
+                yield device_batch(Bb, Tb, Hb, 400, dev, pbn_gen)[0]
+            else:
+                picks = [pbn_state['sampler'].randrange(len(folder_ds)) for _ in range(Bb)]
+                own, folder_ds.rng = folder_ds.rng, pbn_state['rng']
+                try:
+                    xb = folder_ds.batch(picks, base_task, long_ind)[0]
+                finally:
+                    folder_ds.rng = own
+                yield xb
+
     tot_loss = tot_corr = tot_dat = 0.0
     t0 = time.time()
     clips = 0
@@ -388,41 +423,51 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                     print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s{}'.format(
                         steps, long_ind, B, T, H, tot_loss, acc, optimizer.param_groups[0]['lr'], clips / dt, gline),
                         flush=True)
-            if val_every and done % val_every == 0 and val_ds is not None:
-                res = validate_topk(model, val_ds.batches(val_batch_size, rank, world), process_group=pg)
-                model.train(True)                                   # train...:199-200
-                if rank == 0:
-                    print(' val after step {}: {}'.format(steps, val_line(res)), flush=True)
+            if val_every and done % val_every == 0:
+                if val_ds is not None:
+                    def score():
+                        return val_line(validate_topk(model, val_ds.batches(val_batch_size, rank, world), process_group=pg))
+                else:
+                    Tv, Hv = frames // gamma_tau, crop_size
+                    vb = []
+                    for _ in range(val_batches):
+                        xv, yv = device_batch(val_batch_size * val_crops, Tv, Hv, 400, dev, gen)
+                        vb.append((xv.view(val_batch_size, val_crops, 3, Tv, Hv, Hv), yv.view(-1)[:val_batch_size]))
+
+                    def score():
+                        return 'Cls Loss: {:.4f} Acc: {:.4f} ({} videos)'.format(*validate(model, vb))
+
+                def report(prefix, line):
+                    if prefix:
+                        model.aggregate_sub_bn_stats()              # bn.* belong to the live statistics again
+                    model.train(True)                               # train...:199-200
+                    if rank == 0:
+                        print(' {}val after step {}: {}'.format(prefix, steps, line), flush=True)
+
+                def score_pbn(key):
+                    # K training batches under the weights as they are now; after the all-gather every rank holds the same
+                    # pooled statistics
+                    pbn = optimizer.precise_bn.compute(pbn_batches())
+                    with pbn.applied():
+                        line = score()
+                    pbn_ckpt[key] = pbn.state_dict()                # derived data: saved, never loaded
+                    return line
+
+                report('', score())
+                if precise_bn:
+                    report('PBN ', score_pbn('precise_bn_state_dict'))
                 if ema is not None:
                     with ema.applied():                             # each rank scores its shard with its own statistics
-                        res = validate_topk(model, val_ds.batches(val_batch_size, rank, world), process_group=pg)
-                    model.aggregate_sub_bn_stats()                  # bn.* belong to the live statistics again
-                    model.train(True)
-                    if rank == 0:
-                        print(' EMA val after step {}: {}'.format(steps, val_line(res)), flush=True)
-            elif val_every and done % val_every == 0:
-                Tv, Hv = frames // gamma_tau, crop_size
-                vb = []
-                for _ in range(val_batches):
-                    xv, yv = device_batch(val_batch_size * val_crops, Tv, Hv, 400, dev, gen)
-                    vb.append((xv.view(val_batch_size, val_crops, 3, Tv, Hv, Hv), yv.view(-1)[:val_batch_size]))
-                v_loss, v_acc, v_seen = validate(model, vb)
-                model.train(True)                                   # train...:199-200
-                if rank == 0:
-                    print(' val after step {}: Cls Loss: {:.4f} Acc: {:.4f} ({} videos)'.format(steps, v_loss, v_acc, v_seen),
-                          flush=True)
-                if ema is not None:
-                    with ema.applied():
-                        v_loss, v_acc, v_seen = validate(model, vb)
-                    model.aggregate_sub_bn_stats()                  # bn.* belong to the live statistics again
-                    model.train(True)
-                    if rank == 0:
-                        print(' EMA val after step {}: Cls Loss: {:.4f} Acc: {:.4f} ({} videos)'.format(
-                            steps, v_loss, v_acc, v_seen), flush=True)
+                        line = score()
+                    report('EMA ', line)
+                    if precise_bn:
+                        with ema.applied():                         # the statistics of the averaged weights
+                            line = score_pbn('ema_precise_bn_state_dict')
+                        report('EMA PBN ', line)
             if save_every and steps % save_every == 0 and rank == 0:
-                _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps)
+                _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps, pbn_ckpt)
         if save_every and rank == 0 and steps >= total_steps and done > 0 and steps % save_every != 0:
-            _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps)     # end of the schedule: final checkpoint
+            _save_ckpt(model, optimizer, lr_sched, long_ind, save_model, steps, pbn_ckpt)     # end of the schedule: final checkpoint
     finally:
         # runs on errors too: a rank that raised must not leave the others waiting inside a collective
         torch.cuda.synchronize()
@@ -492,6 +537,10 @@ if __name__ == '__main__':
                              'ema_state_dict (off by default)')
     parser.add_argument('--no-ema-warmup', action='store_true',
                         help='with --ema-decay: use D from the first update on instead of min(D, (1 + k) / (10 + k))')
+    parser.add_argument('--precise-bn', type=int, default=None, metavar='K',
+                        help='before every validation recompute the BN statistics over K training batches on the GPU and '
+                             'validate once more with them (lines prefixed PBN; with --ema-decay also EMA PBN); checkpoints '
+                             'gain precise_bn_state_dict (off by default)')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -520,4 +569,5 @@ if __name__ == '__main__':
         act_dtype=torch.bfloat16 if args.bf16 else torch.float32, frames_root=frames_root, val_every=args.val_every,
         val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames,
         clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, skip_nonfinite=args.skip_nonfinite,
-        max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup)
+        max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
+        precise_bn=args.precise_bn)

@@ -24,9 +24,13 @@ KEEP_SAVE, KEEP_RESTORE = 0, 1
 STATE_WORDS = 8
 MAX_SEGMENTS = 1 << 20
 MAX_ITEMS = 0x7fffff00
+PBN_RUN = 256
+PBN_ACC_DOUBLES = 4
 
 ITEM_DT = np.dtype([("start", "<i8"), ("seg", "<i4"), ("len", "<i4")])
 KEEP_DT = np.dtype([("addr", "<i8"), ("offset", "<i8"), ("len", "<i4"), ("pad", "<i4")])
+PBN_LAYER_DT = np.dtype([("mean_addr", "<i8"), ("var_addr", "<i8"), ("mean_off", "<i8"), ("var_off", "<i8"), ("first", "<i8"),
+                         ("C", "<i4"), ("S", "<i4")])
 HEADER_DT = np.dtype([("step", "<i8"), ("total", "<f8"), ("norm", "<f8"), ("coef", "<f4"), ("nonfinite", "<i4"),
                       ("first_bad", "<i4"), ("nseg", "<i4")])
 
@@ -65,6 +69,14 @@ SIGNATURES = {
     "x3dstep_swap_host": (_I, [_P, _P, _L]),
     "x3dstep_swap_keep": (_I, [_P, _I, _P, _L, _P, _L, _P]),
     "x3dstep_swap_keep_host": (_I, [_P, _I, _P, _L, _P, _L]),
+    "x3dstep_pbn_layer_bytes": (_Z, []),
+    "x3dstep_pbn_build_layers": (_L, [_P, _I, _P, _I, _P]),
+    "x3dstep_pbn_work_count": (_L, [_P, _I]),
+    "x3dstep_pbn_build_work": (_L, [_P, _I, _P, _L]),
+    "x3dstep_pbn_accum": (_I, [_P, _I, _P, _L, _P, _P]),
+    "x3dstep_pbn_accum_host": (_I, [_P, _I, _P, _L, _P]),
+    "x3dstep_pbn_finish": (_I, [_P, _I, _P, _L, _P, _I, _L, _P, _L, _P]),
+    "x3dstep_pbn_finish_host": (_I, [_P, _I, _P, _L, _P, _I, _L, _P, _L]),
 }
 
 _lib = None

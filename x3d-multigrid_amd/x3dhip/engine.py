@@ -139,17 +139,19 @@ def _bn_tensors(bn):
     return bn.weight.data, bn.bias.data, bn.split_bn.running_mean, bn.split_bn.running_var
 
 
-def _bn_train(partial, bn, S, count, want_nsum=False):
-    return ops.bn_fwd_finalize(partial, S, count, *_bn_tensors(bn), BN_MOMENTUM, BN_EPS, want_nsum=want_nsum)
+def _bn_train(partial, bn, S, count, want_nsum=False, momentum=BN_MOMENTUM):
+    return ops.bn_fwd_finalize(partial, S, count, *_bn_tensors(bn), momentum, BN_EPS, want_nsum=want_nsum)
 
 
 def _bn_eval(bn, N):
     return ops.bn_eval_coef(bn.bn.running_mean, bn.bn.running_var, bn.weight.data, bn.bias.data, N, BN_EPS)
 
 
-def trunk_forward(model, x, training, ctx=None):
+def trunk_forward(model, x, training, ctx=None, bn_momentum=BN_MOMENTUM):
     """x: float32 [N,3,T,H,W] on the GPU.  Returns pooled features [N, C5] (task 'class') or [N, C5, T] (task 'loc',
-    x3d.py:241) -- the input of the head's fc1 (x3d.py:331-333).  ctx (TrunkContext) collects what backward needs."""
+    x3d.py:241) -- the input of the head's fc1 (x3d.py:331-333).  ctx (TrunkContext) collects what backward needs.
+    bn_momentum: the momentum of every running-statistics update of a training-mode pass (x3dhip.precisebn passes 1.0:
+    the pass then leaves each split's own mean and unbiased variance in split_bn.running_*)."""
     N, _, T, H, W = x.shape
     S = model.bn1.num_splits
     packs = weight_packs(model)
@@ -162,7 +164,7 @@ def trunk_forward(model, x, training, ctx=None):
     a_t, part = ops.dw5t_fwd(a_s, model.conv1_t.weight.data, want_stats=training)
     P = a_t[0, 0].numel()
     if training:
-        c0, save0, _ = _bn_train(part, model.bn1, S, P)
+        c0, save0, _ = _bn_train(part, model.bn1, S, P, momentum=bn_momentum)
     else:
         c0, save0 = _bn_eval(model.bn1, N), None
     if ctx is not None:
@@ -171,14 +173,15 @@ def trunk_forward(model, x, training, ctx=None):
     cur_raw, cur_coef = a_t, c0          # lazy: consumers apply relu(c0 * a_t)
     for layer in (model.layer1, model.layer2, model.layer3, model.layer4):
         for blk in layer:
-            cur_raw, cur_coef = _block_forward(blk, cur_raw, cur_coef, S, training, ctx, packs, wide_dtype(model))
+            cur_raw, cur_coef = _block_forward(blk, cur_raw, cur_coef, S, training, ctx, packs, wide_dtype(model),
+                                               bn_momentum)
 
     # ---- conv5 / bn5 / relu / global average pool
     w5 = _w2d(model.conv5.weight)
     a5, p5 = ops.pw_fwd(cur_raw, w5, want_stats=training, wp=packs.get(model.conv5.weight))
     P5 = a5[0, 0].numel()
     if training:
-        c5, save5, _ = _bn_train(p5, model.bn5, S, P5)
+        c5, save5, _ = _bn_train(p5, model.bn5, S, P5, momentum=bn_momentum)
     else:
         c5, save5 = _bn_eval(model.bn5, N), None
     pooled = ops.bn_relu_pool_fwd(a5, c5, per_frame=getattr(model, "task", "class") == "loc")
@@ -198,7 +201,7 @@ def wide_dtype(model):
     return dt
 
 
-def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float32):
+def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float32, bn_momentum=BN_MOMENTUM):
     N = x_raw.shape[0]
     pre_act = ACT_RELU if x_coef is not None else ACT_NONE
     stride = blk.stride
@@ -210,10 +213,10 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
     if training and not cfg.no_dw_stats:
         # bn1's finalize runs inside the depthwise kernel's prologue (one launch less per block)
         a2, p2, c1, s1 = ops.dw333_fwd_stats(a1, blk.conv2.weight.data, p1, S, P1, *_bn_tensors(blk.bn1),
-                                             stride=stride, pre_act=ACT_RELU, momentum=BN_MOMENTUM, eps=BN_EPS)
+                                             stride=stride, pre_act=ACT_RELU, momentum=bn_momentum, eps=BN_EPS)
     else:
         if training:
-            c1, s1, _ = _bn_train(p1, blk.bn1, S, P1)
+            c1, s1, _ = _bn_train(p1, blk.bn1, S, P1, momentum=bn_momentum)
         else:
             c1, s1 = _bn_eval(blk.bn1, N), None
         a2, p2 = ops.dw333_fwd(a1, blk.conv2.weight.data, stride=stride, pre=c1, pre_act=ACT_RELU,
@@ -225,11 +228,11 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
         # bn2's finalize and the SE branch in one launch (round 4)
         c2e, s2, nsum2, se_v, z, pool = ops.se_bn_fwd(p2, S, P2, *_bn_tensors(blk.bn2), _w2d(blk.fc1.weight),
                                                       blk.fc1.bias.data, _w2d(blk.fc2.weight), blk.fc2.bias.data,
-                                                      BN_MOMENTUM, BN_EPS)
+                                                      bn_momentum, BN_EPS)
         se = dict(se=se_v, z=z, pool=pool, nsum=nsum2)
     else:
         if training:
-            c2, s2, nsum2 = _bn_train(p2, blk.bn2, S, P2, want_nsum=blk.has_se)
+            c2, s2, nsum2 = _bn_train(p2, blk.bn2, S, P2, want_nsum=blk.has_se, momentum=bn_momentum)
         else:
             c2, s2 = _bn_eval(blk.bn2, N), None
             if blk.has_se:
@@ -250,7 +253,7 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
         ad, pd = ops.pw_fwd(x_raw, wd, stride=stride, pre=x_coef, pre_act=pre_act, want_stats=training,
                             wp=packs.get(blk.downsample[0].weight))
         if training:
-            cd, sd, _ = _bn_train(pd, blk.downsample[1], S, P2)
+            cd, sd, _ = _bn_train(pd, blk.downsample[1], S, P2, momentum=bn_momentum)
         else:
             cd, sd = _bn_eval(blk.downsample[1], N), None
         res, rcoef = ad, cd
@@ -260,7 +263,7 @@ def _block_forward(blk, x_raw, x_coef, S, training, ctx, packs, wide=torch.float
         res, rcoef = x_raw, None
     if training:
         out, s3 = ops.bn_stats_add_relu_fwd(a3, p3, S, P2, *_bn_tensors(blk.bn3), res, rcoef,
-                                            momentum=BN_MOMENTUM, eps=BN_EPS)
+                                            momentum=bn_momentum, eps=BN_EPS)
     else:
         out = ops.bn_add_relu_fwd(a3, c3, res, rcoef)
     if ctx is not None:

@@ -356,6 +356,92 @@ def swap_keep_host(kt, snap):
                                                 kt.snap_n))
 
 
+class PbnTable:
+    """The tables `pbn_accum` / `pbn_finish` take, built by the library from a KeepTable whose buffers come in pairs
+    (split_bn.running_mean, split_bn.running_var) and the number of splits of each pair: the layer table (where the live
+    buffers are, where they lie in the keep table's snapshot, C, S and the layer's first channel in the accumulator array)
+    and the work table (runs of at most PBN_RUN channels).  `channels`: the accumulator array has 4 * channels doubles."""
+
+    def __init__(self, kt, splits):
+        splits = np.ascontiguousarray(splits, dtype=np.int32).reshape(-1)
+        if kt.nbuf != 2 * splits.size or splits.size < 1:
+            raise ValueError("PbnTable: %d buffers for %d layers (a mean and a variance buffer each)" % (kt.nbuf, splits.size))
+        L = _steplib.lib()
+        assert L.x3dstep_pbn_layer_bytes() == _steplib.PBN_LAYER_DT.itemsize
+        self.kt, self.device, self.snap_n = kt, kt.device, kt.snap_n
+        self.nlayers = int(splits.size)
+        self.layers = np.zeros(self.nlayers, dtype=_steplib.PBN_LAYER_DT)
+        self.channels = int(check(L.x3dstep_pbn_build_layers(_np_ptr(kt.table), kt.nbuf, _np_ptr(splits), self.nlayers,
+                                                             _np_ptr(self.layers))))
+        n = check(L.x3dstep_pbn_work_count(_np_ptr(self.layers), self.nlayers))
+        self.work = np.zeros(n, dtype=ITEM_DT)
+        assert check(L.x3dstep_pbn_build_work(_np_ptr(self.layers), self.nlayers, _np_ptr(self.work), n)) == n
+        self.nwork = int(n)
+        if self.device is not None:
+            self.d_layers = torch.from_numpy(self.layers.view(np.uint8).copy()).to(self.device)
+            self.d_work = torch.from_numpy(self.work.view(np.uint8).copy()).to(self.device)
+
+    def new_acc(self, W=1):
+        """Zeroed accumulators of W ranks: float64 [W * 4 * channels] (a torch tensor on the table's device, or numpy)."""
+        n = int(W) * _steplib.PBN_ACC_DOUBLES * self.channels
+        if self.device is None:
+            return aligned_bytes(8 * n).view(np.float64)
+        return torch.zeros(n, dtype=torch.float64, device=self.device)
+
+
+def _check_pbn_device(who, pt, acc, W):
+    dev = pt.device
+    if dev is None or dev.type != "cuda":
+        raise ValueError("%s: the table is not on a GPU (%s_host is the CPU twin)" % (who, who))
+    need = int(W) * _steplib.PBN_ACC_DOUBLES * pt.channels
+    if (not isinstance(acc, torch.Tensor) or acc.device != dev or acc.dtype != torch.float64 or acc.dim() != 1
+            or not acc.is_contiguous() or acc.numel() != need or W < 1):
+        raise ValueError("%s: the accumulators must be a contiguous float64 [%d] on %s" % (who, need, dev))
+    return dev
+
+
+def _check_pbn_host(who, pt, acc, W):
+    if pt.device is not None:
+        raise ValueError("%s: the table is on a GPU" % who)
+    need = int(W) * _steplib.PBN_ACC_DOUBLES * pt.channels
+    if acc.dtype != np.float64 or acc.ndim != 1 or acc.size != need or not acc.flags.c_contiguous or W < 1:
+        raise ValueError("%s: the accumulators must be a contiguous float64 [%d]" % (who, need))
+
+
+def pbn_accum(pt, acc):
+    """One launch on the current stream: one cell update per split for every channel, from the table's live buffers (which
+    a forward pass with BN momentum 1 just wrote) into acc (float64 [4 * channels]: {n, mean, m2, vsum} per channel)."""
+    _check_pbn_device("pbn_accum", pt, acc, 1)
+    check(_steplib.lib().x3dstep_pbn_accum(ptr(pt.d_layers), pt.nlayers, ptr(pt.d_work), pt.nwork, ptr(acc), stream()))
+
+
+def pbn_accum_host(pt, acc):
+    """The CPU twin of `pbn_accum` (a PbnTable over a KeepTable of numpy arrays)."""
+    _check_pbn_host("pbn_accum_host", pt, acc, 1)
+    check(_steplib.lib().x3dstep_pbn_accum_host(_np_ptr(pt.layers), pt.nlayers, _np_ptr(pt.work), pt.nwork, _np_ptr(acc)))
+
+
+def pbn_finish(pt, acc_all, W, expect_n, snap):
+    """One launch: the W accumulators of every channel (acc_all float64 [W * 4 * channels], rank after rank) merged in rank
+    order, the pooled mean and variance written into all S slots of the layer's buffers in `snap` (float32 [snap_n], laid
+    out as the keep table's snapshot; the padding is left alone); NaN where the merged count is not expect_n."""
+    dev = _check_pbn_device("pbn_finish", pt, acc_all, W)
+    if (snap.device != dev or snap.dtype != torch.float32 or snap.dim() != 1 or not snap.is_contiguous()
+            or snap.numel() != pt.snap_n):
+        raise ValueError("pbn_finish: the snapshot must be a contiguous float32 [%d] on %s" % (pt.snap_n, dev))
+    check(_steplib.lib().x3dstep_pbn_finish(ptr(pt.d_layers), pt.nlayers, ptr(pt.d_work), pt.nwork, ptr(acc_all), int(W),
+                                            int(expect_n), ptr(snap), pt.snap_n, stream()))
+
+
+def pbn_finish_host(pt, acc_all, W, expect_n, snap):
+    """The CPU twin of `pbn_finish`."""
+    _check_pbn_host("pbn_finish_host", pt, acc_all, W)
+    if snap.dtype != np.float32 or snap.ndim != 1 or snap.size != pt.snap_n or not snap.flags.c_contiguous:
+        raise ValueError("pbn_finish_host: the snapshot must be a contiguous float32 [%d]" % pt.snap_n)
+    check(_steplib.lib().x3dstep_pbn_finish_host(_np_ptr(pt.layers), pt.nlayers, _np_ptr(pt.work), pt.nwork, _np_ptr(acc_all),
+                                                 int(W), int(expect_n), _np_ptr(snap), pt.snap_n))
+
+
 def aligned_bytes(nbytes, align=16):
     """A zeroed uint8 numpy array of nbytes whose address is a multiple of `align` (the tables of the twin are 8-byte
     aligned, g 16-byte aligned for the vector loads)."""

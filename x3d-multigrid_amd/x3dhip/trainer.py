@@ -167,6 +167,13 @@ class Trainer:
         exchanges the average with the live weights and statistics in place for validation.  The average is not part of
         state_dict(): trainer.ema.state_dict() is its own.  None (the default): no attribute, not one launch.
 
+        `trainer.precise_bn` is a precisebn.PreciseBN over this model and process group, made on first use:
+        `trainer.precise_bn.compute(batches)` recomputes the BN statistics over K training batches under the weights as they
+        are (inside `ema.applied()`: the averaged ones), pooled over batches, splits and ranks, and
+        `with trainer.precise_bn.applied():` exchanges them with the live statistics for validation.  Until it is first
+        used there is no attribute (`'precise_bn' in vars(trainer)`; `hasattr` would make it) and not one launch, and
+        state_dict() is the same either way.
+
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
         afterwards is not part of the flat buffers and would not be trained."""
@@ -209,6 +216,14 @@ class Trainer:
         if ema_decay is not None:
             from .weightema import WeightEMA
             self.ema = WeightEMA(self.fp, model, ema_decay, warmup=ema_warmup, monitor=getattr(self, "monitor", None))
+
+    def __getattr__(self, name):
+        # only reached when the attribute is missing: precise_bn is made on first use
+        if name == "precise_bn":
+            from .precisebn import PreciseBN
+            self.precise_bn = PreciseBN(self.model, self.pg)
+            return self.precise_bn
+        raise AttributeError("%s object has no attribute %r" % (type(self).__name__, name))
 
     @property
     def lr(self):
