@@ -186,6 +186,50 @@ int x3dstep_apply_host(float* w, const float* g, float* m, int64_t n, int64_t* s
                        float momentum, float weight_decay, float grad_scale, int first);
 
 /*
+ * The grouped update: x3dstep_apply with a learning-rate scale and a weight-decay scale per tensor, and optional Nesterov
+ * momentum.  One launch, one wave per item of the item table of the flat buffer (X3DSTEP_ITEMS_PER_GROUP items to a
+ * workgroup, the grid from nitems alone), so that every lane knows which tensor its elements belong to.
+ *   hyper  X3DStepHyper [S] on the device: the scales of tensor s
+ *   decision rule  state non-null: x3dstep_apply's, word for word (every thread reads the counter, the `nonfinite` field of
+ *                  the latest record and the coefficient word; nonfinite > 0: no store to w, g or m; a counter of 0: the
+ *                  kernel stores nothing and the twin refuses; thread 0 of workgroup 0 writes state[X3DSTEP_S_SKIP],
+ *                  [X3DSTEP_S_SKIPPED] and [X3DSTEP_S_RUN], which no other thread reads).  state null: the unguarded form:
+ *                  nothing is read from a state or a ring (ring and R are ignored), the coefficient is 1, the update is
+ *                  always applied and no state word is written.
+ *   tensor rule    lr_s = lr * hyper[seg].lr_scale; wd_s = weight_decay * hyper[seg].wd_scale: fp32, each rounded once,
+ *                  once per item, the same in every lane.  A scale of exactly 1.0f gives the bits of lr and weight_decay.
+ *   element rule   fp32, every operation rounded once (no contraction):
+ *     gi = coef == 1.0f ? g[i] : g[i] * coef
+ *     t  = gi * grad_scale;  gg = fmaf(wd_s, w[i], t)         (always the fma, also when wd_s == 0)
+ *     m' = first ? gg : fmaf(momentum, m[i], gg)
+ *     u  = nesterov ? fmaf(momentum, m', gg) : m';            w' = w[i] - lr_s * u           (g is never written)
+ *                  With nesterov == 0 and every scale 1.0f this is x3dstep_apply's rule: the same bits.  wd_s == 0 gives
+ *                  gg = t up to the sign of a zero for finite w (fmaf(0, w, -0) is +0 when w > 0).  lr_scale == 0 is plain
+ *                  arithmetic, not a freeze: the momentum still moves, and w stays put for a finite u.
+ *   walk           inside an item, 16-byte groups when w + start, g + start and m + start are congruent mod 16 (the elements
+ *                  before the 16-byte grid and after the last whole group one by one), element by element otherwise; a
+ *                  lane's loads for a batch of four groups are issued before that batch's first store; every element of w
+ *                  and m is stored at most once.  No LDS, no atomics, no allocation, no synchronisation: capturable.
+ *   per-item tests seg in [0, S), len in 1 .. X3DSTEP_ITEM, start in [0, n - len], both scales of the tensor finite and >= 0:
+ *                  an item that fails one is left untouched by the kernel (the tables are device memory nobody checked).
+ * x3dstep_apply_groups_host refuses the same with X3DSTEP_EINVAL and writes nothing; both refuse null or 4-byte-unaligned
+ * pointers, n < 1, overlapping w / g / m, nesterov or first outside {0, 1} and nesterov with momentum <= 0; the twin also an
+ * item table that is not exactly the in-order tiling of [0, n), and a counter of 0 when state is given.
+ */
+typedef struct {
+    float lr_scale;  /* the tensor's learning rate is lr * lr_scale */
+    float wd_scale;  /* ... and its weight decay weight_decay * wd_scale */
+} X3DStepHyper;
+
+size_t x3dstep_hyper_bytes(void);
+int x3dstep_apply_groups(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items, int64_t nitems,
+                         const X3DStepHyper* hyper, int S, int64_t* state, const void* ring, int R, float lr, float momentum,
+                         float weight_decay, float grad_scale, int first, int nesterov, void* stream);
+int x3dstep_apply_groups_host(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items, int64_t nitems,
+                              const X3DStepHyper* hyper, int S, int64_t* state, const void* ring, int R, float lr,
+                              float momentum, float weight_decay, float grad_scale, int first, int nesterov);
+
+/*
  * Saves and restores small buffers that a forward pass overwrites (the running statistics of batch normalisation).
  *   table  X3DStepKeep [nbuf]: the live buffers and where each lies in snap (fp32 [snap_n]); the ranges do not overlap
  *   items  the item table x3dstep_build_items gives for a segment table of snap (tensor s is buffer s; a tensor may be

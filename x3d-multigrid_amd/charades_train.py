@@ -201,7 +201,8 @@ def _save_ckpt(model, optimizer, lr_sched, save_model, steps, pbn_ckpt=None):
 def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_version='M', load_ckpt=None, resume=None,
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
         device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
+        head_lr_scale=1.0, nesterov=False):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -228,7 +229,13 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     `optimizer.ema.applied()` (prefix EMA PBN, 'ema_pbn_map' and 'ema_pbn_loss').  The K batches are drawn with a generator
     of their own: the training draws and every printed training loss are the same bits with and without it.  Checkpoints
     gain 'precise_bn_state_dict' (and 'ema_precise_bn_state_dict') once a 'val' phase has run; nothing loads them: they are
-    derived data, recomputed at the next validation."""
+    derived data, recomputed at the next validation.
+    wd_exempt_1d / head_lr_scale / nesterov: Trainer(tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale),
+    nesterov=) -- no weight decay on the parameters with ndim <= 1, the fresh 157-way fc2.* at a multiple of the base rate
+    (which ReduceLROnPlateau keeps driving), Nesterov momentum.  With any of them rank 0 prints one line before training
+    (tensors and elements exempt from decay, tensors at a scaled rate) and 'optimizer_state_dict' gains 'tensor_hyper',
+    which `resume` restores."""
+    from x3dhip import hypergroups
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
     ddp = process_group is not None and world > 1
@@ -279,7 +286,10 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update,
                         clip_grad_norm=clip_grad_norm, monitor=monitor, skip_nonfinite=skip_nonfinite,
                         ema_decay=ema_decay, ema_warmup=ema_warmup,
+                        tensor_hyper=hypergroups.recipe(x3d, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov,
                         **(dict(process_group=process_group, world_size=world) if ddp else {}))
+    if hasattr(optimizer, 'hyper'):
+        say(hypergroups.describe(optimizer))
     mon = getattr(optimizer, 'monitor', None)
     ema = getattr(optimizer, 'ema', None)
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)

@@ -277,6 +277,101 @@ STEP_HD ApplyPlan apply_plan(const void* w, const void* g, const void* m, int64_
     return p;
 }
 
+// -- the grouped update (x3dstep_apply_groups) -----------------------------------------------------------------------------
+struct GroupArgs {
+    float lr, mu, wd, gs;
+    int first, nesterov;
+};
+
+// one element: apply_one with the tensor's own rate and decay, and the Nesterov look-ahead.  With nesterov == 0, lr_s == lr
+// and wd_s == wd this is apply_one operation for operation.
+STEP_HD void group_one(float& w, float g, float& m, float coef, const GroupArgs& a, float lr_s, float wd_s) {
+    const float gi = coef == 1.0f ? g : scale_one(g, coef);
+    const float t = gi * a.gs;
+    const float gg = fmaf(wd_s, w, t);
+    const float mi = a.first ? gg : fmaf(a.mu, m, gg);
+    const float u = a.nesterov ? fmaf(a.mu, mi, gg) : mi;
+    const float step = lr_s * u;
+    m = mi;
+    w = w - step;
+}
+
+// a scale the tensor rule takes: finite and not negative (a NaN fails both comparisons)
+STEP_HD bool group_scale_ok(float s) { return s >= 0.0f && s <= 3.402823466e38f; }
+
+struct GroupItem {
+    int64_t start;
+    int len;                         // 0: the item is refused, nothing is touched
+    float lr_s, wd_s;                // the tensor rule: two fp32 multiplies, the same in every lane
+};
+
+// Item i resolved against the hyper table.  The tests are those x3dstep_apply_groups_host refuses a call for; the kernel
+// makes them per item, since the tables it reads are device memory nobody has checked.
+STEP_HD GroupItem group_resolve(const X3DStepItem* items, int64_t i, const X3DStepHyper* hyper, int S, int64_t n,
+                                const GroupArgs& a) {
+    GroupItem r = {0, 0, 0.0f, 0.0f};
+    const X3DStepItem it = items[i];
+    if (it.seg < 0 || it.seg >= S || it.len < 1 || it.len > X3DSTEP_ITEM || it.start < 0 || it.start > n - it.len) return r;
+    const X3DStepHyper h = hyper[it.seg];
+    if (!group_scale_ok(h.lr_scale) || !group_scale_ok(h.wd_scale)) return r;
+    r.start = it.start;
+    r.len = it.len;
+    r.lr_s = a.lr * h.lr_scale;
+    r.wd_s = a.wd * h.wd_scale;
+    return r;
+}
+
+constexpr int kGroupPieces = 4;      // 16-byte groups of w, g and m a lane holds at once: a batch
+constexpr int kGroupBatches = X3DSTEP_ITEM / (4 * kLanes * kGroupPieces);      // batches that cover a full item: 2
+
+// What lane `lane` of the item's wave updates.  When the three addresses of the item are congruent mod 16: `head` elements
+// up to the 16-byte grid one by one (lane j the j-th), the 16-byte groups q = lane, lane + 64, .. in batches of
+// kGroupPieces (a batch's loads of w, g and m before its first store), then the tail one by one.  Otherwise the elements
+// j = lane, lane + 64, ...  Every element of the item is stored once; nothing outside it is read or written.
+STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, int lane, float coef, const GroupArgs& a) {
+    float* wi = w + c.start;
+    const float* gi = g + c.start;
+    float* mi = m + c.start;
+    const uintptr_t r = (uintptr_t)wi & 15;
+    if (r != ((uintptr_t)gi & 15) || r != ((uintptr_t)mi & 15)) {
+        for (int j = lane; j < c.len; j += kLanes) group_one(wi[j], gi[j], mi[j], coef, a, c.lr_s, c.wd_s);
+        return;
+    }
+    int head = (int)(((16 - r) & 15) >> 2);
+    if (head > c.len) head = c.len;
+    const int groups = (c.len - head) >> 2;
+    const int tail = head + 4 * groups;
+    Vec4* wu = (Vec4*)(wi + head);
+    const Vec4* gu = (const Vec4*)(gi + head);
+    Vec4* mu = (Vec4*)(mi + head);
+#pragma unroll
+    for (int b = 0; b < kGroupBatches; ++b) {        // groups <= X3DSTEP_ITEM / 4 = kGroupBatches * kGroupPieces * kLanes
+        const int q0 = lane + b * kGroupPieces * kLanes;
+        if (q0 >= groups) break;
+        Vec4 wv[kGroupPieces], gv[kGroupPieces], mv[kGroupPieces];
+#pragma unroll
+        for (int k = 0; k < kGroupPieces; ++k) {
+            const int q = q0 + k * kLanes;
+            if (q < groups) {
+                wv[k] = wu[q];
+                gv[k] = gu[q];
+                mv[k] = mu[q];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kGroupPieces; ++k) {
+            const int q = q0 + k * kLanes;
+            if (q < groups) {
+                for (int e = 0; e < 4; ++e) group_one(wv[k].v[e], gv[k].v[e], mv[k].v[e], coef, a, c.lr_s, c.wd_s);
+                mu[q] = mv[k];
+                wu[q] = wv[k];
+            }
+        }
+    }
+    if (lane < head) group_one(wi[lane], gi[lane], mi[lane], coef, a, c.lr_s, c.wd_s);
+    if (lane < c.len - tail) group_one(wi[tail + lane], gi[tail + lane], mi[tail + lane], coef, a, c.lr_s, c.wd_s);
+}
+
 // -- the kept buffers (x3dstep_keep) ---------------------------------------------------------------------------------------
 constexpr int kKeepPieces = X3DSTEP_ITEM / (4 * kLanes);      // 16-byte groups of a full item per lane: 8
 

@@ -210,6 +210,91 @@ extern "C" int x3dstep_apply_host(float* w, const float* g, float* m, int64_t n,
     return X3DSTEP_OK;
 }
 
+// -- the grouped update -----------------------------------------------------------------------------------------------------
+extern "C" size_t x3dstep_hyper_bytes(void) { return sizeof(X3DStepHyper); }
+
+static bool ranges_overlap(const float* a, const float* b, int64_t n);
+
+// the argument checks x3dstep_apply_groups and its twin share (no pointer is followed: the tables may be device memory)
+int x3dstep_check_groups(const char* who, const float* w, const float* g, const float* m, int64_t n, const X3DStepItem* items,
+                         int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state, const void* ring, int R,
+                         float momentum, int first, int nesterov) {
+    if (!w || !g || !m || !items || !hyper || n < 1 || n > ((int64_t)1 << 40) || nitems < 1 || nitems > X3DSTEP_MAX_ITEMS ||
+        S < 1 || S > X3DSTEP_MAX_SEGMENTS || (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)hyper) & 3) != 0 ||
+        ((uintptr_t)items & 7) != 0) {
+        x3dstep_set_error("%s: null or unaligned pointer, n %lld outside 1 .. 2^40, nitems %lld outside 1 .. %d or S %d outside "
+                          "1 .. %d", who, (long long)n, (long long)nitems, X3DSTEP_MAX_ITEMS, S, X3DSTEP_MAX_SEGMENTS);
+        return X3DSTEP_EINVAL;
+    }
+    if (ranges_overlap(w, g, n) || ranges_overlap(w, m, n) || ranges_overlap(g, m, n)) {
+        x3dstep_set_error("%s: w, g and m overlap", who);
+        return X3DSTEP_EINVAL;
+    }
+    if (state && (!ring || R < 1 || (((uintptr_t)state | (uintptr_t)ring) & 7) != 0)) {
+        x3dstep_set_error("%s: a state without a ring, an unaligned state or ring, or R %d < 1", who, R);
+        return X3DSTEP_EINVAL;
+    }
+    if ((first != 0 && first != 1) || (nesterov != 0 && nesterov != 1) || (nesterov == 1 && !(momentum > 0.0f))) {
+        x3dstep_set_error("%s: first %d or nesterov %d outside {0, 1}, or nesterov with momentum %g <= 0", who, first, nesterov,
+                          (double)momentum);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items,
+                                         int64_t nitems, const X3DStepHyper* hyper, int S, int64_t* state, const void* ring,
+                                         int R, float lr, float momentum, float weight_decay, float grad_scale, int first,
+                                         int nesterov) {
+    using namespace x3ds;
+    const char* who = "x3dstep_apply_groups_host";
+    const int rc = x3dstep_check_groups(who, w, g, m, n, items, nitems, hyper, S, state, ring, R, momentum, first, nesterov);
+    if (rc) return rc;
+    // the tables are host memory here: refuse the call for what the kernel would leave out item by item
+    for (int s = 0; s < S; ++s) {
+        if (!group_scale_ok(hyper[s].lr_scale) || !group_scale_ok(hyper[s].wd_scale)) {
+            x3dstep_set_error("%s: tensor %d: a scale that is negative or not finite (lr_scale %g, wd_scale %g)", who, s,
+                              (double)hyper[s].lr_scale, (double)hyper[s].wd_scale);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    int64_t at = 0;
+    int32_t seg = 0;
+    for (int64_t i = 0; i < nitems; ++i) {
+        const X3DStepItem it = items[i];
+        if (it.seg < seg || it.seg >= S || it.len < 1 || it.len > X3DSTEP_ITEM || it.start != at || it.start > n - it.len) {
+            x3dstep_set_error("%s: item %lld (start %lld, tensor %d, len %d) is not the next piece of the in-order tiling of "
+                              "[0, %lld) over %d tensors", who, (long long)i, (long long)it.start, it.seg, it.len, (long long)n,
+                              S);
+            return X3DSTEP_EINVAL;
+        }
+        at += it.len;
+        seg = it.seg;
+    }
+    if (at != n) {
+        x3dstep_set_error("%s: the items cover %lld of %lld elements", who, (long long)at, (long long)n);
+        return X3DSTEP_EINVAL;
+    }
+    float coef = 1.0f;
+    if (state) {
+        const Decision d = apply_decision(state, ring, R, S);
+        if (!d.go) {
+            x3dstep_set_error("%s: the state's step counter is 0: nothing has been measured", who);
+            return X3DSTEP_EINVAL;
+        }
+        apply_counters(state, d.skip);
+        if (d.skip) return X3DSTEP_OK;
+        coef = d.coef;
+    }
+    const GroupArgs a = {lr, momentum, weight_decay, grad_scale, first, nesterov};
+    for (int64_t i = 0; i < nitems; ++i) {
+        const GroupItem c = group_resolve(items, i, hyper, S, n, a);
+        if (c.len > 0)
+            for (int l = 0; l < kLanes; ++l) group_lane(w, g, m, c, l, coef, a);
+    }
+    return X3DSTEP_OK;
+}
+
 // the argument checks x3dstep_keep and its twin share (no pointer is followed: the tables may be device memory)
 int x3dstep_check_keep(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
                        const float* snap, int64_t snap_n, const int64_t* state, int mode) {

@@ -40,7 +40,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
+        head_lr_scale=1.0, nesterov=False):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
     every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
@@ -57,7 +58,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
                               world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor,
                               skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
-                              ema_warmup=ema_warmup, precise_bn=precise_bn)
+                              ema_warmup=ema_warmup, precise_bn=precise_bn, wd_exempt_1d=wd_exempt_1d,
+                              head_lr_scale=head_lr_scale, nesterov=nesterov)
 
 
 def init_distributed():
@@ -126,6 +128,11 @@ def main(run_fn, default_save):
                         help='before every validation recompute the BN statistics over K training batches on the GPU and '
                              'validate once more with them (a line prefixed PBN; with --ema-decay also EMA PBN); checkpoints '
                              'gain precise_bn_state_dict (off by default)')
+    parser.add_argument('--wd-exempt-1d', action='store_true',
+                        help='no weight decay on BatchNorm scale / shift and biases (every parameter with ndim <= 1)')
+    parser.add_argument('--head-lr-scale', type=float, default=1.0, metavar='X',
+                        help='train the classifier fc2.* at X times the base learning rate (default 1)')
+    parser.add_argument('--nesterov', action='store_true', help='Nesterov momentum (off by default)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -143,7 +150,8 @@ def main(run_fn, default_save):
                use_graph=not args.no_graph, num_steps_per_update=args.accumulate, device=str(dev), process_group=pg,
                rank=rank, world=world, clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False,
                skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, ema_decay=args.ema_decay,
-               ema_warmup=not args.no_ema_warmup, precise_bn=args.precise_bn, **size)
+               ema_warmup=not args.no_ema_warmup, precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d,
+               head_lr_scale=args.head_lr_scale, nesterov=args.nesterov, **size)
     finally:
         if pg is not None:
             import torch.distributed as dist

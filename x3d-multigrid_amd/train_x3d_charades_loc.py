@@ -32,7 +32,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         x3d_version=X3D_VERSION, load_ckpt=None, resume=None, save_model=SAVE_MODEL, save_every=1000, use_graph=True,
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
-        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None):
+        skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
+        head_lr_scale=1.0, nesterov=False):
     """The reference's run() (train_x3d_charades_loc.py:54-221) over a charades.Charades dataset with task='loc'.
     Arguments as train_x3d_charades.run."""
     if not isinstance(anno, dict):
@@ -46,7 +47,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               dropout=dropout, seed=seed, device=device, process_group=process_group, rank=rank,
                               world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor,
                               skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
-                              ema_warmup=ema_warmup, precise_bn=precise_bn)
+                              ema_warmup=ema_warmup, precise_bn=precise_bn, wd_exempt_1d=wd_exempt_1d,
+                              head_lr_scale=head_lr_scale, nesterov=nesterov)
 
 
 if __name__ == '__main__':

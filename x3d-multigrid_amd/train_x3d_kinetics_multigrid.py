@@ -206,7 +206,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
         frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8,
-        ema_decay=None, ema_warmup=True, precise_bn=None):
+        ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False, head_lr_scale=1.0, nesterov=False):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -236,7 +236,12 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     `optimizer.ema.applied()`: the statistics of the averaged weights, prefix EMA PBN.  The K batches come from a generator
     of their own, so the training draws -- and every printed training loss -- are the same bits with and without it.
     Checkpoints gain 'precise_bn_state_dict' (and 'ema_precise_bn_state_dict'); nothing loads them: they are derived data,
-    recomputed at the next validation."""
+    recomputed at the next validation.
+    wd_exempt_1d / head_lr_scale / nesterov: Trainer(tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale),
+    nesterov=) -- no weight decay on the parameters with ndim <= 1, fc2.* at a multiple of the base rate, Nesterov momentum;
+    the schedule keeps driving the base rate.  With any of them rank 0 prints one line before training (tensors and elements
+    exempt from decay, tensors at a scaled rate) and the optimizer's state in a checkpoint gains 'tensor_hyper'."""
+    from x3dhip import hypergroups
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -285,7 +290,10 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     lr = init_lr
     optimizer = Trainer(model, lr=lr, momentum=0.9, weight_decay=5e-5, process_group=pg, world_size=world,
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update, clip_grad_norm=clip_grad_norm,
-                        monitor=monitor, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                        monitor=monitor, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                        tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov)
+    if rank == 0 and hasattr(optimizer, 'hyper'):
+        print(hypergroups.describe(optimizer))
     mon = getattr(optimizer, 'monitor', None)
     ema = getattr(optimizer, 'ema', None)
     lr_sched = MultiStepLR(optimizer, lr_schedule)
@@ -541,6 +549,11 @@ if __name__ == '__main__':
                         help='before every validation recompute the BN statistics over K training batches on the GPU and '
                              'validate once more with them (lines prefixed PBN; with --ema-decay also EMA PBN); checkpoints '
                              'gain precise_bn_state_dict (off by default)')
+    parser.add_argument('--wd-exempt-1d', action='store_true',
+                        help='no weight decay on BatchNorm scale / shift and biases (every parameter with ndim <= 1)')
+    parser.add_argument('--head-lr-scale', type=float, default=1.0, metavar='X',
+                        help='train the classifier fc2.* at X times the base learning rate (default 1)')
+    parser.add_argument('--nesterov', action='store_true', help='Nesterov momentum (off by default)')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -570,4 +583,5 @@ if __name__ == '__main__':
         val_batch_size=args.val_batch, val_crops=args.val_crops, val_frames=val_frames,
         clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, skip_nonfinite=args.skip_nonfinite,
         max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
-        precise_bn=args.precise_bn)
+        precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d, head_lr_scale=args.head_lr_scale,
+        nesterov=args.nesterov)

@@ -31,6 +31,7 @@ ITEM_DT = np.dtype([("start", "<i8"), ("seg", "<i4"), ("len", "<i4")])
 KEEP_DT = np.dtype([("addr", "<i8"), ("offset", "<i8"), ("len", "<i4"), ("pad", "<i4")])
 PBN_LAYER_DT = np.dtype([("mean_addr", "<i8"), ("var_addr", "<i8"), ("mean_off", "<i8"), ("var_off", "<i8"), ("first", "<i8"),
                          ("C", "<i4"), ("S", "<i4")])
+HYPER_DT = np.dtype([("lr_scale", "<f4"), ("wd_scale", "<f4")])
 HEADER_DT = np.dtype([("step", "<i8"), ("total", "<f8"), ("norm", "<f8"), ("coef", "<f4"), ("nonfinite", "<i4"),
                       ("first_bad", "<i4"), ("nseg", "<i4")])
 
@@ -59,6 +60,9 @@ SIGNATURES = {
     "x3dstep_measure_host": (_I, [_P, _L, _P, _I, _P, _P, _L, _P, _P, _P, _I, _D, _D]),
     "x3dstep_apply": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P]),
     "x3dstep_apply_host": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _F, _F, _I]),
+    "x3dstep_hyper_bytes": (_Z, []),
+    "x3dstep_apply_groups": (_I, [_P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I, _P]),
+    "x3dstep_apply_groups_host": (_I, [_P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I]),
     "x3dstep_keep": (_I, [_P, _I, _P, _L, _P, _L, _P, _I, _P]),
     "x3dstep_keep_host": (_I, [_P, _I, _P, _L, _P, _L, _P, _I]),
     "x3dstep_ema": (_I, [_P, _P, _L, _P, _L, _F, _I, _P]),

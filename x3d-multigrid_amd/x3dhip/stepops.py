@@ -172,6 +172,70 @@ def apply_host(w, g, m, tables, state, ring, R, lr, momentum=0.9, weight_decay=5
                                             1 if first else 0))
 
 
+def _group_flags(who, momentum, first, nesterov):
+    if first not in (0, 1, False, True) or nesterov not in (0, 1, False, True):
+        raise ValueError("%s: first and nesterov must be 0 or 1 (got %r, %r)" % (who, first, nesterov))
+    if nesterov and not float(momentum) > 0.0:
+        raise ValueError("%s: nesterov needs momentum > 0 (got %r)" % (who, momentum))
+    return int(first), int(nesterov)
+
+
+def apply_groups(w, g, m, tables, hyper, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, grad_scale=1.0, first=False,
+                 nesterov=False):
+    """The grouped update, one launch on the current stream: `apply` with tensor s at the rate lr * hyper[s, 0] and the
+    decay weight_decay * hyper[s, 1], and Nesterov momentum when asked (include/x3dstep.h).  hyper: float32 [S, 2] on the
+    tables' device (X3DStepHyper [S]: lr_scale, wd_scale).  state: the monitor's int64 [STATE_WORDS] after `measure` on the
+    same state and ring, or None: the unguarded form, which reads no state (ring and R are then ignored), takes the
+    coefficient 1 and always applies."""
+    R = int(R)
+    dev = tables.device
+    if dev is None or dev.type != "cuda":
+        raise ValueError("apply_groups: the tables are not on a GPU (apply_groups_host is the CPU twin)")
+    for name, t in (("w", w), ("g", g), ("m", m)):
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.dim() != 1
+                or not t.is_contiguous() or t.numel() != tables.n):
+            raise ValueError("apply_groups: %s must be a contiguous float32 [%d] on %s" % (name, tables.n, dev))
+    if (not isinstance(hyper, torch.Tensor) or hyper.device != dev or hyper.dtype != torch.float32
+            or tuple(hyper.shape) != (tables.S, 2) or not hyper.is_contiguous()):
+        raise ValueError("apply_groups: hyper must be a contiguous float32 [%d, 2] on %s" % (tables.S, dev))
+    if state is not None:
+        _check_device("apply_groups", g, tables, None, state, ring, R)
+    first, nesterov = _group_flags("apply_groups", momentum, first, nesterov)
+    check(_steplib.lib().x3dstep_apply_groups(ptr(w), ptr(g), ptr(m), tables.n, ptr(tables.d_items), tables.nitems,
+                                              ptr(hyper), tables.S, None if state is None else ptr(state),
+                                              None if state is None else ptr(ring), R if state is not None else 0,
+                                              float(lr), float(momentum), float(weight_decay), float(grad_scale), first,
+                                              nesterov, stream()))
+
+
+def apply_groups_host(w, g, m, tables, hyper, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, grad_scale=1.0,
+                      first=False, nesterov=False):
+    """The CPU twin of `apply_groups` on numpy arrays (w and m are updated in place; hyper: HYPER_DT [S] or float32
+    [S, 2]; state int64 [STATE_WORDS] or None)."""
+    R = int(R)
+    for name, a, wr in (("w", w, True), ("g", g, False), ("m", m, True)):
+        if (a.dtype != np.float32 or a.ndim != 1 or a.size != tables.n or not a.flags.c_contiguous
+                or (wr and not a.flags.writeable)):
+            raise ValueError("apply_groups_host: %s must be a %scontiguous float32 [%d]"
+                             % (name, "writeable " if wr else "", tables.n))
+    if hyper.dtype == _steplib.HYPER_DT:
+        ok = hyper.ndim == 1 and hyper.size == tables.S
+    else:
+        ok = hyper.dtype == np.float32 and hyper.shape == (tables.S, 2)
+    if not ok or not hyper.flags.c_contiguous:
+        raise ValueError("apply_groups_host: hyper must be a contiguous HYPER_DT [%d] or float32 [%d, 2]"
+                         % (tables.S, tables.S))
+    if state is not None:
+        _check_host("apply_groups_host", g, tables, None, state, ring, R, writeable=False)
+    first, nesterov = _group_flags("apply_groups_host", momentum, first, nesterov)
+    check(_steplib.lib().x3dstep_apply_groups_host(_np_ptr(w), _np_ptr(g), _np_ptr(m), tables.n, _np_ptr(tables.items),
+                                                   tables.nitems, _np_ptr(hyper), tables.S,
+                                                   None if state is None else _np_ptr(state),
+                                                   None if state is None else _np_ptr(ring), R if state is not None else 0,
+                                                   float(lr), float(momentum), float(weight_decay), float(grad_scale), first,
+                                                   nesterov))
+
+
 class KeepTable:
     """The table `keep` takes for a list of small float32 buffers: where each lies in the snapshot (every buffer starts on
     a multiple of four elements, so that a 16-byte aligned buffer is copied in 16-byte groups), the item table of the

@@ -121,7 +121,7 @@ class Trainer:
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
                  objective="ce", clip_grad_norm=None, monitor=False, skip_nonfinite=False, ema_decay=None,
-                 ema_warmup=True):
+                 ema_warmup=True, tensor_hyper=None, nesterov=False):
         """overlap: multi-rank steps are captured as two graphs around the first gradient bucket (False: single graph,
         all-reduce after the whole backward); force_split: the two-graph form on a single rank too (tests);
         force_collectives: all-reduce on a one-rank process group (the single-GPU RCCL test).  Round 4: constructor
@@ -174,6 +174,21 @@ class Trainer:
         used there is no attribute (`'precise_bn' in vars(trainer)`; `hasattr` would make it) and not one launch, and
         state_dict() is the same either way.
 
+        tensor_hyper / nesterov: per-tensor hyper-parameters of the update.  tensor_hyper is a dict of fnmatch pattern over
+        the named_parameters() names -> dict(lr_scale= / wd_scale=), applied in order (hypergroups.recipe(model,
+        wd_exempt_1d=True, head_lr_scale=10) gives the usual one: no weight decay on BatchNorm scale / shift and biases,
+        the classifier at a multiple of the base rate); a pattern that matches nothing raises.  nesterov=True is Nesterov
+        momentum (torch.optim.SGD's form).  Either creates a hypergroups.HyperTable (`self.hyper`) and turns the update into
+        one launch of stepops.apply_groups, which reads the scales of every tensor from a device table: with skip_nonfinite
+        in the place of stepops.apply (measure, apply_groups, restore), without it in the place of ops.sgd_fused after the
+        monitor's observe, if there is one.  Same order as ever: after the all-reduce and `pre_step`, outside every
+        captured graph, on the updating call only under accumulation, grad_scale = 1 / world; data parallel: every rank
+        holds the same table, no collective is added.  param_groups stays the single base dict (its 'nesterov' key tells),
+        so schedules that drive trainer.lr keep working on the base rate; state_dict() gains a top-level 'tensor_hyper'
+        ({'names', 'lr_scale', 'wd_scale'}), which load_state_dict restores (ValueError on other names; a checkpoint
+        without the key loads as before).  lr_scale = 0 is arithmetic, not a freeze: the momentum still moves and no
+        backward pass is skipped.  Both at their defaults: no attribute, no launch, the update kernels called as before.
+
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
         afterwards is not part of the flat buffers and would not be trained."""
@@ -196,7 +211,7 @@ class Trainer:
         self._acc_reducer = None
         self.stepped = False
         self.param_groups = [dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay,
-                                  nesterov=False, params=list(range(len(self.fp.params))))]
+                                  nesterov=bool(nesterov), params=list(range(len(self.fp.params))))]
         self.pg = process_group
         self.world = world_size
         self.first = True
@@ -213,6 +228,13 @@ class Trainer:
             ring = 64 if (monitor is True or not monitor) else int(monitor)
             self.monitor = GradMonitor(self.fp, [k for k, _ in model.named_parameters()], ring=ring,
                                        max_norm=clip_grad_norm, inv_world=1.0 / world_size)
+        if tensor_hyper is not None or nesterov:
+            from .hypergroups import HyperTable
+            if nesterov and not float(momentum) > 0.0:
+                raise ValueError("nesterov needs momentum > 0 (got %r)" % (momentum,))
+            self.hyper = HyperTable(self.fp, [k for k, _ in model.named_parameters()], monitor=getattr(self, "monitor", None))
+            if tensor_hyper:
+                self.hyper.apply(tensor_hyper)
         if ema_decay is not None:
             from .weightema import WeightEMA
             self.ema = WeightEMA(self.fp, model, ema_decay, warmup=ema_warmup, monitor=getattr(self, "monitor", None))
@@ -349,6 +371,22 @@ class Trainer:
     def _update(self, grad=None):
         mon = getattr(self, "monitor", None)
         g = self.param_groups[0]
+        hy = getattr(self, "hyper", None)
+        if hy is not None:                   # per-tensor scales and / or Nesterov: one launch that knows the tensors
+            from . import _steplib, stepops
+            guarded = self.skip_nonfinite
+            if guarded:
+                mon.measure(grad)
+            elif mon is not None:
+                mon.observe(grad)            # scales the gradient in place, as before ops.sgd_fused
+            stepops.apply_groups(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, hy.tables, hy.hyper,
+                                 mon.state if guarded else None, mon.ring if guarded else None, mon.R if guarded else 0,
+                                 g['lr'], g['momentum'], g['weight_decay'], 1.0 / self.world, first=self.first,
+                                 nesterov=bool(g['nesterov']))
+            if guarded:
+                stepops.keep(self._keep_table(), mon.state, _steplib.KEEP_RESTORE)
+            self.first = False
+            return
         if self.skip_nonfinite:
             from . import _steplib, stepops
             mon.measure(grad)                # the decision and the coefficient stay on the device
@@ -573,13 +611,20 @@ class Trainer:
         if not self.first:
             for i, (o, k) in enumerate(self.fp.offsets):
                 state[i] = {'momentum_buffer': self.fp.mom[o:o + k].view(self.fp.params[i].shape).clone()}
-        return {'state': state, 'param_groups': [dict(self.param_groups[0])]}
+        sd = {'state': state, 'param_groups': [dict(self.param_groups[0])]}
+        hy = getattr(self, "hyper", None)
+        if hy is not None:
+            sd['tensor_hyper'] = hy.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         g = sd['param_groups'][0]
         for k in ('lr', 'momentum', 'weight_decay'):
             if k in g:
                 self.param_groups[0][k] = g[k]
+        hy = getattr(self, "hyper", None)
+        if hy is not None and sd.get('tensor_hyper') is not None:
+            hy.load_state_dict(sd['tensor_hyper'])
         st = sd.get('state', {})
         if st:
             for i, (o, k) in enumerate(self.fp.offsets):
