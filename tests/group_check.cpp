@@ -13,7 +13,7 @@
 //
 // After the file's cases: the kernel's own walk (x3ds::group_resolve and x3ds::group_lane of step_core.h, item by item and
 // lane by lane, as the launch runs them) over a table with one bad item of each kind -- exactly the elements of that item
-// keep their bytes, and every other element is what x3ds::group_one gives with its tensor's scales.
+// keep their bytes, and every other element is what x3ds::sgd_one gives with its tensor's scales.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -205,7 +205,7 @@ static long item_case(int kind, int shift) {
         z = z * 1664525u + 1013904223u;
         m[i] = m0[(size_t)i] = (float)((int)(z >> 8) % 2001 - 1000) / 4096.0f;
     }
-    const GroupArgs a = {0.05f, 0.9f, 5e-5f, 0.5f, 0, 1};
+    const SgdArgs a = {0.05f, 0.9f, 5e-5f, 0.5f, 0, 1};
     // the twin refuses the table ...
     long failures = 0;
     if (x3dstep_apply_groups_host(w, g, m, n, items, nitems, hyper, S, nullptr, nullptr, 0, a.lr, a.mu, a.wd, a.gs, 0, 1) !=
@@ -225,7 +225,7 @@ static long item_case(int kind, int shift) {
         const float lr_s = a.lr * kLrScales[s % 5], wd_s = a.wd * kWdScales[s % 3];
         for (int64_t i = seg_off[s]; i < seg_off[s + 1]; ++i) {
             float we = w0[(size_t)i], me = m0[(size_t)i];
-            if (!frozen[(size_t)i]) group_one(we, g[i], me, 1.0f, a, lr_s, wd_s);
+            if (!frozen[(size_t)i]) sgd_one(we, g[i], me, 1.0f, a, lr_s, wd_s);
             wrong += memcmp(&we, &w[i], 4) != 0 || memcmp(&me, &m[i], 4) != 0;
             moved += memcmp(&m0[(size_t)i], &m[i], 4) != 0;
         }

@@ -4,9 +4,7 @@ for byte and inside guard bands; the count, skip and decay rules; the refusals; 
 stand-alone program.  No GPU."""
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import pytest
 from tests import ema_cases as ec
 from tests import ema_ref
 from tests import guard_cases as gc
+from tests import step_program
 from x3dhip import _steplib, stepops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -328,8 +327,7 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
     """step_host.cpp and step_core.h compiled with -fsanitize=address,undefined into a program of their own
     (tests/ema_check.cpp), run as a child process on lists of this file, every buffer a heap block of exactly the size the
     library is told; nothing sanitised is loaded into this interpreter."""
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no C++ compiler"
+    step_program.compiler()
     _lib()
     ema_cases = []
     for i, n in enumerate(ec.LENGTHS):
@@ -350,15 +348,6 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
         for n, sa, sb in swap_cases:
             f.write(struct.pack("<III", n, sa, sb))
             f.write(_bit_patterns(n, n).tobytes() + _bit_patterns(n, 9000 + n).tobytes())
-    exe = str(tmp_path / "ema_check")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "ema_check.cpp"),
-           os.path.join(ROOT, "x3d-multigrid_amd", "csrc_step", "step_host.cpp"), "-o", exe]
-    # the sanitisers' runtimes linked into the program itself where the compiler ships them so (gcc needs to be told)
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[:6] == ["ema", str(len(ema_cases)), "keep", str(len(keep_cases)), "swap", str(len(swap_cases))], r.stdout[-500:]
-    assert int(last[-1]) == 0, r.stdout[-500:]
+    last, out = step_program.run(tmp_path, "ema_check", path)
+    assert last[:6] == ["ema", str(len(ema_cases)), "keep", str(len(keep_cases)), "swap", str(len(swap_cases))], out[-500:]
+    assert int(last[-1]) == 0, out[-500:]

@@ -4,7 +4,6 @@ of scales; the restatement itself against torch.optim.SGD in fp64; the identity 
 refusals; the ABI; the same lists in a sanitised stand-alone program.  No GPU."""
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -15,6 +14,7 @@ import torch
 from tests import group_cases as grc
 from tests import group_ref, guard_ref, step_ref
 from tests import guard_cases as gc
+from tests import step_program
 from x3dhip import _steplib, stepops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -377,8 +377,7 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
     exactly the size the library is told; nothing sanitised is loaded into this interpreter.  The program also runs the
     kernel's per-item walk (group_resolve, group_lane) over the tables with one bad item each and checks that exactly that
     item is untouched."""
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no C++ compiler"
+    step_program.compiler()
     _lib()
     syn = gc.synthetic()
     S = len(syn) - 1
@@ -399,15 +398,6 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
             _write_case(f, *c)
-    exe = str(tmp_path / "group_check")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "group_check.cpp"),
-           os.path.join(ROOT, "x3d-multigrid_amd", "csrc_step", "step_host.cpp"), "-o", exe]
-    # the sanitisers' runtimes linked into the program itself where the compiler ships them so (gcc needs to be told)
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[:2] == ["groups", str(len(cases))] and last[2] == "items" and int(last[3]) == 10, r.stdout[-500:]
-    assert int(last[-1]) == 0, r.stdout[-500:]
+    last, out = step_program.run(tmp_path, "group_check", path)
+    assert last[:2] == ["groups", str(len(cases))] and last[2] == "items" and int(last[3]) == 10, out[-500:]
+    assert int(last[-1]) == 0, out[-500:]

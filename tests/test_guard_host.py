@@ -4,9 +4,7 @@ the skip decision and its counters; the refusals; the ABI; the same lists in a s
 import ctypes
 import os
 import re
-import shutil
 import struct
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -14,6 +12,7 @@ import pytest
 
 from tests import guard_cases as gc
 from tests import guard_ref, step_ref
+from tests import step_program
 from x3dhip import _steplib, stepops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -314,8 +313,7 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
     """step_host.cpp and step_core.h compiled with -fsanitize=address,undefined into a program of their own
     (tests/guard_check.cpp), run as a child process on lists of this file, every buffer a heap block of exactly the size
     the library is told; nothing sanitised is loaded into this interpreter."""
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no C++ compiler"
+    step_program.compiler()
     _lib()
     syn = gc.synthetic()
     good, bad = gc.normals(N, 91), gc.normals(N, 92)
@@ -339,15 +337,6 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
             _write_apply_case(f, *c)
         for c in keep_cases:
             _write_keep_case(f, *c)
-    exe = str(tmp_path / "guard_check")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "guard_check.cpp"),
-           os.path.join(ROOT, "x3d-multigrid_amd", "csrc_step", "step_host.cpp"), "-o", exe]
-    # the sanitisers' runtimes linked into the program itself where the compiler ships them so (gcc needs to be told)
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[:2] == ["apply", str(len(apply_cases))] and last[2:4] == ["keep", str(len(keep_cases))], r.stdout[-500:]
-    assert int(last[-1]) == 0, r.stdout[-500:]
+    last, out = step_program.run(tmp_path, "guard_check", path)
+    assert last[:2] == ["apply", str(len(apply_cases))] and last[2:4] == ["keep", str(len(keep_cases))], out[-500:]
+    assert int(last[-1]) == 0, out[-500:]

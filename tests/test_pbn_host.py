@@ -4,7 +4,6 @@ of the rule itself; the exact cases; the NaN rule; the refusals; the ABI; the sa
 No GPU."""
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -14,6 +13,7 @@ import pytest
 from tests import guard_cases as gc
 from tests import pbn_cases as pc
 from tests import pbn_ref
+from tests import step_program
 from x3dhip import _steplib, stepops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -306,8 +306,7 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
     """step_host.cpp and step_core.h compiled with -fsanitize=address,undefined into a program of their own
     (tests/pbn_check.cpp), run as a child process on lists of this file, every buffer a heap block of exactly the size the
     library is told; nothing sanitised is loaded into this interpreter."""
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no C++ compiler"
+    step_program.compiler()
     _lib()
     cases = []
     for i, S in enumerate(pc.SPLITS):
@@ -319,14 +318,5 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
         f.write(struct.pack("<I", len(cases)))
         for c in cases:
             _write_case(f, *c)
-    exe = str(tmp_path / "pbn_check")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "pbn_check.cpp"),
-           os.path.join(ROOT, "x3d-multigrid_amd", "csrc_step", "step_host.cpp"), "-o", exe]
-    # the sanitisers' runtimes linked into the program itself where the compiler ships them so (gcc needs to be told)
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[:2] == ["pbn", str(len(cases))] and int(last[-1]) == 0, r.stdout[-500:]
+    last, out = step_program.run(tmp_path, "pbn_check", path)
+    assert last[:2] == ["pbn", str(len(cases))] and int(last[-1]) == 0, out[-500:]

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import step_ref
+from tests import step_program
 from x3dhip import _steplib, stepops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -296,8 +297,7 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
     """step_host.cpp and step_core.h compiled with -fsanitize=address,undefined into a program of their own, run as a child
     process on the lists of this file (heap blocks of exactly the sizes the library is told); nothing sanitised is loaded
     into this interpreter."""
-    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no C++ compiler"
+    step_program.compiler()
     syn = step_ref.synthetic_seg_off()
     clean, bad = _normals(16384, 61), _normals(16384, 62)
     bad[int(syn[9]) + 7] = np.nan
@@ -313,14 +313,36 @@ def test_the_same_lists_in_a_sanitised_stand_alone_program(tmp_path):
         f.write(struct.pack("<I", len(cases)))
         for off, R, steps, mis in cases:
             _check_file_case(f, off, R, steps, mis)
-    exe = str(tmp_path / "step_check")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "step_check.cpp"),
-           os.path.join(ROOT, "x3d-multigrid_amd", "csrc_step", "step_host.cpp"), "-o", exe]
-    # the sanitisers' runtimes linked into the program itself where the compiler ships them so (gcc needs to be told)
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.run(cmd, check=True)
-    r = subprocess.run([exe, path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    last = r.stdout.strip().splitlines()[-1].split()
-    assert last[0] == "cases" and int(last[1]) == len(cases) and int(last[-1]) == 0, r.stdout[-500:]
+    last, out = step_program.run(tmp_path, "step_check", path)
+    assert last[0] == "cases" and int(last[1]) == len(cases) and int(last[-1]) == 0, out[-500:]
+
+
+def test_no_kernel_of_the_library_uses_scratch(tmp_path):
+    """The four .hip files compiled for gfx950 with the Makefile's flags and the compiler's resource-usage remarks: every
+    kernel reports 0 bytes of scratch per lane (an array of 16-byte groups that the compiler leaves in private memory makes
+    a walk move its data through scratch, and nothing else would show it), and the kernels that tools and documents cite
+    are among them.  The compiler needs no GPU."""
+    src = os.path.join(ROOT, "x3d-multigrid_amd", "csrc_step")
+    make = open(os.path.join(src, "Makefile")).read()
+    hipcc = os.environ.get("HIPCC") or re.search(r"^HIPCC \?= (\S+)", make, re.M).group(1)
+    if not (shutil.which(hipcc) or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    hipcc = shutil.which(hipcc) or shutil.which("hipcc")
+    arch = re.search(r"^ARCH\s+\?= (\S+)", make, re.M).group(1)
+    flags = re.search(r"^CXXFLAGS = (.*)$", make, re.M).group(1).replace("$(ARCH)", arch).split()
+    assert arch == "gfx950" and "-ffp-contract=off" in flags
+    files = ("step", "ema", "group", "pbn")
+    jobs = [subprocess.Popen([hipcc] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(src, f + ".hip"),
+                                                "-o", str(tmp_path / (f + ".o"))], stderr=subprocess.PIPE, text=True)
+            for f in files]
+    scratch = {}
+    for f, job in zip(files, jobs):
+        err = job.communicate()[1]
+        assert job.returncode == 0, err[-4000:]
+        found = re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", err, re.S)
+        assert found, "%s.hip: no resource-usage remarks" % f
+        scratch.update((name, int(b)) for name, b in found)
+    print(scratch)
+    assert [k for k, b in scratch.items() if b != 0] == []
+    for cited in ("x3dstep_partials_kernel", "x3dstep_finalize_kernel", "x3dstep_scale_kernel", "x3dstep_apply_groups_kernel"):
+        assert any(cited in k for k in scratch), cited

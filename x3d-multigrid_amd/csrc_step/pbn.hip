@@ -3,22 +3,9 @@
 // variance into every split's slot of a keep table's snapshot).  The cell, merge and result rules and the per-item tests are
 // step_core.h's, shared with the CPU twins.  One workgroup per run of at most X3DSTEP_PBN_RUN channels, one thread per
 // channel, reads coalesced over the channel; no LDS, no atomics, no allocation, no synchronisation.
-#include "step_core.h"
-
-void x3dstep_set_error(const char* fmt, ...);  // step_host.cpp
-int x3dstep_check_pbn(const char* who, const X3DStepPbnLayer* layers, int nlayers, const X3DStepItem* work, int64_t nwork,
-                      const double* acc, bool finish, int W, int64_t expect_n, const float* snap, int64_t snap_n);
+#include "step_priv.h"
 
 using namespace x3ds;
-
-#define X3DSTEP_LAUNCH_CHECK()                                                                                  \
-    do {                                                                                                        \
-        hipError_t e_ = hipGetLastError();                                                                      \
-        if (e_ != hipSuccess) {                                                                                 \
-            x3dstep_set_error("%s:%d: launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_));           \
-            return X3DSTEP_ELAUNCH;                                                                             \
-        }                                                                                                       \
-    } while (0)
 
 __global__ __launch_bounds__(X3DSTEP_PBN_RUN) void x3dstep_pbn_accum_kernel(const X3DStepPbnLayer* __restrict__ layers,
                                                                              int nlayers,

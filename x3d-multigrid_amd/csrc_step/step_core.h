@@ -1,6 +1,7 @@
-// The arithmetic of libx3dstep (include/x3dstep.h) item by item and tensor by tensor, compiled into step.hip (the kernels)
-// and step_host.cpp (the CPU twin): what a lane adds and in which order, the sum of a tensor's items, the coefficient rule,
-// the record's layout and what the one finishing thread writes.  No HIP call, no global state.
+// The arithmetic of libx3dstep (include/x3dstep.h) item by item and tensor by tensor, compiled into the .hip files (the
+// kernels) and step_host.cpp (the CPU twins): what a lane adds and in which order, the sum of a tensor's items, the
+// coefficient rule, the record's layout and what the one finishing thread writes; the plan of a walk, the element operations
+// of the two walks of step_priv.h and the item walk of one lane.  No HIP call, no global state.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -31,6 +32,11 @@ struct Part {
 struct alignas(16) Vec4 {
     float v[4];
 };
+
+// A 16-byte group of the two walks: one aligned load or store, held in registers.  Vector types, not structs of four: an
+// array of structs that a lane holds between its loads and its stores is left in private memory by the compiler.
+typedef float Float4 __attribute__((vector_size(16)));
+typedef uint32_t Bits4 __attribute__((vector_size(16)));
 
 STEP_HD uint64_t splitmix64(uint64_t z) {
     z += 0x9e3779b97f4a7c15ull;
@@ -214,13 +220,88 @@ STEP_HD float state_coef(const int64_t* state) {
 
 STEP_HD float scale_one(float x, float coef) { return x * coef; }
 
-// -- the guarded update (x3dstep_apply) ------------------------------------------------------------------------------------
-struct ApplyArgs {
-    float lr, mu, wd, gs;
-    int first;
+// -- the plan and the element operations of the walks ----------------------------------------------------------------------
+// How a run of n elements in one or more buffers is cut: `head` elements one by one, `groups` 16-byte groups, then the
+// tail, when all the addresses are congruent mod 16 (`same`; r: the residue of any of them); otherwise n elements one by
+// one (vec says which: head, groups and tail are then never used).
+struct Plan {
+    bool vec;
+    int64_t head, groups, tail;      // tail: the index of the first element after the groups
 };
 
-// What every thread of the apply kernel reads before anything else: the decision and the coefficient of the step measured
+STEP_HD Plan walk_plan(uintptr_t r, bool same, int64_t n) {
+    Plan p;
+    p.vec = same;
+    p.head = (int64_t)(((16 - r) & 15) >> 2);
+    if (p.head > n) p.head = n;
+    p.groups = (n - p.head) >> 2;
+    p.tail = p.head + 4 * p.groups;
+    return p;
+}
+
+STEP_HD uintptr_t mod16(const void* p) { return (uintptr_t)p & 15; }
+
+// An element operation Op of the flat walk (step_priv.h; flat_host of step_host.cpp) and of the item walk (item_lane) says:
+//   Elem, Group       what it works on, float or bits, and sixteen bytes of it;
+//   kBufs             how many buffers it takes; kLoads, kStores: the masks of those a walk loads and of those it stores
+//                     (a buffer the operation only reads is never stored, one it only writes never loaded);
+//   begin(counting)   what every thread reads before anything else (uniform loads); false: the launch does nothing.
+//                     `counting` is true in the one thread that writes the state's counters;
+//   one(x)            the rule on one element of each buffer, x[kBufs];
+//   mode              (item walk only) which end of an item is buffer 0: X3DSTEP_KEEP_SAVE, the snapshot's.
+// A unit of a walk is an element or a group; on a group the rule runs on its four elements in order.
+template <class Op, class Unit>
+STEP_HD void walk_unit(const Op& op, Unit (&v)[Op::kBufs]) {
+    if constexpr (sizeof(Unit) == sizeof(typename Op::Elem)) {
+        op.one(v);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            typename Op::Elem x[Op::kBufs];
+#pragma unroll
+            for (int b = 0; b < Op::kBufs; ++b)
+                if (Op::kLoads >> b & 1) x[b] = v[b][e];
+            op.one(x);
+#pragma unroll
+            for (int b = 0; b < Op::kBufs; ++b)
+                if (Op::kStores >> b & 1) v[b][e] = x[b];
+        }
+    }
+}
+
+// unit `at` of the buffers p: load, rule, store
+template <class Op, class Unit>
+STEP_HD void walk_at(const Op& op, Unit* const* p, int64_t at) {
+    Unit v[Op::kBufs];
+#pragma unroll
+    for (int b = 0; b < Op::kBufs; ++b)
+        if (Op::kLoads >> b & 1) v[b] = p[b][at];
+    walk_unit(op, v);
+#pragma unroll
+    for (int b = 0; b < Op::kBufs; ++b)
+        if (Op::kStores >> b & 1) p[b][at] = v[b];
+}
+
+// the flat buffers of an operation and their plan
+template <class Op>
+struct Bufs {
+    typename Op::Elem* p[Op::kBufs];
+};
+
+template <class Op>
+STEP_HD Plan flat_plan(const Bufs<Op>& bufs, int64_t n) {
+    bool same = true;
+    for (int b = 1; b < Op::kBufs; ++b) same = same && mod16(bufs.p[b]) == mod16(bufs.p[0]);
+    return walk_plan(mod16(bufs.p[0]), same, n);
+}
+
+// -- the guarded update (x3dstep_apply, x3dstep_apply_groups) --------------------------------------------------------------
+struct SgdArgs {
+    float lr, mu, wd, gs;
+    int first, nesterov;
+};
+
+// What every thread of an update kernel reads before anything else: the decision and the coefficient of the step measured
 // last.  go: the counter is not 0 (something was measured); skip: that step's gradient had a non-finite element.
 struct Decision {
     bool go, skip;
@@ -236,18 +317,6 @@ STEP_HD Decision apply_decision(const int64_t* state, const void* ring, int R, i
     return d;
 }
 
-// one element: the multiply of the scale launch, then the arithmetic of the SGD kernel of libx3dhip.so (csrc/bn.hip
-// sgd_kernel), each operation rounded once (both libraries compile with -ffp-contract=off)
-STEP_HD void apply_one(float& w, float g, float& m, float coef, const ApplyArgs& a) {
-    const float gi = coef == 1.0f ? g : scale_one(g, coef);
-    const float t = gi * a.gs;
-    const float gg = fmaf(a.wd, w, t);
-    const float mi = a.first ? gg : fmaf(a.mu, m, gg);
-    const float step = a.lr * mi;
-    m = mi;
-    w = w - step;
-}
-
 // what the one counting thread writes
 STEP_HD void apply_counters(int64_t* state, bool skip) {
     state[X3DSTEP_S_SKIP] = skip ? 1 : 0;
@@ -259,43 +328,47 @@ STEP_HD void apply_counters(int64_t* state, bool skip) {
     }
 }
 
-// How the flat buffers are walked: `head` elements one by one, `groups` 16-byte groups, then the tail, when the three
-// addresses are congruent mod 16; otherwise n elements one by one (groups = 0, head = n is never used: vec says which).
-struct ApplyPlan {
-    bool vec;
-    int64_t head, groups, tail;      // tail: the index of the first element after the groups
-};
-
-STEP_HD ApplyPlan apply_plan(const void* w, const void* g, const void* m, int64_t n) {
-    ApplyPlan p;
-    const uintptr_t a = (uintptr_t)w & 15;
-    p.vec = a == ((uintptr_t)g & 15) && a == ((uintptr_t)m & 15);
-    p.head = (int64_t)(((16 - a) & 15) >> 2);
-    if (p.head > n) p.head = n;
-    p.groups = (n - p.head) >> 2;
-    p.tail = p.head + 4 * p.groups;
-    return p;
+// The start of an update launch: false when nothing was measured or the step is skipped, else the coefficient.  The
+// counters are words no thread of the grid reads here.
+STEP_HD bool apply_begin(int64_t* state, const void* ring, int R, int S, bool counting, float* coef) {
+    const Decision d = apply_decision(state, ring, R, S);
+    if (!d.go) return false;
+    if (counting) apply_counters(state, d.skip);
+    *coef = d.coef;
+    return !d.skip;
 }
 
-// -- the grouped update (x3dstep_apply_groups) -----------------------------------------------------------------------------
-struct GroupArgs {
-    float lr, mu, wd, gs;
-    int first, nesterov;
-};
-
-// one element: apply_one with the tensor's own rate and decay, and the Nesterov look-ahead.  With nesterov == 0, lr_s == lr
-// and wd_s == wd this is apply_one operation for operation.
-STEP_HD void group_one(float& w, float g, float& m, float coef, const GroupArgs& a, float lr_s, float wd_s) {
+// One element: the multiply of the scale launch, then the arithmetic of the SGD kernel of libx3dhip.so (csrc/bn.hip
+// sgd_kernel) with the tensor's own rate and decay and the Nesterov look-ahead, each operation rounded once (both libraries
+// compile with -ffp-contract=off).  kPlain: no Nesterov term, whatever a.nesterov says.
+template <bool kPlain = false>
+STEP_HD void sgd_one(float& w, float g, float& m, float coef, const SgdArgs& a, float lr_s, float wd_s) {
     const float gi = coef == 1.0f ? g : scale_one(g, coef);
     const float t = gi * a.gs;
     const float gg = fmaf(wd_s, w, t);
     const float mi = a.first ? gg : fmaf(a.mu, m, gg);
-    const float u = a.nesterov ? fmaf(a.mu, mi, gg) : mi;
+    const float u = !kPlain && a.nesterov ? fmaf(a.mu, mi, gg) : mi;
     const float step = lr_s * u;
     m = mi;
     w = w - step;
 }
 
+// x3dstep_apply over w, g, m: every tensor at the rate lr and the decay wd, no Nesterov term
+struct ApplyOp {
+    typedef float Elem;
+    typedef Float4 Group;
+    static constexpr int kBufs = 3;
+    static constexpr unsigned kLoads = 7, kStores = 5;
+    int64_t* state;
+    const void* ring;
+    int R, S;
+    SgdArgs a;
+    float coef;
+    STEP_HD_MEMBER bool begin(bool counting) { return apply_begin(state, ring, R, S, counting, &coef); }
+    STEP_HD_MEMBER void one(float (&x)[3]) const { sgd_one<true>(x[0], x[1], x[2], coef, a, a.lr, a.wd); }
+};
+
+// -- the grouped update (x3dstep_apply_groups) -----------------------------------------------------------------------------
 // a scale the tensor rule takes: finite and not negative (a NaN fails both comparisons)
 STEP_HD bool group_scale_ok(float s) { return s >= 0.0f && s <= 3.402823466e38f; }
 
@@ -308,7 +381,7 @@ struct GroupItem {
 // Item i resolved against the hyper table.  The tests are those x3dstep_apply_groups_host refuses a call for; the kernel
 // makes them per item, since the tables it reads are device memory nobody has checked.
 STEP_HD GroupItem group_resolve(const X3DStepItem* items, int64_t i, const X3DStepHyper* hyper, int S, int64_t n,
-                                const GroupArgs& a) {
+                                const SgdArgs& a) {
     GroupItem r = {0, 0, 0.0f, 0.0f};
     const X3DStepItem it = items[i];
     if (it.seg < 0 || it.seg >= S || it.len < 1 || it.len > X3DSTEP_ITEM || it.start < 0 || it.start > n - it.len) return r;
@@ -328,19 +401,16 @@ constexpr int kGroupBatches = X3DSTEP_ITEM / (4 * kLanes * kGroupPieces);      /
 // up to the 16-byte grid one by one (lane j the j-th), the 16-byte groups q = lane, lane + 64, .. in batches of
 // kGroupPieces (a batch's loads of w, g and m before its first store), then the tail one by one.  Otherwise the elements
 // j = lane, lane + 64, ...  Every element of the item is stored once; nothing outside it is read or written.
-STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, int lane, float coef, const GroupArgs& a) {
+STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, int lane, float coef, const SgdArgs& a) {
     float* wi = w + c.start;
     const float* gi = g + c.start;
     float* mi = m + c.start;
-    const uintptr_t r = (uintptr_t)wi & 15;
-    if (r != ((uintptr_t)gi & 15) || r != ((uintptr_t)mi & 15)) {
-        for (int j = lane; j < c.len; j += kLanes) group_one(wi[j], gi[j], mi[j], coef, a, c.lr_s, c.wd_s);
+    const Plan p = walk_plan(mod16(wi), mod16(wi) == mod16(gi) && mod16(wi) == mod16(mi), c.len);
+    if (!p.vec) {
+        for (int j = lane; j < c.len; j += kLanes) sgd_one(wi[j], gi[j], mi[j], coef, a, c.lr_s, c.wd_s);
         return;
     }
-    int head = (int)(((16 - r) & 15) >> 2);
-    if (head > c.len) head = c.len;
-    const int groups = (c.len - head) >> 2;
-    const int tail = head + 4 * groups;
+    const int head = (int)p.head, groups = (int)p.groups, tail = (int)p.tail;
     Vec4* wu = (Vec4*)(wi + head);
     const Vec4* gu = (const Vec4*)(gi + head);
     Vec4* mu = (Vec4*)(mi + head);
@@ -362,14 +432,14 @@ STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, 
         for (int k = 0; k < kGroupPieces; ++k) {
             const int q = q0 + k * kLanes;
             if (q < groups) {
-                for (int e = 0; e < 4; ++e) group_one(wv[k].v[e], gv[k].v[e], mv[k].v[e], coef, a, c.lr_s, c.wd_s);
+                for (int e = 0; e < 4; ++e) sgd_one(wv[k].v[e], gv[k].v[e], mv[k].v[e], coef, a, c.lr_s, c.wd_s);
                 mu[q] = mv[k];
                 wu[q] = wv[k];
             }
         }
     }
-    if (lane < head) group_one(wi[lane], gi[lane], mi[lane], coef, a, c.lr_s, c.wd_s);
-    if (lane < c.len - tail) group_one(wi[tail + lane], gi[tail + lane], mi[tail + lane], coef, a, c.lr_s, c.wd_s);
+    if (lane < head) sgd_one(wi[lane], gi[lane], mi[lane], coef, a, c.lr_s, c.wd_s);
+    if (lane < c.len - tail) sgd_one(wi[tail + lane], gi[tail + lane], mi[tail + lane], coef, a, c.lr_s, c.wd_s);
 }
 
 // -- the kept buffers (x3dstep_keep) ---------------------------------------------------------------------------------------
@@ -403,24 +473,52 @@ STEP_HD KeepCopy keep_resolve(const X3DStepKeep* table, int nbuf, const X3DStepI
     return c;
 }
 
-// What lane `lane` of the item's wave copies: the 16-byte groups q = lane, lane + 64, .. when both addresses are 16-byte
-// aligned (all loads before the first store), the elements j = lane, lane + 64, .. otherwise and for the last len mod 4.
-STEP_HD void keep_lane(const KeepCopy& c, int lane) {
-    const bool vec = (((uintptr_t)c.dst | (uintptr_t)c.src) & 15) == 0;
+// The item walk: what lane `lane` of the item's wave does with buffers 0 (c.dst) and 1 (c.src) of a two-buffer operation.
+// The 16-byte groups q = lane, lane + 64, .. when both addresses are 16-byte aligned (all of a lane's loads before its first
+// store), the elements j = lane, lane + 64, .. otherwise and for the last len mod 4.
+template <class Op>
+STEP_HD void item_lane(const Op& op, const KeepCopy& c, int lane) {
+    static_assert(Op::kBufs == 2, "the item walk takes two buffers");
+    typedef typename Op::Elem Elem;
+    typedef typename Op::Group Group;
+    Elem* const p[2] = {(Elem*)c.dst, (Elem*)c.src};
+    Group* const u[2] = {(Group*)c.dst, (Group*)c.src};
+    const bool vec = (mod16(c.dst) | mod16(c.src)) == 0;
     const int groups = vec ? c.len >> 2 : 0;
-    Vec4 v[kKeepPieces];
+    Group v[kKeepPieces][2];
 #pragma unroll
     for (int k = 0; k < kKeepPieces; ++k) {
         const int q = lane + k * kLanes;
-        if (q < groups) v[k] = ((const Vec4*)c.src)[q];
+        if (q < groups) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                if (Op::kLoads >> b & 1) v[k][b] = u[b][q];
+        }
     }
 #pragma unroll
     for (int k = 0; k < kKeepPieces; ++k) {
         const int q = lane + k * kLanes;
-        if (q < groups) ((Vec4*)c.dst)[q] = v[k];
+        if (q < groups) {
+            walk_unit(op, v[k]);
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                if (Op::kStores >> b & 1) u[b][q] = v[k][b];
+        }
     }
-    for (int j = 4 * groups + lane; j < c.len; j += kLanes) c.dst[j] = c.src[j];
+    for (int j = 4 * groups + lane; j < c.len; j += kLanes) walk_at(op, p, (int64_t)j);
 }
+
+// x3dstep_keep: buffer 0 <- buffer 1, on bits.  A restore reads the skip word first.
+struct CopyOp {
+    typedef uint32_t Elem;
+    typedef Bits4 Group;
+    static constexpr int kBufs = 2;
+    static constexpr unsigned kLoads = 2, kStores = 1;
+    const int64_t* state;
+    int mode;
+    STEP_HD_MEMBER bool begin(bool) { return mode != X3DSTEP_KEEP_RESTORE || state[X3DSTEP_S_SKIP] == 1; }
+    STEP_HD_MEMBER void one(uint32_t (&x)[2]) const { x[0] = x[1]; }
+};
 
 // -- the weight average (x3dstep_ema, x3dstep_ema_keep) --------------------------------------------------------------------
 // The number of the update being averaged: the host's `count`, plus (with a state) the updates applied so far, which
@@ -455,78 +553,44 @@ STEP_HD void ema_one(float& e, float w, const EmaCoef& c) {
     e = fmaf(c.d, e, p);
 }
 
-// the plan of two flat buffers (x3dstep_ema, x3dstep_swap): 16-byte groups when both addresses are congruent mod 16
-STEP_HD ApplyPlan pair_plan(const void* a, const void* b, int64_t n) {
-    ApplyPlan p;
-    const uintptr_t r = (uintptr_t)a & 15;
-    p.vec = r == ((uintptr_t)b & 15);
-    p.head = (int64_t)(((16 - r) & 15) >> 2);
-    if (p.head > n) p.head = n;
-    p.groups = (n - p.head) >> 2;
-    p.tail = p.head + 4 * p.groups;
-    return p;
-}
-
-// What lane `lane` of the item's wave averages: c.dst is the averaged snapshot's part of the item and c.src the live
-// buffer's (keep_resolve with X3DSTEP_KEEP_SAVE).  The walk of keep_lane: all loads of the groups before the first store.
-STEP_HD void ema_lane(const KeepCopy& c, int lane, const EmaCoef& k) {
-    const bool vec = (((uintptr_t)c.dst | (uintptr_t)c.src) & 15) == 0;
-    const int groups = vec ? c.len >> 2 : 0;
-    Vec4 e[kKeepPieces], w[kKeepPieces];
-#pragma unroll
-    for (int i = 0; i < kKeepPieces; ++i) {
-        const int q = lane + i * kLanes;
-        if (q < groups) {
-            e[i] = ((const Vec4*)c.dst)[q];
-            w[i] = ((const Vec4*)c.src)[q];
-        }
+// x3dstep_ema, x3dstep_ema_keep over e (the average), w: every thread reads the three state words and derives k and the
+// two coefficients itself
+struct EmaOp {
+    typedef float Elem;
+    typedef Float4 Group;
+    static constexpr int kBufs = 2;
+    static constexpr unsigned kLoads = 3, kStores = 1;
+    const int64_t* state;
+    int64_t count;
+    float decay;
+    int warmup;
+    EmaCoef c;
+    static constexpr int mode = X3DSTEP_KEEP_SAVE;
+    STEP_HD_MEMBER bool begin(bool) {
+        if (ema_skips(state)) return false;
+        const int64_t k = ema_count(state, count);
+        if (k <= 0) return false;
+        c = ema_coef(k, decay, warmup);
+        return true;
     }
-#pragma unroll
-    for (int i = 0; i < kKeepPieces; ++i) {
-        const int q = lane + i * kLanes;
-        if (q < groups) {
-            for (int x = 0; x < 4; ++x) ema_one(e[i].v[x], w[i].v[x], k);
-            ((Vec4*)c.dst)[q] = e[i];
-        }
-    }
-    for (int j = 4 * groups + lane; j < c.len; j += kLanes) ema_one(c.dst[j], c.src[j], k);
-}
+    STEP_HD_MEMBER void one(float (&x)[2]) const { ema_one(x[0], x[1], c); }
+};
 
 // -- the exchange (x3dstep_swap, x3dstep_swap_keep) ------------------------------------------------------------------------
 // Bits, not floats: no operation that could quieten a NaN or lose a payload ever sees the values.
-typedef uint32_t Bits4 __attribute__((vector_size(16)));      // one 16-byte load or store, in registers
-
-STEP_HD void swap_one(uint32_t& a, uint32_t& b) {
-    const uint32_t t = a;
-    a = b;
-    b = t;
-}
-
-// what lane `lane` of the item's wave exchanges: the walk of keep_lane, both sides loaded before the first store
-STEP_HD void swap_lane(const KeepCopy& c, int lane) {
-    const bool vec = (((uintptr_t)c.dst | (uintptr_t)c.src) & 15) == 0;
-    const int groups = vec ? c.len >> 2 : 0;
-    uint32_t* a = (uint32_t*)c.dst;
-    uint32_t* b = (uint32_t*)c.src;
-    Bits4 x[kKeepPieces], y[kKeepPieces];
-#pragma unroll
-    for (int i = 0; i < kKeepPieces; ++i) {
-        const int q = lane + i * kLanes;
-        if (q < groups) {
-            x[i] = ((const Bits4*)a)[q];
-            y[i] = ((const Bits4*)b)[q];
-        }
+struct SwapOp {
+    typedef uint32_t Elem;
+    typedef Bits4 Group;
+    static constexpr int kBufs = 2;
+    static constexpr unsigned kLoads = 3, kStores = 3;
+    static constexpr int mode = X3DSTEP_KEEP_SAVE;
+    STEP_HD_MEMBER bool begin(bool) { return true; }
+    STEP_HD_MEMBER void one(uint32_t (&x)[2]) const {
+        const uint32_t t = x[0];
+        x[0] = x[1];
+        x[1] = t;
     }
-#pragma unroll
-    for (int i = 0; i < kKeepPieces; ++i) {
-        const int q = lane + i * kLanes;
-        if (q < groups) {
-            ((Bits4*)a)[q] = y[i];
-            ((Bits4*)b)[q] = x[i];
-        }
-    }
-    for (int j = 4 * groups + lane; j < c.len; j += kLanes) swap_one(a[j], b[j]);
-}
+};
 
 // -- precise BN statistics (x3dstep_pbn_accum, x3dstep_pbn_finish) ---------------------------------------------------------
 // One accumulator per channel: the count of cells, the running mean of the cell means, the sum of squared deviations of

@@ -1,9 +1,9 @@
 // The host's part of libx3dstep (include/x3dstep.h): error text, sizes, the item-table builder and the *_host twins: the
-// launches of step.hip run serially through the same step_core.h.  Plain C++, no HIP call.
+// launches of the .hip files run serially through the same step_core.h, the two walks included.  Plain C++, no HIP call.
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "step_core.h"
+#include "step_priv.h"
 
 static thread_local char g_err[512] = "";
 
@@ -68,6 +68,65 @@ extern "C" int64_t x3dstep_build_items(const int64_t* seg_off, int S, X3DStepIte
         return X3DSTEP_EINVAL;
     }
     return c;
+}
+
+static bool ranges_overlap(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+    return x < y + bytes && y < x + bytes;
+}
+
+// The flat walk of step_priv.h, serially: the plan decides which element goes through a 16-byte group; the arithmetic is
+// per element.
+template <class Op>
+static void flat_host(const Op& op, const x3ds::Bufs<Op>& bufs, int64_t n) {
+    using namespace x3ds;
+    const Plan plan = flat_plan(bufs, n);
+    if (!plan.vec) {
+        for (int64_t i = 0; i < n; ++i) walk_at(op, bufs.p, i);
+        return;
+    }
+    typename Op::Group* u[Op::kBufs];
+    for (int b = 0; b < Op::kBufs; ++b) u[b] = (typename Op::Group*)(bufs.p[b] + plan.head);
+    for (int64_t i = 0; i < plan.head; ++i) walk_at(op, bufs.p, i);
+    for (int64_t q = 0; q < plan.groups; ++q) walk_at(op, u, q);
+    for (int64_t i = plan.tail; i < n; ++i) walk_at(op, bufs.p, i);
+}
+
+// The tables are host memory in a twin: refuse the call for what the kernel would leave out item by item.
+static int table_host_ok(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
+                         float* snap, int64_t snap_n) {
+    using namespace x3ds;
+    for (int b = 0; b < nbuf; ++b) {
+        const X3DStepKeep k = table[b];
+        if (k.addr == 0 || (k.addr & 3) != 0 || k.len < 1 || k.offset < 0 || k.offset > snap_n - k.len ||
+            (b > 0 && k.offset < table[b - 1].offset + table[b - 1].len)) {
+            x3dstep_set_error("%s: buffer %d: a null or unaligned address, or a range outside snap or over the buffer before "
+                              "it", who, b);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    for (int64_t i = 0; i < nitems; ++i) {
+        bool bad;
+        (void)keep_resolve(table, nbuf, items, i, snap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
+        if (bad) {
+            x3dstep_set_error("%s: item %lld lies outside snap or outside its buffer's range", who, (long long)i);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    return X3DSTEP_OK;
+}
+
+// The item walk of step_priv.h, serially: item after item, lane after lane.
+template <class Op>
+static void items_host(const Op& op, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
+                       float* snap, int64_t snap_n) {
+    using namespace x3ds;
+    for (int64_t i = 0; i < nitems; ++i) {
+        bool bad;
+        const KeepCopy c = keep_resolve(table, nbuf, items, i, snap, snap_n, op.mode, &bad);
+        if (c.len > 0)
+            for (int l = 0; l < kLanes; ++l) item_lane(op, c, l);
+    }
 }
 
 // the argument checks x3dstep_observe and its twin share (step.hip calls it too)
@@ -184,36 +243,17 @@ extern "C" int x3dstep_apply_host(float* w, const float* g, float* m, int64_t n,
     using namespace x3ds;
     const int rc = x3dstep_check_apply("x3dstep_apply_host", w, g, m, n, state, ring, R, S);
     if (rc) return rc;
-    const Decision d = apply_decision(state, ring, R, S);
-    if (!d.go) {
+    if (!apply_decision(state, ring, R, S).go) {
         x3dstep_set_error("x3dstep_apply_host: the state's step counter is 0: nothing has been measured");
         return X3DSTEP_EINVAL;
     }
-    apply_counters(state, d.skip);
-    if (d.skip) return X3DSTEP_OK;
-    const ApplyArgs a = {lr, momentum, weight_decay, grad_scale, first ? 1 : 0};
-    // the kernel's walk: the plan decides which element goes through a 16-byte group; the arithmetic is per element
-    const ApplyPlan plan = apply_plan(w, g, m, n);
-    if (plan.vec) {
-        for (int64_t i = 0; i < plan.head; ++i) apply_one(w[i], g[i], m[i], d.coef, a);
-        for (int64_t q = 0; q < plan.groups; ++q) {
-            Vec4 wv = *(Vec4*)(w + plan.head + 4 * q), mv = *(Vec4*)(m + plan.head + 4 * q);
-            const Vec4 gv = *(const Vec4*)(g + plan.head + 4 * q);
-            for (int e = 0; e < 4; ++e) apply_one(wv.v[e], gv.v[e], mv.v[e], d.coef, a);
-            *(Vec4*)(m + plan.head + 4 * q) = mv;
-            *(Vec4*)(w + plan.head + 4 * q) = wv;
-        }
-        for (int64_t i = plan.tail; i < n; ++i) apply_one(w[i], g[i], m[i], d.coef, a);
-    } else {
-        for (int64_t i = 0; i < n; ++i) apply_one(w[i], g[i], m[i], d.coef, a);
-    }
+    ApplyOp op = {state, ring, R, S, {lr, momentum, weight_decay, grad_scale, first ? 1 : 0, 0}, 1.0f};
+    if (op.begin(true)) flat_host(op, Bufs<ApplyOp>{{w, (float*)g, m}}, n);
     return X3DSTEP_OK;
 }
 
 // -- the grouped update -----------------------------------------------------------------------------------------------------
 extern "C" size_t x3dstep_hyper_bytes(void) { return sizeof(X3DStepHyper); }
-
-static bool ranges_overlap(const float* a, const float* b, int64_t n);
 
 // the argument checks x3dstep_apply_groups and its twin share (no pointer is followed: the tables may be device memory)
 int x3dstep_check_groups(const char* who, const float* w, const float* g, const float* m, int64_t n, const X3DStepItem* items,
@@ -277,16 +317,13 @@ extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int
     }
     float coef = 1.0f;
     if (state) {
-        const Decision d = apply_decision(state, ring, R, S);
-        if (!d.go) {
+        if (!apply_decision(state, ring, R, S).go) {
             x3dstep_set_error("%s: the state's step counter is 0: nothing has been measured", who);
             return X3DSTEP_EINVAL;
         }
-        apply_counters(state, d.skip);
-        if (d.skip) return X3DSTEP_OK;
-        coef = d.coef;
+        if (!apply_begin(state, ring, R, S, true, &coef)) return X3DSTEP_OK;
     }
-    const GroupArgs a = {lr, momentum, weight_decay, grad_scale, first, nesterov};
+    const SgdArgs a = {lr, momentum, weight_decay, grad_scale, first, nesterov};
     for (int64_t i = 0; i < nitems; ++i) {
         const GroupItem c = group_resolve(items, i, hyper, S, n, a);
         if (c.len > 0)
@@ -295,67 +332,20 @@ extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int
     return X3DSTEP_OK;
 }
 
-// the argument checks x3dstep_keep and its twin share (no pointer is followed: the tables may be device memory)
-int x3dstep_check_keep(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
-                       const float* snap, int64_t snap_n, const int64_t* state, int mode) {
-    if (!table || !items || !snap || !state || nbuf < 1 || nbuf > X3DSTEP_MAX_SEGMENTS || nitems < nbuf ||
-        nitems > X3DSTEP_MAX_ITEMS || snap_n < 1 || (mode != X3DSTEP_KEEP_SAVE && mode != X3DSTEP_KEEP_RESTORE) ||
-        (((uintptr_t)table | (uintptr_t)items | (uintptr_t)state) & 7) != 0 || ((uintptr_t)snap & 3) != 0) {
-        x3dstep_set_error("%s: null or unaligned pointer, nbuf %d outside 1 .. %d, nitems %lld outside nbuf .. %d, snap_n %lld "
-                          "< 1 or mode %d", who, nbuf, X3DSTEP_MAX_SEGMENTS, (long long)nitems, X3DSTEP_MAX_ITEMS,
-                          (long long)snap_n, mode);
-        return X3DSTEP_EINVAL;
-    }
-    return X3DSTEP_OK;
-}
-
-// The tables are host memory in a twin: refuse the call for what the kernel would leave out item by item.
-static int table_host_ok(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
-                         float* snap, int64_t snap_n) {
-    using namespace x3ds;
-    for (int b = 0; b < nbuf; ++b) {
-        const X3DStepKeep k = table[b];
-        if (k.addr == 0 || (k.addr & 3) != 0 || k.len < 1 || k.offset < 0 || k.offset > snap_n - k.len ||
-            (b > 0 && k.offset < table[b - 1].offset + table[b - 1].len)) {
-            x3dstep_set_error("%s: buffer %d: a null or unaligned address, or a range outside snap or over the buffer before "
-                              "it", who, b);
-            return X3DSTEP_EINVAL;
-        }
-    }
-    for (int64_t i = 0; i < nitems; ++i) {
-        bool bad;
-        (void)keep_resolve(table, nbuf, items, i, snap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
-        if (bad) {
-            x3dstep_set_error("%s: item %lld lies outside snap or outside its buffer's range", who, (long long)i);
-            return X3DSTEP_EINVAL;
-        }
-    }
-    return X3DSTEP_OK;
-}
-
 extern "C" int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
                                  int64_t snap_n, const int64_t* state, int mode) {
     using namespace x3ds;
-    const int rc = x3dstep_check_keep("x3dstep_keep_host", table, nbuf, items, nitems, snap, snap_n, state, mode);
+    const char* who = "x3dstep_keep_host";
+    const int rc = x3dstep_check_table(who, table, nbuf, items, nitems, snap, snap_n, state, true, mode, 0.0f);
     if (rc) return rc;
-    const int rt = table_host_ok("x3dstep_keep_host", table, nbuf, items, nitems, snap, snap_n);
+    const int rt = table_host_ok(who, table, nbuf, items, nitems, snap, snap_n);
     if (rt) return rt;
-    if (mode == X3DSTEP_KEEP_RESTORE && state[X3DSTEP_S_SKIP] != 1) return X3DSTEP_OK;
-    for (int64_t i = 0; i < nitems; ++i) {
-        bool bad;
-        const KeepCopy c = keep_resolve(table, nbuf, items, i, snap, snap_n, mode, &bad);
-        if (c.len > 0)
-            for (int l = 0; l < kLanes; ++l) keep_lane(c, l);
-    }
+    CopyOp op = {state, mode};
+    if (op.begin(false)) items_host(op, table, nbuf, items, nitems, snap, snap_n);
     return X3DSTEP_OK;
 }
 
 // -- the weight average and the exchange ----------------------------------------------------------------------------------
-static bool ranges_overlap(const float* a, const float* b, int64_t n) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * 4;
-    return x < y + bytes && y < x + bytes;
-}
-
 // the argument checks x3dstep_ema and its twin share (no pointer is followed)
 int x3dstep_check_ema(const char* who, const float* e, const float* w, int64_t n, const int64_t* state, float decay) {
     if (!e || !w || n < 1 || n > ((int64_t)1 << 40) || (((uintptr_t)e | (uintptr_t)w) & 3) != 0 || ((uintptr_t)state & 7) != 0 ||
@@ -375,15 +365,17 @@ int x3dstep_check_swap(const char* who, const float* a, const float* b, int64_t 
     return X3DSTEP_OK;
 }
 
-// the argument checks of the table forms (state may be null; x3dstep_swap_keep passes decay 0)
+// The argument checks of the table forms.  need_state: x3dstep_keep, which reads the state whatever the mode (elsewhere it
+// may be null); the others pass X3DSTEP_KEEP_SAVE for mode, and x3dstep_keep and x3dstep_swap_keep 0 for decay.
 int x3dstep_check_table(const char* who, const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems,
-                        const float* snap, int64_t snap_n, const int64_t* state, float decay) {
-    if (!table || !items || !snap || nbuf < 1 || nbuf > X3DSTEP_MAX_SEGMENTS || nitems < nbuf || nitems > X3DSTEP_MAX_ITEMS ||
-        snap_n < 1 || (((uintptr_t)table | (uintptr_t)items | (uintptr_t)state) & 7) != 0 || ((uintptr_t)snap & 3) != 0 ||
+                        const float* snap, int64_t snap_n, const int64_t* state, bool need_state, int mode, float decay) {
+    if (!table || !items || !snap || (need_state && !state) || nbuf < 1 || nbuf > X3DSTEP_MAX_SEGMENTS || nitems < nbuf ||
+        nitems > X3DSTEP_MAX_ITEMS || snap_n < 1 || (mode != X3DSTEP_KEEP_SAVE && mode != X3DSTEP_KEEP_RESTORE) ||
+        (((uintptr_t)table | (uintptr_t)items | (uintptr_t)state) & 7) != 0 || ((uintptr_t)snap & 3) != 0 ||
         !(decay >= 0.0f && decay < 1.0f)) {
         x3dstep_set_error("%s: null or unaligned pointer, nbuf %d outside 1 .. %d, nitems %lld outside nbuf .. %d, snap_n %lld "
-                          "< 1 or decay %g outside [0, 1)", who, nbuf, X3DSTEP_MAX_SEGMENTS, (long long)nitems,
-                          X3DSTEP_MAX_ITEMS, (long long)snap_n, (double)decay);
+                          "< 1, mode %d or decay %g outside [0, 1)", who, nbuf, X3DSTEP_MAX_SEGMENTS, (long long)nitems,
+                          X3DSTEP_MAX_ITEMS, (long long)snap_n, mode, (double)decay);
         return X3DSTEP_EINVAL;
     }
     return X3DSTEP_OK;
@@ -401,44 +393,23 @@ extern "C" int x3dstep_ema_host(float* e, const float* w, int64_t n, const int64
     using namespace x3ds;
     const int rc = x3dstep_check_ema("x3dstep_ema_host", e, w, n, state, decay);
     if (rc) return rc;
-    const int64_t k = ema_count_host("x3dstep_ema_host", state, count);
-    if (k == 0) return X3DSTEP_EINVAL;
-    if (ema_skips(state)) return X3DSTEP_OK;
-    const EmaCoef c = ema_coef(k, decay, warmup ? 1 : 0);
-    // the kernel's walk: the plan decides which element goes through a 16-byte group; the arithmetic is per element
-    const ApplyPlan plan = pair_plan(e, w, n);
-    if (plan.vec) {
-        for (int64_t i = 0; i < plan.head; ++i) ema_one(e[i], w[i], c);
-        for (int64_t q = 0; q < plan.groups; ++q) {
-            Vec4 ev = *(Vec4*)(e + plan.head + 4 * q);
-            const Vec4 wv = *(const Vec4*)(w + plan.head + 4 * q);
-            for (int x = 0; x < 4; ++x) ema_one(ev.v[x], wv.v[x], c);
-            *(Vec4*)(e + plan.head + 4 * q) = ev;
-        }
-        for (int64_t i = plan.tail; i < n; ++i) ema_one(e[i], w[i], c);
-    } else {
-        for (int64_t i = 0; i < n; ++i) ema_one(e[i], w[i], c);
-    }
+    if (ema_count_host("x3dstep_ema_host", state, count) == 0) return X3DSTEP_EINVAL;
+    EmaOp op = {state, count, decay, warmup ? 1 : 0, {0.0f, 0.0f}};
+    if (op.begin(false)) flat_host(op, Bufs<EmaOp>{{e, (float*)w}}, n);
     return X3DSTEP_OK;
 }
 
 extern "C" int x3dstep_ema_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* esnap,
                                      int64_t snap_n, const int64_t* state, int64_t count, float decay, int warmup) {
     using namespace x3ds;
-    const int rc = x3dstep_check_table("x3dstep_ema_keep_host", table, nbuf, items, nitems, esnap, snap_n, state, decay);
+    const char* who = "x3dstep_ema_keep_host";
+    const int rc = x3dstep_check_table(who, table, nbuf, items, nitems, esnap, snap_n, state, false, X3DSTEP_KEEP_SAVE, decay);
     if (rc) return rc;
-    const int rt = table_host_ok("x3dstep_ema_keep_host", table, nbuf, items, nitems, esnap, snap_n);
+    const int rt = table_host_ok(who, table, nbuf, items, nitems, esnap, snap_n);
     if (rt) return rt;
-    const int64_t k = ema_count_host("x3dstep_ema_keep_host", state, count);
-    if (k == 0) return X3DSTEP_EINVAL;
-    if (ema_skips(state)) return X3DSTEP_OK;
-    const EmaCoef c = ema_coef(k, decay, warmup ? 1 : 0);
-    for (int64_t i = 0; i < nitems; ++i) {
-        bool bad;
-        const KeepCopy kc = keep_resolve(table, nbuf, items, i, esnap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
-        if (kc.len > 0)
-            for (int l = 0; l < kLanes; ++l) ema_lane(kc, l, c);
-    }
+    if (ema_count_host(who, state, count) == 0) return X3DSTEP_EINVAL;
+    EmaOp op = {state, count, decay, warmup ? 1 : 0, {0.0f, 0.0f}};
+    if (op.begin(false)) items_host(op, table, nbuf, items, nitems, esnap, snap_n);
     return X3DSTEP_OK;
 }
 
@@ -446,36 +417,19 @@ extern "C" int x3dstep_swap_host(float* a, float* b, int64_t n) {
     using namespace x3ds;
     const int rc = x3dstep_check_swap("x3dstep_swap_host", a, b, n);
     if (rc) return rc;
-    uint32_t* x = (uint32_t*)a;
-    uint32_t* y = (uint32_t*)b;
-    const ApplyPlan plan = pair_plan(a, b, n);
-    if (plan.vec) {
-        for (int64_t i = 0; i < plan.head; ++i) swap_one(x[i], y[i]);
-        for (int64_t q = 0; q < plan.groups; ++q) {
-            const Bits4 xv = *(const Bits4*)(x + plan.head + 4 * q), yv = *(const Bits4*)(y + plan.head + 4 * q);
-            *(Bits4*)(x + plan.head + 4 * q) = yv;
-            *(Bits4*)(y + plan.head + 4 * q) = xv;
-        }
-        for (int64_t i = plan.tail; i < n; ++i) swap_one(x[i], y[i]);
-    } else {
-        for (int64_t i = 0; i < n; ++i) swap_one(x[i], y[i]);
-    }
+    flat_host(SwapOp{}, Bufs<SwapOp>{{(uint32_t*)a, (uint32_t*)b}}, n);
     return X3DSTEP_OK;
 }
 
 extern "C" int x3dstep_swap_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
                                       int64_t snap_n) {
     using namespace x3ds;
-    const int rc = x3dstep_check_table("x3dstep_swap_keep_host", table, nbuf, items, nitems, snap, snap_n, nullptr, 0.0f);
+    const char* who = "x3dstep_swap_keep_host";
+    const int rc = x3dstep_check_table(who, table, nbuf, items, nitems, snap, snap_n, nullptr, false, X3DSTEP_KEEP_SAVE, 0.0f);
     if (rc) return rc;
-    const int rt = table_host_ok("x3dstep_swap_keep_host", table, nbuf, items, nitems, snap, snap_n);
+    const int rt = table_host_ok(who, table, nbuf, items, nitems, snap, snap_n);
     if (rt) return rt;
-    for (int64_t i = 0; i < nitems; ++i) {
-        bool bad;
-        const KeepCopy kc = keep_resolve(table, nbuf, items, i, snap, snap_n, X3DSTEP_KEEP_SAVE, &bad);
-        if (kc.len > 0)
-            for (int l = 0; l < kLanes; ++l) swap_lane(kc, l);
-    }
+    items_host(SwapOp{}, table, nbuf, items, nitems, snap, snap_n);
     return X3DSTEP_OK;
 }
 

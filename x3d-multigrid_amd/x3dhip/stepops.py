@@ -79,14 +79,49 @@ class StepTables:
             self.d_seg_item = torch.from_numpy(self.seg_item).to(self.device)
 
 
-def _check_device(who, g, tables, workspace, state, ring, R):
-    dev = tables.device
+def _need_flat(who, name, t, n, dev):
+    """`t` must be a contiguous float32 [n] tensor on `dev`."""
+    if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.dim() == 1
+            and t.is_contiguous() and t.numel() == n):
+        raise ValueError("%s: %s must be a contiguous float32 [%d] on %s" % (who, name, n, dev))
+
+
+def _need_flat_np(who, name, a, n, writeable=False):
+    """... and the numpy form: a contiguous float32 [n] array, writeable where the twin stores to it."""
+    if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 1 and a.size == n and a.flags.c_contiguous
+            and (a.flags.writeable or not writeable)):
+        raise ValueError("%s: %s must be a %scontiguous float32 [%d]" % (who, name, "writeable " if writeable else "", n))
+
+
+def _need_state(who, state, dev, optional=False):
+    """`state` must be the contiguous int64 [STATE_WORDS] tensor on `dev` (optional: or None)."""
+    if state is None and optional:
+        return
+    if (not isinstance(state, torch.Tensor) or state.device != dev or state.dtype != torch.int64
+            or state.numel() != STATE_WORDS or not state.is_contiguous()):
+        raise ValueError("%s: state must be int64 [%d] on %s%s" % (who, STATE_WORDS, dev, ", or None" if optional else ""))
+
+
+def _state_ptr_np(who, state, optional=False):
+    """... and the numpy form, which gives the address (None for no state)."""
+    if state is None and optional:
+        return None
+    if (not isinstance(state, np.ndarray) or state.dtype != np.int64 or state.size != STATE_WORDS
+            or not state.flags.c_contiguous):
+        raise ValueError("%s: state must be int64 [%d]%s" % (who, STATE_WORDS, ", or None" if optional else ""))
+    return _np_ptr(state)
+
+
+def _on_gpu(who, dev, what="tables are"):
     if dev is None or dev.type != "cuda":
-        raise ValueError("%s: the tables are not on a GPU (%s_host is the CPU twin)" % (who, who))
-    if g.device != dev or g.dtype != torch.float32 or g.dim() != 1 or not g.is_contiguous() or g.numel() != tables.n:
-        raise ValueError("%s: g must be a contiguous float32 [%d] on %s" % (who, tables.n, dev))
-    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
-        raise ValueError("%s: state must be int64 [%d] on %s" % (who, STATE_WORDS, dev))
+        raise ValueError("%s: the %s not on a GPU (%s_host is the CPU twin)" % (who, what, who))
+    return dev
+
+
+def _check_device(who, g, tables, workspace, state, ring, R):
+    dev = _on_gpu(who, tables.device)
+    _need_flat(who, "g", g, tables.n, dev)
+    _need_state(who, state, dev)
     for name, t, need in (("workspace", workspace, tables.workspace_bytes), ("ring", ring, R * tables.record_bytes)):
         if t is None:
             continue
@@ -95,11 +130,8 @@ def _check_device(who, g, tables, workspace, state, ring, R):
 
 
 def _check_host(who, g, tables, workspace, state, ring, R, writeable=True):
-    if (g.dtype != np.float32 or g.ndim != 1 or g.size != tables.n or not g.flags.c_contiguous
-            or (writeable and not g.flags.writeable)):
-        raise ValueError("%s: g must be a %scontiguous float32 [%d]" % (who, "writeable " if writeable else "", tables.n))
-    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
-        raise ValueError("%s: state must be int64 [%d]" % (who, STATE_WORDS))
+    _need_flat_np(who, "g", g, tables.n, writeable)
+    _state_ptr_np(who, state)
     for name, a, need in (("workspace", workspace, tables.workspace_bytes), ("ring", ring, R * tables.record_bytes)):
         if a is None:
             continue
@@ -154,8 +186,7 @@ def apply(w, g, m, tables, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, 
     R = int(R)
     _check_device("apply", g, tables, None, state, ring, R)
     for name, t in (("w", w), ("m", m)):
-        if t.device != g.device or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != tables.n:
-            raise ValueError("apply: %s must be a contiguous float32 [%d] on %s" % (name, tables.n, g.device))
+        _need_flat("apply", name, t, tables.n, g.device)
     check(_steplib.lib().x3dstep_apply(ptr(w), ptr(g), ptr(m), tables.n, ptr(state), ptr(ring), R, tables.S, float(lr),
                                        float(momentum), float(weight_decay), float(grad_scale), 1 if first else 0, stream()))
 
@@ -165,8 +196,7 @@ def apply_host(w, g, m, tables, state, ring, R, lr, momentum=0.9, weight_decay=5
     R = int(R)
     _check_host("apply_host", g, tables, None, state, ring, R, writeable=False)
     for name, a in (("w", w), ("m", m)):
-        if a.dtype != np.float32 or a.ndim != 1 or a.size != tables.n or not a.flags.c_contiguous or not a.flags.writeable:
-            raise ValueError("apply_host: %s must be a writeable contiguous float32 [%d]" % (name, tables.n))
+        _need_flat_np("apply_host", name, a, tables.n, writeable=True)
     check(_steplib.lib().x3dstep_apply_host(_np_ptr(w), _np_ptr(g), _np_ptr(m), tables.n, _np_ptr(state), _np_ptr(ring), R,
                                             tables.S, float(lr), float(momentum), float(weight_decay), float(grad_scale),
                                             1 if first else 0))
@@ -188,13 +218,9 @@ def apply_groups(w, g, m, tables, hyper, state, ring, R, lr, momentum=0.9, weigh
     same state and ring, or None: the unguarded form, which reads no state (ring and R are then ignored), takes the
     coefficient 1 and always applies."""
     R = int(R)
-    dev = tables.device
-    if dev is None or dev.type != "cuda":
-        raise ValueError("apply_groups: the tables are not on a GPU (apply_groups_host is the CPU twin)")
+    dev = _on_gpu("apply_groups", tables.device)
     for name, t in (("w", w), ("g", g), ("m", m)):
-        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.dim() != 1
-                or not t.is_contiguous() or t.numel() != tables.n):
-            raise ValueError("apply_groups: %s must be a contiguous float32 [%d] on %s" % (name, tables.n, dev))
+        _need_flat("apply_groups", name, t, tables.n, dev)
     if (not isinstance(hyper, torch.Tensor) or hyper.device != dev or hyper.dtype != torch.float32
             or tuple(hyper.shape) != (tables.S, 2) or not hyper.is_contiguous()):
         raise ValueError("apply_groups: hyper must be a contiguous float32 [%d, 2] on %s" % (tables.S, dev))
@@ -214,10 +240,7 @@ def apply_groups_host(w, g, m, tables, hyper, state, ring, R, lr, momentum=0.9, 
     [S, 2]; state int64 [STATE_WORDS] or None)."""
     R = int(R)
     for name, a, wr in (("w", w, True), ("g", g, False), ("m", m, True)):
-        if (a.dtype != np.float32 or a.ndim != 1 or a.size != tables.n or not a.flags.c_contiguous
-                or (wr and not a.flags.writeable)):
-            raise ValueError("apply_groups_host: %s must be a %scontiguous float32 [%d]"
-                             % (name, "writeable " if wr else "", tables.n))
+        _need_flat_np("apply_groups_host", name, a, tables.n, wr)
     if hyper.dtype == _steplib.HYPER_DT:
         ok = hyper.ndim == 1 and hyper.size == tables.S
     else:
@@ -282,11 +305,7 @@ class KeepTable:
 def keep(kt, state, mode):
     """One launch on the current stream: mode KEEP_SAVE copies the table's buffers into its snapshot; KEEP_RESTORE copies
     them back when state[S_SKIP] == 1 (the latest `apply` skipped) and does nothing otherwise."""
-    dev = kt.device
-    if dev is None or dev.type != "cuda":
-        raise ValueError("keep: the table is not on a GPU (keep_host is the CPU twin)")
-    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
-        raise ValueError("keep: state must be int64 [%d] on %s" % (STATE_WORDS, dev))
+    _need_state("keep", state, _on_gpu("keep", kt.device, "table is"))
     if mode not in (_steplib.KEEP_SAVE, _steplib.KEEP_RESTORE):
         raise ValueError("keep: mode must be KEEP_SAVE or KEEP_RESTORE (got %r)" % (mode,))
     check(_steplib.lib().x3dstep_keep(ptr(kt.d_table), kt.nbuf, ptr(kt.d_items), kt.nitems, ptr(kt.snap), kt.snap_n,
@@ -297,10 +316,8 @@ def keep_host(kt, state, mode):
     """The CPU twin of `keep` (a KeepTable of numpy arrays; state int64 [STATE_WORDS])."""
     if kt.device is not None:
         raise ValueError("keep_host: the table is on a GPU")
-    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
-        raise ValueError("keep_host: state must be int64 [%d]" % STATE_WORDS)
     check(_steplib.lib().x3dstep_keep_host(_np_ptr(kt.table), kt.nbuf, _np_ptr(kt.items), kt.nitems, _np_ptr(kt.snap),
-                                           kt.snap_n, _np_ptr(state), int(mode)))
+                                           kt.snap_n, _state_ptr_np("keep_host", state), int(mode)))
 
 
 def _check_decay(who, decay):
@@ -312,41 +329,21 @@ def _check_decay(who, decay):
 
 def _check_flat_pair(who, a, b, dev):
     for t in (a, b):
-        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.dim() != 1
-                or not t.is_contiguous() or t.numel() != a.numel() or t.numel() < 1):
-            raise ValueError("%s: both buffers must be contiguous float32 [n] on %s" % (who, dev))
-
-
-def _check_state(who, state, dev):
-    if state is None:
-        return
-    if state.device != dev or state.dtype != torch.int64 or state.numel() != STATE_WORDS or not state.is_contiguous():
-        raise ValueError("%s: state must be int64 [%d] on %s, or None" % (who, STATE_WORDS, dev))
+        _need_flat(who, "each of the two buffers", t, a.numel(), dev)
+    if a.numel() < 1:
+        raise ValueError("%s: the buffers are empty" % who)
 
 
 def _check_keep_device(who, kt, snap):
-    dev = kt.device
-    if dev is None or dev.type != "cuda":
-        raise ValueError("%s: the table is not on a GPU (%s_host is the CPU twin)" % (who, who))
-    if (snap.device != dev or snap.dtype != torch.float32 or snap.dim() != 1 or not snap.is_contiguous()
-            or snap.numel() != kt.snap_n):
-        raise ValueError("%s: the snapshot must be a contiguous float32 [%d] on %s" % (who, kt.snap_n, dev))
+    dev = _on_gpu(who, kt.device, "table is")
+    _need_flat(who, "the snapshot", snap, kt.snap_n, dev)
     return dev
 
 
 def _check_keep_host(who, kt, snap):
     if kt.device is not None:
         raise ValueError("%s: the table is on a GPU" % who)
-    if snap.dtype != np.float32 or snap.ndim != 1 or snap.size != kt.snap_n or not snap.flags.c_contiguous:
-        raise ValueError("%s: the snapshot must be a contiguous float32 [%d]" % (who, kt.snap_n))
-
-
-def _host_state_ptr(who, state):
-    if state is None:
-        return None
-    if state.dtype != np.int64 or state.size != STATE_WORDS or not state.flags.c_contiguous:
-        raise ValueError("%s: state must be int64 [%d], or None" % (who, STATE_WORDS))
-    return _np_ptr(state)
+    _need_flat_np(who, "the snapshot", snap, kt.snap_n)
 
 
 def ema(e, w, state, count, decay, warmup=True):
@@ -357,25 +354,24 @@ def ema(e, w, state, count, decay, warmup=True):
     if dev.type != "cuda":
         raise ValueError("ema: e is not on a GPU (ema_host is the CPU twin)")
     _check_flat_pair("ema", e, w, dev)
-    _check_state("ema", state, dev)
+    _need_state("ema", state, dev, optional=True)
     check(_steplib.lib().x3dstep_ema(ptr(e), ptr(w), e.numel(), None if state is None else ptr(state), int(count),
                                      _check_decay("ema", decay), 1 if warmup else 0, stream()))
 
 
 def ema_host(e, w, state, count, decay, warmup=True):
     """The CPU twin of `ema` on numpy arrays (e is updated in place)."""
-    for a in (e, w):
-        if a.dtype != np.float32 or a.ndim != 1 or a.size != e.size or not a.flags.c_contiguous:
-            raise ValueError("ema_host: e and w must be contiguous float32 [n]")
-    check(_steplib.lib().x3dstep_ema_host(_np_ptr(e), _np_ptr(w), e.size, _host_state_ptr("ema_host", state), int(count),
-                                          float(decay), 1 if warmup else 0))
+    for name, a in (("e", e), ("w", w)):
+        _need_flat_np("ema_host", name, a, np.size(e))
+    check(_steplib.lib().x3dstep_ema_host(_np_ptr(e), _np_ptr(w), e.size, _state_ptr_np("ema_host", state, optional=True),
+                                          int(count), float(decay), 1 if warmup else 0))
 
 
 def ema_keep(kt, esnap, state, count, decay, warmup=True):
     """One launch: the rule of `ema` over the table's live buffers, into `esnap` (float32 [kt.snap_n], laid out as the
     table's own snapshot; the padding past a buffer's length is left alone)."""
     dev = _check_keep_device("ema_keep", kt, esnap)
-    _check_state("ema_keep", state, dev)
+    _need_state("ema_keep", state, dev, optional=True)
     check(_steplib.lib().x3dstep_ema_keep(ptr(kt.d_table), kt.nbuf, ptr(kt.d_items), kt.nitems, ptr(esnap), kt.snap_n,
                                           None if state is None else ptr(state), int(count),
                                           _check_decay("ema_keep", decay), 1 if warmup else 0, stream()))
@@ -385,7 +381,7 @@ def ema_keep_host(kt, esnap, state, count, decay, warmup=True):
     """The CPU twin of `ema_keep` (a KeepTable of numpy arrays)."""
     _check_keep_host("ema_keep_host", kt, esnap)
     check(_steplib.lib().x3dstep_ema_keep_host(_np_ptr(kt.table), kt.nbuf, _np_ptr(kt.items), kt.nitems, _np_ptr(esnap),
-                                               kt.snap_n, _host_state_ptr("ema_keep_host", state), int(count),
+                                               kt.snap_n, _state_ptr_np("ema_keep_host", state, optional=True), int(count),
                                                float(decay), 1 if warmup else 0))
 
 
@@ -400,9 +396,8 @@ def swap(a, b):
 
 def swap_host(a, b):
     """The CPU twin of `swap`."""
-    for x in (a, b):
-        if x.dtype != np.float32 or x.ndim != 1 or x.size != a.size or not x.flags.c_contiguous or not x.flags.writeable:
-            raise ValueError("swap_host: a and b must be writeable contiguous float32 [n]")
+    for name, x in (("a", a), ("b", b)):
+        _need_flat_np("swap_host", name, x, np.size(a), writeable=True)
     check(_steplib.lib().x3dstep_swap_host(_np_ptr(a), _np_ptr(b), a.size))
 
 
@@ -454,9 +449,7 @@ class PbnTable:
 
 
 def _check_pbn_device(who, pt, acc, W):
-    dev = pt.device
-    if dev is None or dev.type != "cuda":
-        raise ValueError("%s: the table is not on a GPU (%s_host is the CPU twin)" % (who, who))
+    dev = _on_gpu(who, pt.device, "table is")
     need = int(W) * _steplib.PBN_ACC_DOUBLES * pt.channels
     if (not isinstance(acc, torch.Tensor) or acc.device != dev or acc.dtype != torch.float64 or acc.dim() != 1
             or not acc.is_contiguous() or acc.numel() != need or W < 1):
@@ -490,9 +483,7 @@ def pbn_finish(pt, acc_all, W, expect_n, snap):
     order, the pooled mean and variance written into all S slots of the layer's buffers in `snap` (float32 [snap_n], laid
     out as the keep table's snapshot; the padding is left alone); NaN where the merged count is not expect_n."""
     dev = _check_pbn_device("pbn_finish", pt, acc_all, W)
-    if (snap.device != dev or snap.dtype != torch.float32 or snap.dim() != 1 or not snap.is_contiguous()
-            or snap.numel() != pt.snap_n):
-        raise ValueError("pbn_finish: the snapshot must be a contiguous float32 [%d] on %s" % (pt.snap_n, dev))
+    _need_flat("pbn_finish", "the snapshot", snap, pt.snap_n, dev)
     check(_steplib.lib().x3dstep_pbn_finish(ptr(pt.d_layers), pt.nlayers, ptr(pt.d_work), pt.nwork, ptr(acc_all), int(W),
                                             int(expect_n), ptr(snap), pt.snap_n, stream()))
 
@@ -500,8 +491,7 @@ def pbn_finish(pt, acc_all, W, expect_n, snap):
 def pbn_finish_host(pt, acc_all, W, expect_n, snap):
     """The CPU twin of `pbn_finish`."""
     _check_pbn_host("pbn_finish_host", pt, acc_all, W)
-    if snap.dtype != np.float32 or snap.ndim != 1 or snap.size != pt.snap_n or not snap.flags.c_contiguous:
-        raise ValueError("pbn_finish_host: the snapshot must be a contiguous float32 [%d]" % pt.snap_n)
+    _need_flat_np("pbn_finish_host", "the snapshot", snap, pt.snap_n)
     check(_steplib.lib().x3dstep_pbn_finish_host(_np_ptr(pt.layers), pt.nlayers, _np_ptr(pt.work), pt.nwork, _np_ptr(acc_all),
                                                  int(W), int(expect_n), _np_ptr(snap), pt.snap_n))
 

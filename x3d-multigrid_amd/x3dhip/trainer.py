@@ -369,36 +369,29 @@ class Trainer:
             ema.update()                     # two launches; a skipped update is left out on the device
 
     def _update(self, grad=None):
+        """One sequence whatever the configuration: measure or observe, the update, the restore."""
         mon = getattr(self, "monitor", None)
-        g = self.param_groups[0]
         hy = getattr(self, "hyper", None)
-        if hy is not None:                   # per-tensor scales and / or Nesterov: one launch that knows the tensors
+        g = self.param_groups[0]
+        guarded = self.skip_nonfinite
+        w, gr, m = self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom
+        arith = (g['lr'], g['momentum'], g['weight_decay'], 1.0 / self.world)
+        if guarded or hy is not None:
             from . import _steplib, stepops
-            guarded = self.skip_nonfinite
-            if guarded:
-                mon.measure(grad)
-            elif mon is not None:
-                mon.observe(grad)            # scales the gradient in place, as before ops.sgd_fused
-            stepops.apply_groups(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, hy.tables, hy.hyper,
-                                 mon.state if guarded else None, mon.ring if guarded else None, mon.R if guarded else 0,
-                                 g['lr'], g['momentum'], g['weight_decay'], 1.0 / self.world, first=self.first,
-                                 nesterov=bool(g['nesterov']))
-            if guarded:
-                stepops.keep(self._keep_table(), mon.state, _steplib.KEEP_RESTORE)
-            self.first = False
-            return
-        if self.skip_nonfinite:
-            from . import _steplib, stepops
+        if guarded:
             mon.measure(grad)                # the decision and the coefficient stay on the device
-            stepops.apply(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, mon.tables, mon.state,
-                          mon.ring, mon.R, g['lr'], g['momentum'], g['weight_decay'], 1.0 / self.world, first=self.first)
+        elif mon is not None:                # statistics (and clipping) of exactly what the update is about to apply
+            mon.observe(grad)                # scales the gradient in place
+        if hy is not None:                   # per-tensor scales and / or Nesterov: one launch that knows the tensors
+            stepops.apply_groups(w, gr, m, hy.tables, hy.hyper, mon.state if guarded else None,
+                                 mon.ring if guarded else None, mon.R if guarded else 0, *arith, first=self.first,
+                                 nesterov=bool(g['nesterov']))
+        elif guarded:
+            stepops.apply(w, gr, m, mon.tables, mon.state, mon.ring, mon.R, *arith, first=self.first)
+        else:
+            ops.sgd_fused(w, gr, m, *arith, first=self.first)
+        if guarded:
             stepops.keep(self._keep_table(), mon.state, _steplib.KEEP_RESTORE)
-            self.first = False
-            return
-        if mon is not None:                  # statistics (and clipping) of exactly what the SGD kernel is about to apply
-            mon.observe(grad)
-        ops.sgd_fused(self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom, g['lr'], g['momentum'],
-                      g['weight_decay'], 1.0 / self.world, first=self.first)
         self.first = False
 
     # -- public -----------------------------------------------------------------------------
