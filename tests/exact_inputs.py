@@ -948,6 +948,24 @@ PW_WAVES16 = [(2, 432, 192, 4, 5, 5, 1, 1), (2, 448, 256, 2, 4, 4, 1, 0), (2, 19
 DW_TSEG = [(8, 432, 16, 7, 7, 1), (1, 7, 9, 7, 7, 1), (2, 40, 11, 5, 5, 2), (1, 2, 8, 40, 56, 1), (2, 5, 18, 14, 14, 2), (1, 3, 17, 7, 7, 1)]
 
 
+# tests/test_dispatch_options_gpu.py: the kernels and plans behind the library's run-time options (x3d_set_option).
+# X3D-XL widths (630 channels: K beyond the whole-K kernels' LDS tile, 40 M tiles); the last two have P = 50, P % 4 != 0
+PW_XL = [(2, 280, 630, 4, 5, 5, 1, 0), (2, 630, 280, 4, 5, 5, 1, 2), (2, 630, 280, 2, 5, 5, 1, 1), (2, 280, 630, 2, 5, 5, 1, 1)]
+PW_OPT_DENSE = [(2, 96, 216, 4, 10, 10, 1, 0), (2, 432, 192, 4, 5, 5, 1, 2), (2, 216, 96, 4, 10, 10, 1, 2)]     # pw4 / pw2 forward
+PW_OPT_STREAM = [(2, 24, 54, 4, 8, 8, 1, 0), (2, 54, 24, 4, 14, 14, 1, 2), (3, 24, 54, 4, 20, 20, 1, 0)]        # pw3 for the stream kernel
+# (N, P) on both sides of the float4 / 16-voxel choice of pw_plan: 2, 196 and 294 workgroups of 256 voxels
+PW_OPT_NT4 = [(2, 24, 54, 4, 8, 8, 1, 0), (2, 24, 54, 4, 79, 79, 1, 1), (3, 24, 54, 4, 79, 79, 1, 1)]
+PW_OPT_WHOLE_K = [(2, 108, 48, 4, 4, 4, 1, 2)]                          # K = 108, M = 48: the whole-K kernels at three M tiles
+PW_OPT_DGRAD = [(2, 216, 96, 4, 10, 10, 1, 2), (2, 192, 432, 4, 5, 5, 1, 0), (2, 96, 216, 4, 12, 12, 1, 2)]    # pw4 / pw5 data gradient
+PW_OPT_WGRAD = [(20, 96, 112, 8, 14, 14, 1, 2), (2, 48, 96, 4, 16, 16, 2, 1)]      # 500 chunks; the gathered stride-2 kernel
+PW_OPT = (PW_XL + PW_OPT_DENSE + PW_OPT_STREAM + PW_OPT_NT4 + PW_OPT_WHOLE_K + PW_OPT_DGRAD + PW_OPT_WGRAD)
+DW_OPT = [(2, 9, 2, 24, 24, 2), (2, 20, 2, 6, 6, 2), (2, 3, 8, 28, 28, 2), (2, 216, 4, 10, 10, 1), (2, 216, 4, 20, 20, 2),
+          (4, 216, 2, 40, 40, 1), (1, 3, 3, 15, 11, 2), (2, 54, 4, 79, 79, 2)]
+# stem weight gradient: N T 8 = 576 groups > the cap of 512; Wo = 130: two runs per output row (the second holds 2 voxels),
+# 6 tiles on 8 groups -- float4 row loads (W % 4 == 0) and element loads
+STEM_OPT = [(9, 3, 8, 16, 16), (1, 3, 1, 6, 260), (1, 3, 2, 5, 259)]
+
+
 def _uniq(cases):
     return [c for i, c in enumerate(cases) if c not in cases[:i]]
 
@@ -956,6 +974,7 @@ PW_EXACT = PW_CASES + PW_LARGE_P
 FUSED_EXACT = FUSED_CASES + FUSED_LARGE_P
 DW_EXACT = DW_CASES + DW_LARGE_P
 # every case shape the GPU tests use (what tests/test_exact_inputs_host.py proves exact)
-PW_ALL, FUSED_ALL, DW_ALL = _uniq(PW_EXACT + PW_GRID + PW_WAVES16), _uniq(FUSED_EXACT + FUSED_GRID), _uniq(DW_EXACT + DW_TSEG)
-STEM_EXACT = list(STEM_SHAPES)
+PW_ALL, FUSED_ALL = _uniq(PW_EXACT + PW_GRID + PW_WAVES16 + PW_OPT), _uniq(FUSED_EXACT + FUSED_GRID)
+DW_ALL = _uniq(DW_EXACT + DW_TSEG + DW_OPT)
+STEM_EXACT = _uniq(list(STEM_SHAPES) + STEM_OPT)
 HEAD_EXACT = [(R, K, HEAD_J, C) for R in HEAD_R for K in HEAD_K for C in HEAD_C]

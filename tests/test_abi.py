@@ -66,6 +66,23 @@ def test_option_table_set_get_reset():
     assert h.x3d_reset_options() == 0 and _lib.get_option("dw_th") == 16
 
 
+def test_dw_stride2_backward_tiles_start_at_even_rows():
+    """Host: the stride-2 backward of the channelwise conv never gets an odd tile height once a plane has two row tiles
+    (an odd tile origin reads one output row past the staged window): dw_th = 1 gives tiles of 2 rows there, 1 row at
+    stride 1 and in the forward; odd heights above 1 lose a row as before."""
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as ge
+        ge.build()
+    h = _lib.lib()
+    assert h.x3d_dw_bwd_tiles(2, 9, 2, 24, 24, 2) == 2 and h.x3d_dw_bwd_tiles(1, 3, 3, 15, 11, 2) == 2
+    with _lib.options(dw_th=1):
+        assert h.x3d_dw_bwd_tiles(2, 9, 2, 24, 24, 2) == 12 and h.x3d_dw_bwd_tiles(1, 3, 3, 15, 11, 2) == 8
+        assert h.x3d_dw_bwd_tiles(2, 9, 2, 24, 24, 1) == 24 and h.x3d_dw_tiles(2, 9, 2, 12, 12) == 12
+        assert h.x3d_dw_bwd_tiles(2, 9, 2, 1, 24, 2) == 1
+    with _lib.options(dw_th=3):
+        assert h.x3d_dw_bwd_tiles(2, 9, 2, 24, 24, 2) == 12 and h.x3d_dw_bwd_tiles(2, 9, 2, 24, 24, 1) == 8
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))

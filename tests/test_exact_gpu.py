@@ -303,11 +303,14 @@ def test_dw333_exact_integers_t_segments(case):
 def test_stem_exact_integers(shape):
     """stem133_fwd, dw5t_fwd (+ statistics), dw5t_bwd (dx, dw), stem133_bwd_weight bitwise the fp64 reference."""
     from x3dhip import ops
-    dev = _dev()
+    _stem(ops, shape, _dev())
+
+
+def _stem(ops, shape, dev, what=""):
     c = ei.stem_case(shape)
     r = ei.stem_ref(c)
     x, ws, wt, g, a, cb = (_to(getattr(c, k), dev) for k in ("x", "ws", "wt", "g", "a", "cb"))
-    what = "%s" % (shape,)
+    what = "%s%s" % (shape, what)
     ys = ops.stem133_fwd(x, ws)
     _eq(ys, r["ys"], what + " stem133_fwd")
     yt, partial = ops.dw5t_fwd(_to(r["ys"], dev), wt)
@@ -874,7 +877,10 @@ def test_dw333_exact_bn_forms(case):
     storage: coef, save, the running statistics, dgamma and dbeta bitwise what the fp64 finalize gives on dyadic statistics
     (the same in both storage modes), y / dx and their statistics as in test_dw333_exact_mx."""
     from x3dhip import ops
-    dev = _dev()
+    _dw_bn_forms(ops, case, _dev())
+
+
+def _dw_bn_forms(ops, case, dev):
     N, C = case[:2]
     for S in ei.dw_bn_splits(case):
         c, b = ei.dw_mx_bn_fwd_case(case, S)

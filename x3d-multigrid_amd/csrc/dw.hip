@@ -52,7 +52,15 @@ static DwGeom make_geom(int N, int C, int T, int H, int W, int stride, bool back
     if (th > th_max) th = th_max;
     if (th > GH) th = GH;
     if (balance) th = cdiv(GH, cdiv(GH, th));          // equal tile heights (same tile count)
-    if (backward && stride == 2 && th > 1 && (th & 1)) th -= 1;   // even tile origin in backward stride 2
+    // backward stride 2: every tile must start at an EVEN input row.  dw_tile_row0 stages the output rows h0 / 2 - 1 ...
+    // h0 / 2 + TH / 2 of a tile starting at h0; an odd input row 2k + 1 reads the output rows k and k + 1, and from an odd
+    // h0 = 2k + 1 the row k + 1 lies one past that window.  An odd TH > 1 loses a row; TH = 1 (option dw_th = 1, or more
+    // than 128 float4 groups per row) becomes 2 where two rows fit the 256 threads -- where they do not, the backward
+    // entry points refuse the shape (dw_bwd_geom_ok)
+    if (backward && stride == 2 && (th & 1)) {
+        if (th > 1) th -= 1;
+        else if (GH > 1 && 2 * g.groups <= 256) th = 2;
+    }
     g.TH = th;
     g.ipc = th * g.groups;
     int cpb = 256 / g.ipc;
@@ -914,6 +922,10 @@ static int nch_for(const DwGeom& g, bool backward) {
     return cdiv(g.cpb * rows * (g.WP / 4 - 2), 256);
 }
 
+// backward stride 2 with more than one row tile needs an even tile height (make_geom): rows too wide for two of them per
+// workgroup (W > 512) have no kernel
+static bool dw_bwd_geom_ok(const DwGeom& g) { return !(g.stride == 2 && g.tiles > 1 && (g.TH & 1)); }
+
 }  // namespace
 
 // The tile height depends on N and C too (whole rounds of workgroups, make_geom): the queries take the same N, C as the
@@ -1046,6 +1058,7 @@ extern "C" int x3d_dw333_bwd(const void* g, const void* a, const float* cb, cons
     A.out = (float*)out; A.wpartial = wpartial; A.partial = partial;
     A.sp = nullptr; A.stiles = 0; A.count = 0; A.gamma = A.save = nullptr; A.dgamma = A.dbeta = nullptr;
     A.geo = make_geom(N, C, T, H, W, strideHW, true);
+    if (!dw_bwd_geom_ok(A.geo)) { x3d_set_error("dw333_bwd: row too wide for the stride-2 backward (W=%d)", W); return X3D_EINVAL; }
     const size_t ldsb = bwd_lds_bytes(A.geo);
     if (ldsb > 160 * 1024) { x3d_set_error("dw333_bwd: LDS tile too large (W=%d)", W); return X3D_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
@@ -1070,6 +1083,7 @@ extern "C" int x3d_dw333_bwd_stats(const void* g, const void* a, const float* sp
     A.out = (float*)out; A.wpartial = wpartial; A.partial = partial;
     A.sp = spartial; A.stiles = stiles; A.count = count; A.gamma = gamma; A.save = save; A.dgamma = dgamma; A.dbeta = dbeta;
     A.geo = make_geom(N, C, T, H, W, strideHW, true);
+    if (!dw_bwd_geom_ok(A.geo)) { x3d_set_error("dw333_bwd: row too wide for the stride-2 backward (W=%d)", W); return X3D_EINVAL; }
     X3D_CHECK_ARG(A.geo.cpb <= 16);
     const size_t ldsb = bwd_lds_bytes(A.geo);
     if (ldsb > 160 * 1024) { x3d_set_error("dw333_bwd: LDS tile too large (W=%d)", W); return X3D_EINVAL; }
