@@ -958,7 +958,12 @@ PW_OPT_NT4 = [(2, 24, 54, 4, 8, 8, 1, 0), (2, 24, 54, 4, 79, 79, 1, 1), (3, 24, 
 PW_OPT_WHOLE_K = [(2, 108, 48, 4, 4, 4, 1, 2)]                          # K = 108, M = 48: the whole-K kernels at three M tiles
 PW_OPT_DGRAD = [(2, 216, 96, 4, 10, 10, 1, 2), (2, 192, 432, 4, 5, 5, 1, 0), (2, 96, 216, 4, 12, 12, 1, 2)]    # pw4 / pw5 data gradient
 PW_OPT_WGRAD = [(20, 96, 112, 8, 14, 14, 1, 2), (2, 48, 96, 4, 16, 16, 2, 1)]      # 500 chunks; the gathered stride-2 kernel
-PW_OPT = (PW_XL + PW_OPT_DENSE + PW_OPT_STREAM + PW_OPT_NT4 + PW_OPT_WHOLE_K + PW_OPT_DGRAD + PW_OPT_WGRAD)
+# one full 256-voxel tile per sample: the float4 form of the streaming kernels under pw_nt4_min = 0; 24 <-> 54 channels give M
+# blocks of four and of two tiles in either direction, with raw and with activated input
+PW_OPT_FLOAT4 = [(2, 24, 54, 4, 8, 8, 1, 0), (2, 54, 24, 4, 8, 8, 1, 0), (2, 24, 54, 4, 8, 8, 1, 1), (2, 54, 24, 4, 8, 8, 1, 1)]
+PW_OPT_TILED = [(1, 96, 216, 2, 7, 7, 1, 0)]                            # P = 98, raw input, 14 M tiles: pw2's element loads, two tiles per wave
+PW_OPT = (PW_XL + PW_OPT_DENSE + PW_OPT_STREAM + PW_OPT_NT4 + PW_OPT_WHOLE_K + PW_OPT_DGRAD + PW_OPT_WGRAD + PW_OPT_FLOAT4 +
+          PW_OPT_TILED)
 DW_OPT = [(2, 9, 2, 24, 24, 2), (2, 20, 2, 6, 6, 2), (2, 3, 8, 28, 28, 2), (2, 216, 4, 10, 10, 1), (2, 216, 4, 20, 20, 2),
           (4, 216, 2, 40, 40, 1), (1, 3, 3, 15, 11, 2), (2, 54, 4, 79, 79, 2)]
 # stem weight gradient: N T 8 = 576 groups > the cap of 512; Wo = 130: two runs per output row (the second holds 2 voxels),

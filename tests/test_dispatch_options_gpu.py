@@ -203,6 +203,63 @@ def test_pw_fwd_streaming_voxel_forms(case, nt4_min, tiles, default_tiles):
 
 
 @gpu
+@pytest.mark.parametrize("case", ei.PW_OPT_FLOAT4)
+def test_pw_streaming_float4_form_both_directions(case):
+    """pw_nt4_min = 0 (+ no_pwfs): the float4 form of pw_kernel and pw3_kernel, forward and every data-gradient epilogue
+    (plain / ReLU backward / residual-mask backward; no, dense and stride-2 addend).  By default the form needs 256 workgroups
+    of 256 voxels, and the exact cases that large have 54 output rows forward only.  Here: one 256-voxel tile per sample, M
+    blocks of four tiles (-> 54 rows) and of two (-> 24), raw and activated input."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    N, Ci, Co = case[:3]
+    c, r = _pw(case)
+    d = _pw_device(c, dev)
+    L = _lib.lib()
+    assert L.x3d_pw_tiles(N, Ci, Co, _P(case), 1) == 4                      # 16-voxel waves: cdiv(256, 64)
+    with _lib.options(pw_nt4_min=0, no_pwfs=1):
+        assert L.x3d_pw_tiles(N, Ci, Co, _P(case), 1) == L.x3d_pw_tiles(N, Co, Ci, _P(case), 1) == 1
+        ops.pw_fwd(d["x"], d["w"], pre=d["pre"], pre_act=c.act)
+        assert _lib.last_kernel() == "pw_kernel", _lib.last_kernel()
+        _pw_forward(ops, c, r, d, "%s pw_nt4_min 0" % (case,))
+        assert _lib.last_kernel() == "pw3_kernel", _lib.last_kernel()
+        assert _dgrad_kernel(ops, _lib, d) == "pw3_kernel"
+        _pw_backward(ops, c, r, d, "%s pw_nt4_min 0" % (case,))
+
+
+@gpu
+@pytest.mark.parametrize("case", ei.PW_OPT_DGRAD + ei.PW_OPT_DENSE[1:2])
+def test_pw_tiled_kernel_without_persistence_both_directions(case):
+    """pw_no_persist + no_pw6 / no_pw7 / no_pw8: pw2_kernel's float4 form forward and on every data-gradient epilogue -- M
+    blocks of 7, 4 and 6 tiles for the first three data gradients and 4 behind the activated 432 -> 192 (both `mt_run > 4`
+    builds with and without the ReLU backward); forward 192 -> 432 is the raw input on blocks of 4."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    c, r = _pw(case)
+    d = _pw_device(c, dev)
+    opts = dict(pw_no_persist=1, no_pw7=1, **_PW4)
+    with _lib.options(**opts):
+        _pw_forward(ops, c, r, d, "%s %s" % (case, opts))
+        assert _lib.last_kernel() == "pw2_kernel", _lib.last_kernel()
+        assert _dgrad_kernel(ops, _lib, d) == "pw2_kernel"
+        _pw_backward(ops, c, r, d, "%s %s" % (case, opts))
+
+
+@gpu
+def test_pw_tiled_kernel_element_loads_raw_input():
+    """Defaults: 96 -> 216 at P = 98 (P % 4 != 0) is outside the whole-K and the chunked kernels: pw2_kernel's element-load form
+    with a raw input and two M tiles per wave forward, its three data-gradient epilogues backward."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    case = ei.PW_OPT_TILED[0]
+    c, r = _pw(case)
+    d = _pw_device(c, dev)
+    _pw_forward(ops, c, r, d, "%s" % (case,))
+    assert _lib.last_kernel() == "pw2_kernel", _lib.last_kernel()
+    assert _dgrad_kernel(ops, _lib, d) == "pw2_kernel"
+    _pw_backward(ops, c, r, d, "%s" % (case,))
+
+
+@gpu
 @pytest.mark.parametrize("no_pw8,kernel", [(1, "pw6_kernel"), (0, "pw8_kernel")])
 def test_pw_fwd_whole_k_kernels_at_three_m_tiles(no_pw8, kernel):
     """pw6_min_m = 16: K = 108 -> M = 48 on the whole-K kernels (five of the eight waves own no M tile); default: pw3."""

@@ -803,6 +803,25 @@ def test_pw_exact_mx(case):
     assert tuple(kernels) == MX_KERNELS[case] + MX_KERNELS[case][1:], (case, kernels)
 
 
+@pytest.mark.parametrize("case", ei.PW_MX[:2])
+def test_pw_exact_mx_float4_form(case):
+    """pw_nt4_min = 0 + no_pwfs: the float4 form of the mixed-storage pw3_kernel (four bf16 values per load / store), which
+    under defaults needs 256 workgroups of 256 voxels.  P = 1024 is four full tiles per sample; 24 -> 54 has M blocks of four
+    tiles forward and two backward, 54 -> 24 the other way round.  Same inputs and references as test_pw_exact_mx."""
+    from x3dhip import _lib, ops
+    dev = _dev()
+    c = ei.pw_mx_case(case)
+    r = ei.pw_mx_ref(c)
+    d = _pw_device_mx(c, dev)
+    N, Ci, Co = c.shape[:3]
+    L = _lib.lib()
+    with _lib.options(pw_nt4_min=0, no_pwfs=1):
+        assert L.x3d_pw_tiles(N, Ci, Co, 1024, 1) == L.x3d_pw_tiles(N, Co, Ci, 1024, 1) == 4
+        _pw_forward_mx(ops, c, r, d, "%s pw_nt4_min 0" % (case,))
+        assert _lib.last_kernel() == "pw3_kernel", _lib.last_kernel()
+        assert _pw_backward_mx(ops, c, r, d, "%s pw_nt4_min 0" % (case,)) == "pw3_kernel"
+
+
 def _fused_xy(ops, case, dev, what=""):
     """X3D_MX_X | X3D_MX_Y: x and dx bf16, activation-backward mode without addend."""
     N, Ci, Co, T, H, W, act = case

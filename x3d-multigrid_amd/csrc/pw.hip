@@ -9,6 +9,11 @@
 //   pw4_kernel        forward, stages 3-4: persistent software-pipelined LDS-tiled GEMM, fp32 MFMA
 //   pw5_kernel        data-gradient, stages 3-4: pw4's pipeline on split-bf16 MFMA (hi+lo, 3 products)
 //   pw2_kernel, pw_kernel   fallbacks (P % 4 != 0, strided gather, no packed weights)
+// These five differ in their K loops only.  Their epilogue (addend, activation / residual-mask backward, bf16 store
+// rounding, row statistics) is written once: pw_epi_row is the rule for the values of one output row and pw_addend_site the addend's
+// address, used by all five; pw_stream_epilogue is the whole epilogue of pw_kernel and pw3_kernel, pw_item_epilogue
+// that of pw4_kernel and pw5_kernel, whose walk over work items is PwItemWalk.  pw2_kernel keeps its own load and
+// store phases (per-voxel predicates, partials straight to HBM) around the same row rule.
 //   pw_wgrad3_kernel  weight gradient, every dense shape: split-bf16 MFMA, LDS-tiled, XCD-aware groups
 //   pw_wgrad2_kernel, pw_wgrad_kernel   exact-fp32 / strided weight gradient
 //   pw_pack*_kernel   weights -> MFMA fragment order (fp32 image; transposed image also as bf16 hi/lo planes)
@@ -128,6 +133,138 @@ template <int NT>
 __device__ __forceinline__ void vstorex(void* p, size_t i, int bf, const float (&v)[NT]) {
     if (NT == 4) stx4(p, i, bf, v[0], v[1 % NT], v[2 % NT], v[3 % NT]);
     else stx1(p, i, bf, v[0]);
+}
+
+// ---------------------------------------------------------------------------------------
+// The epilogue of the five forward / data-gradient kernels, stated once.
+// ---------------------------------------------------------------------------------------
+// Addend site of output voxel p.  A dense addend sits at the same offset; a half-resolution one (addend_stride 2)
+// feeds only the voxels at even (h, w), from its voxel (t, h / 2, w / 2) -- the others keep `ok` false and read
+// offset 0, a valid address.  `ok` comes in as "this lane's voxel exists and there is an addend".
+__device__ __forceinline__ void pw_addend_site(const PwArgs& A, bool add_s2, int p, bool& ok, int& off) {
+    off = p;
+    if (add_s2) {
+        const int hw = A.H * A.W;
+        const int t = p / hw, rem = p - t * hw;
+        const int h = rem / A.W, w = rem - h * A.W;
+        const bool even = !(h & 1) && !(w & 1);
+        ok = ok && even;
+        off = even ? (t * A.Ho + (h >> 1)) * A.Wo + (w >> 1) : 0;
+    }
+}
+
+// What the epilogue does to the accumulator values v[] a lane holds of one output row (voxel j exists: pv[j]), per
+// value in this order: add the addend where it is valid; gate (EPI_RESBWD: pass where mask > 0; EPI_ACTBWD: times the
+// activation derivative at esc * x + esh; EPI_STATS: zero outside the tensor); round to what a bf16 output stores (MX
+// builds); accumulate the row statistics s1 += v, s2 += v * (x or v), voxels in ascending order.  Operands an EPI does
+// not use are never read (they may be unset).
+template <int EPI, bool MX, int NV>
+__device__ __forceinline__ void pw_epi_row(const PwArgs& A, float (&v)[NV], const bool (&pv)[NV], bool has_add, const bool (&av)[NV],
+                                           const float (&add)[NV], const float (&x)[NV], const float (&mask)[NV], const float& esc,
+                                           const float& esh, float& s1, float& s2) {
+    const int y_bf = MX ? A.y_bf : 0;
+    if (has_add) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] += av[j] ? add[j] : 0.f;
+    }
+    if (EPI_HAS_X(EPI)) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const float xj = pv[j] ? x[j] : 0.f;
+            if (EPI == EPI_RESBWD) v[j] = (pv[j] && mask[j] > 0.f) ? v[j] : 0.f;
+            else v[j] = pv[j] ? v[j] * act_bwd(fmaf(esc, xj, esh), A.e_act) : 0.f;
+            v[j] = stored(v[j], y_bf);
+            s1 += v[j];
+            s2 = fmaf(v[j], xj, s2);
+        }
+    } else if (EPI == EPI_STATS) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) { v[j] = stored(pv[j] ? v[j] : 0.f, y_bf); s1 += v[j]; s2 = fmaf(v[j], v[j], s2); }
+    }
+}
+
+// Epilogue of the streaming kernels (pw_kernel, pw3_kernel): lane (q, r) of wave `wave` holds rows 16 mt + 4 q + e of
+// the M block at m0 (bm rows exist) for the NT voxels from p0.
+// Per 16-row tile: phase 1 issues the four rows' global reads (activation-derivative input,
+// its coefficients, the residual addend) from clamped addresses, phase 2 combines and stores
+// -- no load sits under a per-lane branch (see pw2_kernel).
+template <int MT, int NT, int EPI, bool MX>
+__device__ __forceinline__ void pw_stream_epilogue(const PwArgs& A, const f32x4 (&acc)[MT][NT], float* red, int n, int tile,
+                                                   int m0, int bm, int mt_run, int p0, bool pv) {
+    const int y_bf = MX ? A.y_bf : 0, ex_bf = MX ? A.ex_bf : 0;                              // fp32 build: folded away
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = lane >> 4, r = lane & 15;
+    const int P = A.P;
+    const bool has_add = EPI != EPI_STATS && A.addend != nullptr;
+    const bool add_s2 = has_add && A.addend_stride == 2;
+    int aoff[NT];
+    bool av[NT], pvs[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        pvs[j] = pv;
+        av[j] = has_add && pv;
+        pw_addend_site(A, add_s2, min(p0 + j, P - 1), av[j], aoff[j]);
+    }
+    const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
+    const int pc = pv ? p0 : 0;                   // clamped voxel (NT-aligned)
+
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        if (mt < mt_run) {
+            float xv[4][NT], mk[4][NT], adv[4][NT], esc[4], esh[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int ml = mt * 16 + 4 * q + e;
+                const size_t mrow = (size_t)n * A.M + m0 + (ml < bm ? ml : 0);
+                if (EPI == EPI_ACTBWD) {
+                    const float2 c2 = *reinterpret_cast<const float2*>(A.ecoef + mrow * 2);
+                    esc[e] = c2.x; esh[e] = c2.y;
+                }
+                if (EPI_HAS_X(EPI)) vloadx<NT>(A.ex, mrow * (size_t)P + pc, EPI == EPI_ACTBWD ? ex_bf : 0, xv[e]);
+                if (EPI == EPI_RESBWD) vload<NT>(A.emask + mrow * (size_t)P + pc, mk[e]);
+                if (has_add) {
+                    const float* pa = A.addend + mrow * (size_t)addP;
+                    if (NT == 4 && !add_s2) {
+                        vload<NT>(pa + pc, adv[e]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) adv[e][j] = pa[aoff[j]];
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int ml = mt * 16 + 4 * q + e;
+                const int m = m0 + ml;
+                const bool mv = ml < bm;
+                if (EPI == EPI_ACTBWD) vwiden<NT>(xv[e], ex_bf, xv[e]);
+                float v[NT];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) v[j] = acc[mt][j][e];
+                float s1 = 0.f, s2 = 0.f;
+                pw_epi_row<EPI, MX, NT>(A, v, pvs, has_add, av, adv[e], xv[e], mk[e], esc[e], esh[e], s1, s2);
+                if (mv && pv) vstorex<NT>(A.y, ((size_t)n * A.M + m) * (size_t)P + p0, y_bf, v);
+                if (EPI != EPI_PLAIN) {
+                    s1 = row16_sum(s1);
+                    s2 = row16_sum(s2);
+                    if (r == 0) {
+                        red[(wave * MT * 16 + ml) * 2] = mv ? s1 : 0.f;
+                        red[(wave * MT * 16 + ml) * 2 + 1] = mv ? s2 : 0.f;
+                    }
+                }
+            }
+        }
+    }
+    if (EPI != EPI_PLAIN && A.partial != nullptr) {
+        __syncthreads();
+        for (int idx = tid; idx < bm * 2; idx += 256) {
+            const int ml = idx >> 1, which = idx & 1;
+            float s = 0.f;
+#pragma unroll
+            for (int wv = 0; wv < 4; ++wv) s += red[(wv * MT * 16 + ml) * 2 + which];
+            A.partial[(((size_t)n * A.M + (m0 + ml)) * A.tiles + tile) * 2 + which] = s;
+        }
+    }
 }
 
 template <int MT, int NT, int IN, int EPI>
@@ -267,104 +404,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const PwArgs A) {
             compute_half(1);
         }
     }
-
-    // ------------------------------ epilogue ------------------------------
-    // Per 16-row tile: phase 1 issues the four rows' global reads (activation-derivative input,
-    // its coefficients, the residual addend) from clamped addresses, phase 2 combines and stores
-    // -- no load sits under a per-lane branch (see pw2_kernel).
-    const bool has_add = EPI != EPI_STATS && A.addend != nullptr;
-    const bool add_s2 = has_add && A.addend_stride == 2;
-    int aoff[NT];
-    bool av[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int p = min(p0 + j, P - 1);
-        av[j] = has_add && pv;
-        aoff[j] = p;
-        if (add_s2) {
-            const int hw = A.H * A.W;
-            const int t = p / hw, rem = p - t * hw;
-            const int h = rem / A.W, w = rem - h * A.W;
-            const bool even = !(h & 1) && !(w & 1);
-            av[j] = av[j] && even;
-            aoff[j] = even ? (t * A.Ho + (h >> 1)) * A.Wo + (w >> 1) : 0;
-        }
-    }
-    const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
-    const int pc = pv ? p0 : 0;                   // clamped voxel (NT-aligned)
-
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        if (mt < mt_run) {
-            float xv[4][NT], mk[4][NT], adv[4][NT], esc[4], esh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = mt * 16 + 4 * q + e;
-                const size_t mrow = (size_t)n * A.M + m0 + (ml < bm ? ml : 0);
-                if (EPI == EPI_ACTBWD) {
-                    const float2 c2 = *reinterpret_cast<const float2*>(A.ecoef + mrow * 2);
-                    esc[e] = c2.x; esh[e] = c2.y;
-                }
-                if (EPI_HAS_X(EPI)) vload<NT>(A.ex + mrow * (size_t)P + pc, xv[e]);
-                if (EPI == EPI_RESBWD) vload<NT>(A.emask + mrow * (size_t)P + pc, mk[e]);
-                if (has_add) {
-                    const float* pa = A.addend + mrow * (size_t)addP;
-                    if (NT == 4 && !add_s2) {
-                        vload<NT>(pa + pc, adv[e]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) adv[e][j] = pa[aoff[j]];
-                    }
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = mt * 16 + 4 * q + e;
-                const int m = m0 + ml;
-                const bool mv = ml < bm;
-                float v[NT];
-#pragma unroll
-                for (int j = 0; j < NT; ++j) v[j] = acc[mt][j][e];
-                float s1 = 0.f, s2 = 0.f;
-                if (has_add) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) v[j] += av[j] ? adv[e][j] : 0.f;
-                }
-                if (EPI_HAS_X(EPI)) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        const float xj = pv ? xv[e][j] : 0.f;
-                        if (EPI == EPI_RESBWD) v[j] = (pv && mk[e][j] > 0.f) ? v[j] : 0.f;
-                        else v[j] = pv ? v[j] * act_bwd(fmaf(esc[e], xj, esh[e]), A.e_act) : 0.f;
-                        s1 += v[j];
-                        s2 = fmaf(v[j], xj, s2);
-                    }
-                } else if (EPI == EPI_STATS) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) { v[j] = pv ? v[j] : 0.f; s1 += v[j]; s2 = fmaf(v[j], v[j], s2); }
-                }
-                if (mv && pv) vstore<NT>(A.y + ((size_t)n * A.M + m) * (size_t)P + p0, v);
-                if (EPI != EPI_PLAIN) {
-                    s1 = row16_sum(s1);
-                    s2 = row16_sum(s2);
-                    if (r == 0) {
-                        red[(wave * MT * 16 + ml) * 2] = mv ? s1 : 0.f;
-                        red[(wave * MT * 16 + ml) * 2 + 1] = mv ? s2 : 0.f;
-                    }
-                }
-            }
-        }
-    }
-    if (EPI != EPI_PLAIN && A.partial != nullptr) {
-        __syncthreads();
-        for (int idx = tid; idx < bm * 2; idx += 256) {
-            const int ml = idx >> 1, which = idx & 1;
-            float s = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv) s += red[(wv * MT * 16 + ml) * 2 + which];
-            A.partial[(((size_t)n * A.M + (m0 + ml)) * A.tiles + tile) * 2 + which] = s;
-        }
-    }
+    pw_stream_epilogue<MT, NT, EPI, false>(A, acc, red, n, tile, m0, bm, mt_run, p0, pv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -377,7 +417,7 @@ __global__ __launch_bounds__(256, 2) void pw_kernel(const PwArgs A) {
 // ---------------------------------------------------------------------------------------
 template <int MT, int NT, int IN, int EPI, bool MX>
 __global__ __launch_bounds__(256, 2) void pw3_kernel(const PwArgs A) {
-    const int x_bf = MX ? A.x_bf : 0, y_bf = MX ? A.y_bf : 0, ex_bf = MX ? A.ex_bf : 0;      // fp32 build: folded away
+    const int x_bf = MX ? A.x_bf : 0;                                                         // fp32 build: folded away
     __shared__ float red[4 * MT * 16 * 2];
     __shared__ float Cl[(IN == IN_RAW) ? 4 : 3 * PW_MAXK];
     constexpr int NC = (IN == IN_BNBWD) ? 3 : 2;
@@ -475,106 +515,7 @@ __global__ __launch_bounds__(256, 2) void pw3_kernel(const PwArgs A) {
             compute(s + 1, wn, xn, an_);
         }
     }
-
-    // ------------------------------ epilogue ------------------------------
-    // Per 16-row tile: phase 1 issues the four rows' global reads (activation-derivative input,
-    // its coefficients, the residual addend) from clamped addresses, phase 2 combines and stores
-    // -- no load sits under a per-lane branch (see pw2_kernel).
-    const bool has_add = EPI != EPI_STATS && A.addend != nullptr;
-    const bool add_s2 = has_add && A.addend_stride == 2;
-    int aoff[NT];
-    bool av[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int p = min(p0 + j, P - 1);
-        av[j] = has_add && pv;
-        aoff[j] = p;
-        if (add_s2) {
-            const int hw = A.H * A.W;
-            const int t = p / hw, rem = p - t * hw;
-            const int h = rem / A.W, w = rem - h * A.W;
-            const bool even = !(h & 1) && !(w & 1);
-            av[j] = av[j] && even;
-            aoff[j] = even ? (t * A.Ho + (h >> 1)) * A.Wo + (w >> 1) : 0;
-        }
-    }
-    const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
-    const int pc = pv ? p0 : 0;                   // clamped voxel (NT-aligned)
-
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        if (mt < mt_run) {
-            float xv[4][NT], mk[4][NT], adv[4][NT], esc[4], esh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = mt * 16 + 4 * q + e;
-                const size_t mrow = (size_t)n * A.M + m0 + (ml < bm ? ml : 0);
-                if (EPI == EPI_ACTBWD) {
-                    const float2 c2 = *reinterpret_cast<const float2*>(A.ecoef + mrow * 2);
-                    esc[e] = c2.x; esh[e] = c2.y;
-                }
-                if (EPI_HAS_X(EPI)) vloadx<NT>(A.ex, mrow * (size_t)P + pc, EPI == EPI_ACTBWD ? ex_bf : 0, xv[e]);
-                if (EPI == EPI_RESBWD) vload<NT>(A.emask + mrow * (size_t)P + pc, mk[e]);
-                if (has_add) {
-                    const float* pa = A.addend + mrow * (size_t)addP;
-                    if (NT == 4 && !add_s2) {
-                        vload<NT>(pa + pc, adv[e]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) adv[e][j] = pa[aoff[j]];
-                    }
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = mt * 16 + 4 * q + e;
-                const int m = m0 + ml;
-                const bool mv = ml < bm;
-                if (EPI == EPI_ACTBWD) vwiden<NT>(xv[e], ex_bf, xv[e]);
-                float v[NT];
-#pragma unroll
-                for (int j = 0; j < NT; ++j) v[j] = acc[mt][j][e];
-                float s1 = 0.f, s2 = 0.f;
-                if (has_add) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) v[j] += av[j] ? adv[e][j] : 0.f;
-                }
-                if (EPI_HAS_X(EPI)) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        const float xj = pv ? xv[e][j] : 0.f;
-                        if (EPI == EPI_RESBWD) v[j] = (pv && mk[e][j] > 0.f) ? v[j] : 0.f;
-                        else v[j] = pv ? v[j] * act_bwd(fmaf(esc[e], xj, esh[e]), A.e_act) : 0.f;
-                        v[j] = stored(v[j], y_bf);
-                        s1 += v[j];
-                        s2 = fmaf(v[j], xj, s2);
-                    }
-                } else if (EPI == EPI_STATS) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) { v[j] = stored(pv ? v[j] : 0.f, y_bf); s1 += v[j]; s2 = fmaf(v[j], v[j], s2); }
-                }
-                if (mv && pv) vstorex<NT>(A.y, ((size_t)n * A.M + m) * (size_t)P + p0, y_bf, v);
-                if (EPI != EPI_PLAIN) {
-                    s1 = row16_sum(s1);
-                    s2 = row16_sum(s2);
-                    if (r == 0) {
-                        red[(wave * MT * 16 + ml) * 2] = mv ? s1 : 0.f;
-                        red[(wave * MT * 16 + ml) * 2 + 1] = mv ? s2 : 0.f;
-                    }
-                }
-            }
-        }
-    }
-    if (EPI != EPI_PLAIN && A.partial != nullptr) {
-        __syncthreads();
-        for (int idx = tid; idx < bm * 2; idx += 256) {
-            const int ml = idx >> 1, which = idx & 1;
-            float s = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv) s += red[(wv * MT * 16 + ml) * 2 + which];
-            A.partial[(((size_t)n * A.M + (m0 + ml)) * A.tiles + tile) * 2 + which] = s;
-        }
-    }
+    pw_stream_epilogue<MT, NT, EPI, MX>(A, acc, red, n, tile, m0, bm, mt_run, p0, pv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -867,17 +808,8 @@ __global__ __launch_bounds__(256, 2) void pw2_kernel(const PwArgs A) {
     bool av[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const int p = min(pl + j, P - 1);
         av[j] = has_add && pv[j];
-        aoff[j] = p;
-        if (add_s2) {
-            const int hw = A.H * A.W;
-            const int t = p / hw, rem = p - t * hw;
-            const int h = rem / A.W, w = rem - h * A.W;
-            const bool even = !(h & 1) && !(w & 1);
-            av[j] = av[j] && even;
-            aoff[j] = even ? (t * A.Ho + (h >> 1)) * A.Wo + (w >> 1) : 0;
-        }
+        pw_addend_site(A, add_s2, min(pl + j, P - 1), av[j], aoff[j]);
     }
     const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
     constexpr int NI = TWO ? 2 : 1;
@@ -938,23 +870,7 @@ __global__ __launch_bounds__(256, 2) void pw2_kernel(const PwArgs A) {
             const bool mv = mvv[i][e];
             float v[4] = {acc[i][0][e], acc[i][1][e], acc[i][2][e], acc[i][3][e]};
             float s1 = 0.f, s2 = 0.f;
-            if (has_add) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] += av[j] ? adv[i][e][j] : 0.f;
-            }
-            if (EPI_HAS_X(EPI)) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float xj = pv[j] ? xv[i][e][j] : 0.f;
-                    if (EPI == EPI_RESBWD) v[j] = (pv[j] && mk[i][e][j] > 0.f) ? v[j] : 0.f;
-                    else v[j] = pv[j] ? v[j] * act_bwd(fmaf(esc[i][e], xj, esh[i][e]), A.e_act) : 0.f;
-                    s1 += v[j];
-                    s2 = fmaf(v[j], xj, s2);
-                }
-            } else if (EPI == EPI_STATS) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] = pv[j] ? v[j] : 0.f; s1 += v[j]; s2 = fmaf(v[j], v[j], s2); }
-            }
+            pw_epi_row<EPI, false, 4>(A, v, pv, has_add, av, adv[i][e], xv[i][e], mk[i][e], esc[i][e], esh[i][e], s1, s2);
             if (mv && pv[0]) {
                 float* py = A.y + ((size_t)n * A.M + m) * (size_t)P + pl;
                 if (VEC) {
@@ -1007,6 +923,133 @@ __global__ __launch_bounds__(256, 2) void pw2_kernel(const PwArgs A) {
 // ---------------------------------------------------------------------------------------
 constexpr int P4_BN = 64, P4_KC = 32, P4_PITCH = 72;     // pitch 72: the four k rows of a b64 fragment read hit disjoint banks
 
+// Item walk of the persistent kernels (pw4_kernel, pw5_kernel): workgroup g takes items g, g + G, ... of
+//   item = ((voxel-tile group of 8) * mblocks + mb) * 8 + (voxel tile & 7), voxel tiles numbered over ALL samples
+// (n * tiles + tile): item % 8 -- hence the XCD of the workgroup that owns it -- is the low tile bits, so the M
+// blocks of one voxel tile share an XCD, and every workgroup has work even when a sample has < 8 tiles.
+// A walk is a position in that list, in chunks: chunk c of item `it`, decoded into (n, tile, mb).  A kernel keeps two,
+// the one its MFMAs are at and the one its prefetch is at.
+struct PwItemWalk {
+    int VT, items, tiles, mblocks, G;
+    int it, n, tile, mb, c;
+
+    __device__ __forceinline__ PwItemWalk(const PwArgs& A)
+        : VT(A.N * A.tiles), items(((A.N * A.tiles + 7) / 8) * 8 * A.mblocks), tiles(A.tiles), mblocks(A.mblocks),
+          G(gridDim.x), n(0), tile(0), mb(0), c(0) {
+        seek(blockIdx.x);
+    }
+    // the first item at or after `from` (in steps of G) whose voxel tile exists; none left: it >= items
+    __device__ __forceinline__ void seek(int from) {
+        it = from;
+        while (it < items) {
+            const int tlo = it & 7, rest = it >> 3;
+            mb = rest % mblocks;
+            const int vt = (rest / mblocks) * 8 + tlo;
+            if (vt < VT) {
+                n = vt / tiles;
+                tile = vt - n * tiles;
+                break;
+            }
+            it += G;
+        }
+    }
+    __device__ __forceinline__ bool more() const { return it < items; }
+    __device__ __forceinline__ void next_item() { c = 0; seek(it + G); }
+    // one chunk on: true when that was the item's last one and the walk is still AT the item (next_item() leaves it)
+    __device__ __forceinline__ bool item_done(int nchunks) { return ++c == nchunks; }
+    __device__ __forceinline__ void advance(int nchunks) {
+        if (item_done(nchunks)) next_item();
+    }
+};
+
+// Epilogue of the persistent kernels, once per item: wave (half = wave & 1, mpar = wave >> 1) holds unit j = rows
+// 16 (mpar + 2 j) + 4 q + e of the M block, lane r the two voxels 32 half + 2 r, + 1 of the BN-voxel tile (P even: both
+// or none valid).  Phase 1 issues the four rows' reads branch-free from clamped addresses, phase 2 combines and stores.
+template <int EPI, int U, int BN>
+__device__ __forceinline__ void pw_item_epilogue(const PwArgs& A, const f32x4 (&acc)[U][2], float* red, int wave, int n, int tile,
+                                                 int mb) {
+    const int tid = threadIdx.x, lane = tid & 63;     // wave: the kernel's wave-uniform copy (its lane roles are loop invariants)
+    const int q = lane >> 4, r = lane & 15;
+    const int half = wave & 1, mpar = wave >> 1;
+    const int P = A.P, M = A.M, mt_run = A.mt_run;
+    const bool has_add = EPI != EPI_STATS && A.addend != nullptr;
+    const bool add_s2 = has_add && A.addend_stride == 2;
+    const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
+    const int m0 = mb * mt_run * 16;
+    const int bm = min(mt_run * 16, M - m0);
+    const int pl = tile * BN + 32 * half + 2 * r;
+    const bool pv = pl < P;
+    const int pc = pv ? pl : 0;
+    int aoff[2];
+    bool av[2];
+    const bool pvs[2] = {pv, pv};
+#pragma unroll
+    for (int j2 = 0; j2 < 2; ++j2) {
+        av[j2] = has_add && pv;
+        pw_addend_site(A, add_s2, pc + j2, av[j2], aoff[j2]);
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        const int lt = mpar + 2 * j;
+        float xv[4][2], mk[4][2], adv[4][2], esc[4], esh[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int ml = lt * 16 + 4 * q + e;
+            const size_t mrow = (size_t)n * M + m0 + ((lt < mt_run && ml < bm) ? ml : 0);
+            if (EPI == EPI_ACTBWD) {
+                const float2 c2 = *reinterpret_cast<const float2*>(A.ecoef + mrow * 2);
+                esc[e] = c2.x; esh[e] = c2.y;
+            }
+            if (EPI_HAS_X(EPI)) {
+                const float2 t2 = *reinterpret_cast<const float2*>(A.ex + mrow * (size_t)P + pc);
+                xv[e][0] = t2.x; xv[e][1] = t2.y;
+            }
+            if (EPI == EPI_RESBWD) {
+                const float2 t2 = *reinterpret_cast<const float2*>(A.emask + mrow * (size_t)P + pc);
+                mk[e][0] = t2.x; mk[e][1] = t2.y;
+            }
+            if (has_add) {
+                const float* pa = A.addend + mrow * (size_t)addP;
+                if (!add_s2) {
+                    const float2 t2 = *reinterpret_cast<const float2*>(pa + pc);
+                    adv[e][0] = t2.x; adv[e][1] = t2.y;
+                } else {
+                    adv[e][0] = pa[aoff[0]]; adv[e][1] = pa[aoff[1]];
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int ml = lt * 16 + 4 * q + e;
+            const bool mv = lt < mt_run && ml < bm;
+            float v[2] = {acc[j][0][e], acc[j][1][e]};
+            float s1 = 0.f, s2 = 0.f;
+            pw_epi_row<EPI, false, 2>(A, v, pvs, has_add, av, adv[e], xv[e], mk[e], esc[e], esh[e], s1, s2);
+            if (mv && pv)
+                *reinterpret_cast<float2*>(A.y + ((size_t)n * M + m0 + ml) * (size_t)P + pl) = make_float2(v[0], v[1]);
+            if (EPI != EPI_PLAIN) {
+                s1 = row16_sum(s1);
+                s2 = row16_sum(s2);
+                if (r == 0) {
+                    red[((wave * U + j) * 16 + 4 * q + e) * 2] = mv ? s1 : 0.f;
+                    red[((wave * U + j) * 16 + 4 * q + e) * 2 + 1] = mv ? s2 : 0.f;
+                }
+            }
+        }
+    }
+    if (EPI != EPI_PLAIN && A.partial != nullptr) {
+        __syncthreads();
+        // one partial per (row, 64-voxel tile): the two half-tile waves of a row are summed here
+        for (int idx = tid; idx < bm * 2; idx += 256) {
+            const int ml = idx >> 1, which = idx & 1;
+            const int lt = ml >> 4, wv = (lt & 1) * 2, j = lt >> 1;
+            const float s = red[(((wv)*U + j) * 16 + (ml & 15)) * 2 + which] +
+                            red[(((wv + 1) * U + j) * 16 + (ml & 15)) * 2 + which];
+            A.partial[(((size_t)n * M + (m0 + ml)) * A.tiles + tile) * 2 + which] = s;
+        }
+    }
+}
+
 template <int IN, int EPI, int U>
 __global__ __launch_bounds__(256, 2) void pw4_kernel(const PwArgs A) {
     __shared__ __attribute__((aligned(16))) float Bl[2][P4_KC * P4_PITCH];
@@ -1019,29 +1062,8 @@ __global__ __launch_bounds__(256, 2) void pw4_kernel(const PwArgs A) {
     const int half = wave & 1, mpar = wave >> 1;
     const int K = A.K, P = A.P, M = A.M;
     const int kgroups = (K + 15) / 16, nchunks = (K + P4_KC - 1) / P4_KC;
-    const int mt_run = A.mt_run, mblocks = A.mblocks;
-    // item = ((voxel-tile group of 8) * mblocks + mb) * 8 + (voxel tile & 7), voxel tiles numbered over ALL samples
-    // (n * tiles + tile): item % 8 -- hence the XCD of the workgroup that owns it -- is the low tile bits, so the M
-    // blocks of one voxel tile share an XCD, and every workgroup has work even when a sample has < 8 tiles
-    const int VT = A.N * A.tiles;
-    const int items = ((VT + 7) / 8) * 8 * mblocks;
+    const int mt_run = A.mt_run;
     const int mtl = (M + 15) / 16 - 1;              // last packed M tile
-    const int G = gridDim.x;
-
-    auto next_valid = [&](int it, int& n, int& tile, int& mb) {
-        while (it < items) {
-            const int tlo = it & 7, rest = it >> 3;
-            mb = rest % mblocks;
-            const int vt = (rest / mblocks) * 8 + tlo;
-            if (vt < VT) {
-                n = vt / A.tiles;
-                tile = vt - n * A.tiles;
-                break;
-            }
-            it += G;
-        }
-        return it;
-    };
 
     // staging slots of this thread: rows (tid >> 4) and (tid >> 4) + 16 of a chunk, voxels col..col+3
     const int srow = tid >> 4, scol = (tid & 15) * 4;
@@ -1125,111 +1147,9 @@ __global__ __launch_bounds__(256, 2) void pw4_kernel(const PwArgs A) {
         }
     };
 
-    const bool has_add = EPI != EPI_STATS && A.addend != nullptr;
-    const bool add_s2 = has_add && A.addend_stride == 2;
-    const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
-
-    auto epilogue = [&](int n, int tile, int mb) {
-        const int m0 = mb * mt_run * 16;
-        const int bm = min(mt_run * 16, M - m0);
-        const int pl = tile * P4_BN + 32 * half + 2 * r;       // this lane's two voxels (P even: both or none valid)
-        const bool pv = pl < P;
-        const int pc = pv ? pl : 0;
-        int aoff[2] = {pc, pc + 1};
-        bool av[2] = {has_add && pv, has_add && pv};
-        if (add_s2) {
-#pragma unroll
-            for (int j2 = 0; j2 < 2; ++j2) {
-                const int p = pc + j2;
-                const int hw = A.H * A.W;
-                const int t = p / hw, rem = p - t * hw;
-                const int h = rem / A.W, w = rem - h * A.W;
-                const bool even = !(h & 1) && !(w & 1);
-                av[j2] = av[j2] && even;
-                aoff[j2] = even ? (t * A.Ho + (h >> 1)) * A.Wo + (w >> 1) : 0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int lt = mpar + 2 * j;
-            // phase 1: the four rows' reads, branch-free from clamped addresses
-            float xv[4][2], mk[4][2], adv[4][2], esc[4], esh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = lt * 16 + 4 * q + e;
-                const size_t mrow = (size_t)n * M + m0 + ((lt < mt_run && ml < bm) ? ml : 0);
-                if (EPI == EPI_ACTBWD) {
-                    const float2 c2 = *reinterpret_cast<const float2*>(A.ecoef + mrow * 2);
-                    esc[e] = c2.x; esh[e] = c2.y;
-                }
-                if (EPI_HAS_X(EPI)) {
-                    const float2 t2 = *reinterpret_cast<const float2*>(A.ex + mrow * (size_t)P + pc);
-                    xv[e][0] = t2.x; xv[e][1] = t2.y;
-                }
-                if (EPI == EPI_RESBWD) {
-                    const float2 t2 = *reinterpret_cast<const float2*>(A.emask + mrow * (size_t)P + pc);
-                    mk[e][0] = t2.x; mk[e][1] = t2.y;
-                }
-                if (has_add) {
-                    const float* pa = A.addend + mrow * (size_t)addP;
-                    if (!add_s2) {
-                        const float2 t2 = *reinterpret_cast<const float2*>(pa + pc);
-                        adv[e][0] = t2.x; adv[e][1] = t2.y;
-                    } else {
-                        adv[e][0] = pa[aoff[0]]; adv[e][1] = pa[aoff[1]];
-                    }
-                }
-            }
-            // phase 2
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = lt * 16 + 4 * q + e;
-                const bool mv = lt < mt_run && ml < bm;
-                float v[2] = {acc[j][0][e], acc[j][1][e]};
-                float s1 = 0.f, s2 = 0.f;
-                if (has_add) { v[0] += av[0] ? adv[e][0] : 0.f; v[1] += av[1] ? adv[e][1] : 0.f; }
-                if (EPI_HAS_X(EPI)) {
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const float xj = pv ? xv[e][j2] : 0.f;
-                        if (EPI == EPI_RESBWD) v[j2] = (pv && mk[e][j2] > 0.f) ? v[j2] : 0.f;
-                        else v[j2] = pv ? v[j2] * act_bwd(fmaf(esc[e], xj, esh[e]), A.e_act) : 0.f;
-                        s1 += v[j2];
-                        s2 = fmaf(v[j2], xj, s2);
-                    }
-                } else if (EPI == EPI_STATS) {
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) { v[j2] = pv ? v[j2] : 0.f; s1 += v[j2]; s2 = fmaf(v[j2], v[j2], s2); }
-                }
-                if (mv && pv)
-                    *reinterpret_cast<float2*>(A.y + ((size_t)n * M + m0 + ml) * (size_t)P + pl) = make_float2(v[0], v[1]);
-                if (EPI != EPI_PLAIN) {
-                    s1 = row16_sum(s1);
-                    s2 = row16_sum(s2);
-                    if (r == 0) {
-                        red[((wave * U + j) * 16 + 4 * q + e) * 2] = mv ? s1 : 0.f;
-                        red[((wave * U + j) * 16 + 4 * q + e) * 2 + 1] = mv ? s2 : 0.f;
-                    }
-                }
-            }
-        }
-        if (EPI != EPI_PLAIN && A.partial != nullptr) {
-            __syncthreads();
-            // one partial per (row, 64-voxel tile): the two half-tile waves of a row are summed here
-            for (int idx = tid; idx < bm * 2; idx += 256) {
-                const int ml = idx >> 1, which = idx & 1;
-                const int lt = ml >> 4, wv = (lt & 1) * 2, j = lt >> 1;
-                const float s = red[(((wv)*U + j) * 16 + (ml & 15)) * 2 + which] +
-                                red[(((wv + 1) * U + j) * 16 + (ml & 15)) * 2 + which];
-                A.partial[(((size_t)n * M + (m0 + ml)) * A.tiles + tile) * 2 + which] = s;
-            }
-        }
-    };
-
     // ---------------------------------- flat pipeline ----------------------------------
-    int n = 0, tile = 0, mb = 0;
-    int it = next_valid(blockIdx.x, n, tile, mb);
-    if (it >= items) return;
+    PwItemWalk cur(A);                  // where the MFMAs are
+    if (!cur.more()) return;
 #ifdef X3D_TRACE
     unsigned long long trv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int tri = 1;
@@ -1238,30 +1158,34 @@ __global__ __launch_bounds__(256, 2) void pw4_kernel(const PwArgs A) {
 #else
 #define TRN() do { } while (0)
 #endif
-    int pn = n, ptile = tile, pmb = mb, pit = it, pc_ = 0;          // prefetch cursor: chunk pc_ of item pit
-    auto advance = [&]() {
-        if (++pc_ == nchunks) { pc_ = 0; pit = next_valid(pit + G, pn, ptile, pmb); }
+    PwItemWalk pre = cur;               // where the prefetch is: one chunk ahead
+    auto request = [&](float4 (&a)[U][2]) { prefetch(pre.n, pre.tile, pre.c); fetch_a(pre.mb, pre.c, a); pre.advance(nchunks); };
+    auto chunk_done = [&]() {
+        if (cur.item_done(nchunks)) {
+            TRN();
+            pw_item_epilogue<EPI, U, P4_BN>(A, acc, red, wave, cur.n, cur.tile, cur.mb);
+            TRN();
+            zero_acc();
+            cur.next_item();
+        }
     };
     float4 a0[U][2], a1[U][2];
-    prefetch(pn, ptile, 0);
-    fetch_a(pmb, 0, a0);
-    advance();
+    request(a0);
     zero_acc();
-    int c = 0;
     for (;;) {
         store(0);
         __syncthreads();
-        bool more = pit < items;
-        if (more) { prefetch(pn, ptile, pc_); fetch_a(pmb, pc_, a1); advance(); }
+        bool more = pre.more();
+        if (more) request(a1);
         compute(0, a0);
-        if (++c == nchunks) { TRN(); epilogue(n, tile, mb); TRN(); zero_acc(); c = 0; it = next_valid(it + G, n, tile, mb); }
+        chunk_done();
         if (!more) break;
         store(1);
         __syncthreads();
-        more = pit < items;
-        if (more) { prefetch(pn, ptile, pc_); fetch_a(pmb, pc_, a0); advance(); }
+        more = pre.more();
+        if (more) request(a0);
         compute(1, a1);
-        if (++c == nchunks) { TRN(); epilogue(n, tile, mb); TRN(); zero_acc(); c = 0; it = next_valid(it + G, n, tile, mb); }
+        chunk_done();
         if (!more) break;
     }
 #ifdef X3D_TRACE
@@ -1308,32 +1232,11 @@ __global__ __launch_bounds__(256, 2) void pw5_kernel(const PwArgs A) {
     const int half = wave & 1, mpar = wave >> 1;
     const int K = A.K, P = A.P, M = A.M;
     const int kg16 = (K + 15) / 16, kg32 = (K + 31) / 32, nchunks = kg32;
-    const int mt_run = A.mt_run, mblocks = A.mblocks;
-    // item = ((voxel-tile group of 8) * mblocks + mb) * 8 + (voxel tile & 7), voxel tiles numbered over ALL samples
-    // (n * tiles + tile): item % 8 -- hence the XCD of the workgroup that owns it -- is the low tile bits, so the M
-    // blocks of one voxel tile share an XCD, and every workgroup has work even when a sample has < 8 tiles
-    const int VT = A.N * A.tiles;
-    const int items = ((VT + 7) / 8) * 8 * mblocks;
+    const int mt_run = A.mt_run;
     const int mtiles = (M + 15) / 16, mtl = mtiles - 1;
-    const int G = gridDim.x;
     // split-bf16 planes sit behind the fp32 image of the transposed pack
     const __bf16* wqh = reinterpret_cast<const __bf16*>(A.wp + (size_t)mtiles * kg16 * 256);
     const __bf16* wql = wqh + (size_t)mtiles * kg32 * 512;
-
-    auto next_valid = [&](int it, int& n, int& tile, int& mb) {
-        while (it < items) {
-            const int tlo = it & 7, rest = it >> 3;
-            mb = rest % mblocks;
-            const int vt = (rest / mblocks) * 8 + tlo;
-            if (vt < VT) {
-                n = vt / A.tiles;
-                tile = vt - n * A.tiles;
-                break;
-            }
-            it += G;
-        }
-        return it;
-    };
 
     // staging role: voxel `lane` of the tile, channels 8 * wave .. 8 * wave + 7 of the chunk
     const int srow = (lane & 31) >> 1, sodd = lane & 1, shalf = lane >> 5;
@@ -1406,130 +1309,39 @@ __global__ __launch_bounds__(256, 2) void pw5_kernel(const PwArgs A) {
             }
     };
 
-    const bool has_add = A.addend != nullptr;
-    const bool add_s2 = has_add && A.addend_stride == 2;
-    const long long addP = add_s2 ? (long long)A.T * A.Ho * A.Wo : (long long)P;
-
-    // identical to pw4_kernel's epilogue (lane: rows 4q + e of each unit, voxels 32 half + 2 r, + 1)
-    auto epilogue = [&](int n, int tile, int mb) {
-        const int m0 = mb * mt_run * 16;
-        const int bm = min(mt_run * 16, M - m0);
-        const int pl = tile * P5_BN + 32 * half + 2 * r;
-        const bool pv = pl < P;
-        const int pc = pv ? pl : 0;
-        int aoff[2] = {pc, pc + 1};
-        bool av[2] = {has_add && pv, has_add && pv};
-        if (add_s2) {
-#pragma unroll
-            for (int j2 = 0; j2 < 2; ++j2) {
-                const int p = pc + j2;
-                const int hw = A.H * A.W;
-                const int t = p / hw, rem = p - t * hw;
-                const int h = rem / A.W, w = rem - h * A.W;
-                const bool even = !(h & 1) && !(w & 1);
-                av[j2] = av[j2] && even;
-                aoff[j2] = even ? (t * A.Ho + (h >> 1)) * A.Wo + (w >> 1) : 0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int lt = mpar + 2 * j;
-            float xv[4][2], mk[4][2], adv[4][2], esc[4], esh[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = lt * 16 + 4 * q + e;
-                const size_t mrow = (size_t)n * M + m0 + ((lt < mt_run && ml < bm) ? ml : 0);
-                if (EPI == EPI_ACTBWD) {
-                    const float2 c2 = *reinterpret_cast<const float2*>(A.ecoef + mrow * 2);
-                    esc[e] = c2.x; esh[e] = c2.y;
-                }
-                if (EPI_HAS_X(EPI)) {
-                    const float2 t2 = *reinterpret_cast<const float2*>(A.ex + mrow * (size_t)P + pc);
-                    xv[e][0] = t2.x; xv[e][1] = t2.y;
-                }
-                if (EPI == EPI_RESBWD) {
-                    const float2 t2 = *reinterpret_cast<const float2*>(A.emask + mrow * (size_t)P + pc);
-                    mk[e][0] = t2.x; mk[e][1] = t2.y;
-                }
-                if (has_add) {
-                    const float* pa = A.addend + mrow * (size_t)addP;
-                    if (!add_s2) {
-                        const float2 t2 = *reinterpret_cast<const float2*>(pa + pc);
-                        adv[e][0] = t2.x; adv[e][1] = t2.y;
-                    } else {
-                        adv[e][0] = pa[aoff[0]]; adv[e][1] = pa[aoff[1]];
-                    }
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ml = lt * 16 + 4 * q + e;
-                const bool mv = lt < mt_run && ml < bm;
-                float v[2] = {acc[j][0][e], acc[j][1][e]};
-                float s1 = 0.f, s2 = 0.f;
-                if (has_add) { v[0] += av[0] ? adv[e][0] : 0.f; v[1] += av[1] ? adv[e][1] : 0.f; }
-                if (EPI_HAS_X(EPI)) {
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const float xj = pv ? xv[e][j2] : 0.f;
-                        if (EPI == EPI_RESBWD) v[j2] = (pv && mk[e][j2] > 0.f) ? v[j2] : 0.f;
-                        else v[j2] = pv ? v[j2] * act_bwd(fmaf(esc[e], xj, esh[e]), A.e_act) : 0.f;
-                        s1 += v[j2];
-                        s2 = fmaf(v[j2], xj, s2);
-                    }
-                }
-                if (mv && pv)
-                    *reinterpret_cast<float2*>(A.y + ((size_t)n * M + m0 + ml) * (size_t)P + pl) = make_float2(v[0], v[1]);
-                if (EPI != EPI_PLAIN) {
-                    s1 = row16_sum(s1);
-                    s2 = row16_sum(s2);
-                    if (r == 0) {
-                        red[((wave * U + j) * 16 + 4 * q + e) * 2] = mv ? s1 : 0.f;
-                        red[((wave * U + j) * 16 + 4 * q + e) * 2 + 1] = mv ? s2 : 0.f;
-                    }
-                }
-            }
-        }
-        if (EPI != EPI_PLAIN && A.partial != nullptr) {
-            __syncthreads();
-            for (int idx = tid; idx < bm * 2; idx += 256) {
-                const int ml = idx >> 1, which = idx & 1;
-                const int lt = ml >> 4, wv = (lt & 1) * 2, j = lt >> 1;
-                const float s = red[(((wv)*U + j) * 16 + (ml & 15)) * 2 + which] +
-                                red[(((wv + 1) * U + j) * 16 + (ml & 15)) * 2 + which];
-                A.partial[(((size_t)n * M + (m0 + ml)) * A.tiles + tile) * 2 + which] = s;
-            }
-        }
-    };
-
     // ---------------------------------- flat pipeline (as pw4_kernel) ----------------------------------
-    int n = 0, tile = 0, mb = 0;
-    int it = next_valid(blockIdx.x, n, tile, mb);
-    if (it >= items) return;
-    int pn = n, ptile = tile, pmb = mb, pit = it, pc_ = 0;
-    auto advance = [&]() {
-        if (++pc_ == nchunks) { pc_ = 0; pit = next_valid(pit + G, pn, ptile, pmb); }
+    PwItemWalk cur(A);
+    if (!cur.more()) return;
+    PwItemWalk pre = cur;
+    auto request = [&](bf16x8 (&ah)[U], bf16x8 (&al)[U]) {
+        prefetch(pre.n, pre.tile, pre.c);
+        fetch_a(pre.mb, pre.c, ah, al);
+        pre.advance(nchunks);
+    };
+    auto chunk_done = [&]() {
+        if (cur.item_done(nchunks)) {
+            pw_item_epilogue<EPI, U, P5_BN>(A, acc, red, wave, cur.n, cur.tile, cur.mb);
+            zero_acc();
+            cur.next_item();
+        }
     };
     bf16x8 a0h[U], a0l[U], a1h[U], a1l[U];
-    prefetch(pn, ptile, 0);
-    fetch_a(pmb, 0, a0h, a0l);
-    advance();
+    request(a0h, a0l);
     zero_acc();
-    int c = 0;
     for (;;) {
         store(0);
         __syncthreads();
-        bool more = pit < items;
-        if (more) { prefetch(pn, ptile, pc_); fetch_a(pmb, pc_, a1h, a1l); advance(); }
+        bool more = pre.more();
+        if (more) request(a1h, a1l);
         compute(0, a0h, a0l);
-        if (++c == nchunks) { epilogue(n, tile, mb); zero_acc(); c = 0; it = next_valid(it + G, n, tile, mb); }
+        chunk_done();
         if (!more) break;
         store(1);
         __syncthreads();
-        more = pit < items;
-        if (more) { prefetch(pn, ptile, pc_); fetch_a(pmb, pc_, a0h, a0l); advance(); }
+        more = pre.more();
+        if (more) request(a0h, a0l);
         compute(1, a1h, a1l);
-        if (++c == nchunks) { epilogue(n, tile, mb); zero_acc(); c = 0; it = next_valid(it + G, n, tile, mb); }
+        chunk_done();
         if (!more) break;
     }
 }
@@ -1589,18 +1401,19 @@ int launch_pw(PwArgs& A, hipStream_t s) {
     const bool dense = !A.strided && (A.Pin % 4 == 0);
     pw_plan(A.N, A.K, A.M, A.P, dense, &variant, &A.tiles, &A.mblocks, &A.mt_run);
     dim3 grid(cdiv(A.tiles, 8) * 8 * A.mblocks, A.N), block(256);
-    // mixed storage: only the packed streaming kernel (pw3) of this file reads / writes bf16 tensors
-    const bool mx = A.x_bf || A.y_bf || A.ex_bf;
-    if (mx && variant >= 2 && A.wp != nullptr) {
-        // large-channel layers outside the whole-K kernels of pw6.hip -- voxel count not a multiple of 4 (odd clip sizes), or
-        // K beyond their LDS tile (X3D-XL: 630 channels): the streaming kernel on the same 64-voxel tiles (P2_BN = P4_BN = 64),
-        // as in the "no packed weights" case below
+    // a tiled plan falls back to the streaming kernel on the same 64-voxel tiles (P2_BN = P4_BN = 64)
+    auto stream_on_tiles = [&]() {
         variant = 1;
         const int mtiles = cdiv(A.M, 16);
         A.mblocks = cdiv(mtiles, 4);
         A.mt_run = cdiv(mtiles, A.mblocks);
         grid = dim3(cdiv(A.tiles, 8) * 8 * A.mblocks, A.N);
-    }
+    };
+    // mixed storage: only the packed streaming kernel (pw3) of this file reads / writes bf16 tensors
+    const bool mx = A.x_bf || A.y_bf || A.ex_bf;
+    // large-channel layers outside the whole-K kernels of pw6.hip -- voxel count not a multiple of 4 (odd clip sizes), or
+    // K beyond their LDS tile (X3D-XL: 630 channels)
+    if (mx && variant >= 2 && A.wp != nullptr) stream_on_tiles();
     if (mx && !(variant <= 1 && A.wp != nullptr && A.K <= PW_MAXK)) {
         x3d_set_error("pw: no mixed-storage kernel for K=%d M=%d P=%d (packed=%d)", A.K, A.M, A.P, A.wp != nullptr);
         return X3D_EINVAL;
@@ -1610,32 +1423,29 @@ int launch_pw(PwArgs& A, hipStream_t s) {
         const int pg_max = x3d_opt(X3D_OPT_PW_PGRID);
         dim3 pgrid(min(items, pg_max));         // two resident workgroups per CU walk the item list
         const int U = cdiv(A.mt_run, 2);
+#define PW45_GO(KERNEL_, ...)   /* the kernel's leading template arguments; U units per wave is its last */ \
+    do {                                                                                                    \
+        if (U <= 2) hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, 2>), pgrid, block, 0, s, A);                    \
+        else if (U == 3) hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, 3>), pgrid, block, 0, s, A);               \
+        else hipLaunchKernelGGL((KERNEL_<__VA_ARGS__, 4>), pgrid, block, 0, s, A);                           \
+    } while (0)
         if (IN == IN_BNBWD && EPI != EPI_STATS && !x3d_opt(X3D_OPT_DGRAD_F32) && x3d_opt(X3D_OPT_BWD_TERMS) == 2) {
             // backward-data, two-term mode only: split-bf16 MFMA, hi + lo (the transposed pack carries the bf16 planes).  With
             // three-term operands (the default) the shapes that reach this point -- K beyond pw7's LDS tile: X3D-XL's 630
             // channels -- run on the exact fp32-MFMA pw4 below
             constexpr int E5 = (EPI == EPI_STATS) ? EPI_PLAIN : EPI;
             x3d_note_kernel("pw5_kernel");
-            if (U <= 2) hipLaunchKernelGGL((pw5_kernel<E5, 2>), pgrid, block, 0, s, A);
-            else if (U == 3) hipLaunchKernelGGL((pw5_kernel<E5, 3>), pgrid, block, 0, s, A);
-            else hipLaunchKernelGGL((pw5_kernel<E5, 4>), pgrid, block, 0, s, A);
+            PW45_GO(pw5_kernel, E5);
             X3D_LAUNCH_CHECK();
             return X3D_OK;
         }
         x3d_note_kernel("pw4_kernel");
-        if (U <= 2) hipLaunchKernelGGL((pw4_kernel<IN, EPI, 2>), pgrid, block, 0, s, A);
-        else if (U == 3) hipLaunchKernelGGL((pw4_kernel<IN, EPI, 3>), pgrid, block, 0, s, A);
-        else hipLaunchKernelGGL((pw4_kernel<IN, EPI, 4>), pgrid, block, 0, s, A);
+        PW45_GO(pw4_kernel, IN, EPI);
+#undef PW45_GO
         X3D_LAUNCH_CHECK();
         return X3D_OK;
     }
-    if (variant >= 2 && A.wp == nullptr) {      // no packed weights: streaming kernel on the same 64-voxel tiles
-        variant = 1;
-        const int mtiles = cdiv(A.M, 16);
-        A.mblocks = cdiv(mtiles, 4);
-        A.mt_run = cdiv(mtiles, A.mblocks);
-        grid = dim3(cdiv(A.tiles, 8) * 8 * A.mblocks, A.N);
-    }
+    if (variant >= 2 && A.wp == nullptr) stream_on_tiles();      // no packed weights
     if (variant == 2) {
         if (A.K > PW_MAXK) { x3d_set_error("pw: K=%d exceeds the coefficient table (%d)", A.K, PW_MAXK); return X3D_EINVAL; }
         const bool vec = dense && (A.P % 4 == 0);
