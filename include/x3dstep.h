@@ -230,6 +230,63 @@ int x3dstep_apply_groups_host(float* w, const float* g, float* m, int64_t n, con
                               float momentum, float weight_decay, float grad_scale, int first, int nesterov);
 
 /*
+ * Layer-wise adaptive rate scaling (LARS, You et al. 2017): a trust ratio per tensor, from the norm of the tensor's weights
+ * and the norm of its gradient, multiplied into the grouped update.  x3dstep_trust computes the ratios on the device after
+ * x3dstep_measure / x3dstep_observe on the same state and ring; x3dstep_apply_lars is x3dstep_apply_groups with the ratio in
+ * its element rule.
+ *
+ * x3dstep_trust: two launches, shaped like launches 1 and 2 of x3dstep_measure.
+ *   launch 1   a wave per item of the flat buffer's item table (X3DSTEP_ITEMS_PER_GROUP items to a workgroup): the fp64 sum
+ *              of squares of the item's elements of w, no hash, no count: the lane assignment, the order within a lane and
+ *              the halving reduction of `sumsq` above, 16-byte loads when w is 16-byte aligned.  workspace: fp64 [nitems]
+ *              (x3dstep_trust_workspace_bytes(nitems) bytes, 8-byte aligned).  An item that fails the per-item tests of
+ *              x3dstep_apply_groups (seg, len, start) gets a NaN partial, which gives its tensor a trust of 1.
+ *   launch 2   one workgroup, thread t takes the tensors t, t + 1024, ..: the items of tensor s added in item order with
+ *              the compensated sum, so that wsumsq[s] is, bit for bit, the sumsq[s] x3dstep_measure would record on w.
+ *   trust rule fp64, every operation rounded once.  c = state[X3DSTEP_S_STEP], rec the record in slot (c - 1) mod R, coef the
+ *              coefficient word of the state:
+ *     a    = sqrt(wsumsq[s]);   b = sqrt(rec.sumsq[s]) * (double) grad_scale * (double) coef
+ *     wd_s = weight_decay * hyper[s].wd_scale;   lr_s = lr * hyper[s].lr_scale       (fp32: the tensor rule's products)
+ *     den  = (b + (double) wd_s * a) + (double) eps;   r = ((double) eta[s] * a) / den
+ *     clip : r = lr_s > 0 ? min(r / (double) lr_s, 1.0) : 1.0
+ *     trust[s] = (float) r when eta[s] > 0, a > 0, b > 0, rec.nonfinite[s] == 0 and (float) r is finite, else 1.0f
+ *              Without clip: trust_coefficient * |w| / (|g| + wd |w| + eps), the LARS of torchlars and Lightning-Bolts; with
+ *              clip: apex's LARC in clipping mode.  eta[s] == 0 is the exemption: a trust of exactly 1.0f.  b is the norm of
+ *              the gradient the update applies: the recorded one times grad_scale and the clipping coefficient.
+ *   per-tensor tests  eta[s], hyper[s].lr_scale and hyper[s].wd_scale finite and >= 0, 0 <= seg_item[s] < seg_item[s + 1] <=
+ *              nitems: a tensor that fails one gets no store to wsumsq[s] or trust[s].  A counter of 0 (nothing measured):
+ *              neither launch stores anything.
+ * x3dstep_trust_host refuses the same with X3DSTEP_EINVAL and writes nothing, and also an item table that is not the in-order
+ * tiling of [0, n) or a seg_item that does not index it; both refuse null or misaligned pointers (w, eta, trust, hyper: 4
+ * bytes; the others 8), n < 1, eps < 0 or NaN and clip outside {0, 1}.  w, the state and the ring are only read.  No float
+ * atomics, no allocation, no synchronisation: capturable.
+ *
+ * x3dstep_apply_lars: x3dstep_apply_groups with `trust` (fp32 [S] on the device) after hyper.  The decision rule, the tensor
+ * rule, the walk, the per-item tests and the refusals are x3dstep_apply_groups', word for word; the element rule is
+ *     gi = coef == 1.0f ? g[i] : g[i] * coef;   t = gi * grad_scale;   gg = fmaf(wd_s, w[i], t)
+ *     gl = trust_s == 1.0f ? gg : gg * trust_s
+ *     m' = first ? gl : fmaf(momentum, m[i], gl)
+ *     u  = nesterov ? fmaf(momentum, m', gl) : m';            w' = w[i] - lr_s * u
+ * With every trust 1.0f: the bits of x3dstep_apply_groups.  One more per-item test: trust[seg] finite and >= 0; an item that
+ * fails it is left untouched by the kernel, and the twin refuses the call.  Both refuse a null or unaligned trust.
+ */
+size_t x3dstep_trust_workspace_bytes(int64_t nitems);
+int x3dstep_trust(const float* w, int64_t n, const X3DStepItem* items, const int32_t* seg_item, int64_t nitems,
+                  const X3DStepHyper* hyper, const float* eta, int S, const int64_t* state, const void* ring, int R,
+                  void* workspace, double* wsumsq, float* trust, float lr, float weight_decay, float grad_scale, float eps,
+                  int clip, void* stream);
+int x3dstep_trust_host(const float* w, int64_t n, const X3DStepItem* items, const int32_t* seg_item, int64_t nitems,
+                       const X3DStepHyper* hyper, const float* eta, int S, const int64_t* state, const void* ring, int R,
+                       void* workspace, double* wsumsq, float* trust, float lr, float weight_decay, float grad_scale,
+                       float eps, int clip);
+int x3dstep_apply_lars(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items, int64_t nitems,
+                       const X3DStepHyper* hyper, const float* trust, int S, int64_t* state, const void* ring, int R, float lr,
+                       float momentum, float weight_decay, float grad_scale, int first, int nesterov, void* stream);
+int x3dstep_apply_lars_host(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items, int64_t nitems,
+                            const X3DStepHyper* hyper, const float* trust, int S, int64_t* state, const void* ring, int R,
+                            float lr, float momentum, float weight_decay, float grad_scale, int first, int nesterov);
+
+/*
  * Saves and restores small buffers that a forward pass overwrites (the running statistics of batch normalisation).
  *   table  X3DStepKeep [nbuf]: the live buffers and where each lies in snap (fp32 [snap_n]); the ranges do not overlap
  *   items  the item table x3dstep_build_items gives for a segment table of snap (tensor s is buffer s; a tensor may be

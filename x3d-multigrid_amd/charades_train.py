@@ -202,7 +202,7 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
         device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
         skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
-        head_lr_scale=1.0, nesterov=False):
+        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -234,8 +234,14 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     nesterov=) -- no weight decay on the parameters with ndim <= 1, the fresh 157-way fc2.* at a multiple of the base rate
     (which ReduceLROnPlateau keeps driving), Nesterov momentum.  With any of them rank 0 prints one line before training
     (tensors and elements exempt from decay, tensors at a scaled rate) and 'optimizer_state_dict' gains 'tensor_hyper',
-    which `resume` restores."""
+    which `resume` restores.
+    lars / lars_clip / lars_eps: Trainer(lars=dict(eta=lars, clip=lars_clip, eps=lars_eps)) -- layer-wise adaptive rate
+    scaling, the parameters with ndim <= 1 exempt.  It implies the monitor and the hyper table, so their lines and fields
+    appear too; rank 0 prints one more line before training (tensors adapted and exempt, eta, eps, clip), the training log
+    line gains `trust MIN/MEDIAN/MAX` over the adapted tensors, and 'optimizer_state_dict' gains 'lars', which `resume`
+    restores."""
     from x3dhip import hypergroups
+    from x3dhip import lars as larsmod
     from x3dhip.trainer import Trainer
     loc = task == 'loc'
     ddp = process_group is not None and world > 1
@@ -287,9 +293,12 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                         clip_grad_norm=clip_grad_norm, monitor=monitor, skip_nonfinite=skip_nonfinite,
                         ema_decay=ema_decay, ema_warmup=ema_warmup,
                         tensor_hyper=hypergroups.recipe(x3d, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov,
+                        lars=None if lars is None else dict(eta=lars, clip=lars_clip, eps=lars_eps),
                         **(dict(process_group=process_group, world_size=world) if ddp else {}))
     if hasattr(optimizer, 'hyper'):
         say(hypergroups.describe(optimizer))
+    if lars is not None:
+        say(larsmod.describe(optimizer))
     mon = getattr(optimizer, 'monitor', None)
     ema = getattr(optimizer, 'ema', None)
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
@@ -385,6 +394,8 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                                                                                               float(mon.last_coef()))
                             if skip_nonfinite:
                                 gline += ' skipped {}'.format(mon.skip_report(max_skip_run))
+                            if lars is not None:
+                                gline += ' ' + larsmod.log_field(optimizer)
                             if loc:
                                 say(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}{}'
                                       .format(epochs, phase, steps, float(tot_loc_loss) / n, float(tot_cls_loss) / n,

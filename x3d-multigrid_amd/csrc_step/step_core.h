@@ -340,12 +340,14 @@ STEP_HD bool apply_begin(int64_t* state, const void* ring, int R, int S, bool co
 
 // One element: the multiply of the scale launch, then the arithmetic of the SGD kernel of libx3dhip.so (csrc/bn.hip
 // sgd_kernel) with the tensor's own rate and decay and the Nesterov look-ahead, each operation rounded once (both libraries
-// compile with -ffp-contract=off).  kPlain: no Nesterov term, whatever a.nesterov says.
-template <bool kPlain = false>
-STEP_HD void sgd_one(float& w, float g, float& m, float coef, const SgdArgs& a, float lr_s, float wd_s) {
+// compile with -ffp-contract=off).  kPlain: no Nesterov term, whatever a.nesterov says.  kTrust: the decayed gradient times
+// `trust` before the momentum (a trust of exactly 1.0f: no multiply, the same bits as without).
+template <bool kPlain = false, bool kTrust = false>
+STEP_HD void sgd_one(float& w, float g, float& m, float coef, const SgdArgs& a, float lr_s, float wd_s, float trust = 1.0f) {
     const float gi = coef == 1.0f ? g : scale_one(g, coef);
     const float t = gi * a.gs;
-    const float gg = fmaf(wd_s, w, t);
+    const float gd = fmaf(wd_s, w, t);
+    const float gg = kTrust && trust != 1.0f ? gd * trust : gd;      // x3dstep_apply_lars: the tensor's trust ratio
     const float mi = a.first ? gg : fmaf(a.mu, m, gg);
     const float u = !kPlain && a.nesterov ? fmaf(a.mu, mi, gg) : mi;
     const float step = lr_s * u;
@@ -400,14 +402,18 @@ constexpr int kGroupBatches = X3DSTEP_ITEM / (4 * kLanes * kGroupPieces);      /
 // What lane `lane` of the item's wave updates.  When the three addresses of the item are congruent mod 16: `head` elements
 // up to the 16-byte grid one by one (lane j the j-th), the 16-byte groups q = lane, lane + 64, .. in batches of
 // kGroupPieces (a batch's loads of w, g and m before its first store), then the tail one by one.  Otherwise the elements
-// j = lane, lane + 64, ...  Every element of the item is stored once; nothing outside it is read or written.
-STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, int lane, float coef, const SgdArgs& a) {
+// j = lane, lane + 64, ...  Every element of the item is stored once; nothing outside it is read or written.  kTrust: the
+// element rule of x3dstep_apply_lars, which multiplies by `trust`, the tensor's ratio.
+template <bool kTrust = false>
+STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, int lane, float coef, const SgdArgs& a,
+                        float trust = 1.0f) {
     float* wi = w + c.start;
     const float* gi = g + c.start;
     float* mi = m + c.start;
     const Plan p = walk_plan(mod16(wi), mod16(wi) == mod16(gi) && mod16(wi) == mod16(mi), c.len);
     if (!p.vec) {
-        for (int j = lane; j < c.len; j += kLanes) sgd_one(wi[j], gi[j], mi[j], coef, a, c.lr_s, c.wd_s);
+        for (int j = lane; j < c.len; j += kLanes)
+            sgd_one<false, kTrust>(wi[j], gi[j], mi[j], coef, a, c.lr_s, c.wd_s, trust);
         return;
     }
     const int head = (int)p.head, groups = (int)p.groups, tail = (int)p.tail;
@@ -432,14 +438,113 @@ STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, 
         for (int k = 0; k < kGroupPieces; ++k) {
             const int q = q0 + k * kLanes;
             if (q < groups) {
-                for (int e = 0; e < 4; ++e) sgd_one(wv[k].v[e], gv[k].v[e], mv[k].v[e], coef, a, c.lr_s, c.wd_s);
+                for (int e = 0; e < 4; ++e)
+                    sgd_one<false, kTrust>(wv[k].v[e], gv[k].v[e], mv[k].v[e], coef, a, c.lr_s, c.wd_s, trust);
                 mu[q] = mv[k];
                 wu[q] = wv[k];
             }
         }
     }
-    if (lane < head) sgd_one(wi[lane], gi[lane], mi[lane], coef, a, c.lr_s, c.wd_s);
-    if (lane < c.len - tail) sgd_one(wi[tail + lane], gi[tail + lane], mi[tail + lane], coef, a, c.lr_s, c.wd_s);
+    if (lane < head) sgd_one<false, kTrust>(wi[lane], gi[lane], mi[lane], coef, a, c.lr_s, c.wd_s, trust);
+    if (lane < c.len - tail)
+        sgd_one<false, kTrust>(wi[tail + lane], gi[tail + lane], mi[tail + lane], coef, a, c.lr_s, c.wd_s, trust);
+}
+
+// -- trust ratios (x3dstep_trust, x3dstep_apply_lars) ----------------------------------------------------------------------
+// The item tests of group_resolve alone, for the launch that reads w only: an item that fails them gets a NaN partial.
+STEP_HD bool trust_item_ok(const X3DStepItem& it, int S, int64_t n) {
+    return !(it.seg < 0 || it.seg >= S || it.len < 1 || it.len > X3DSTEP_ITEM || it.start < 0 || it.start > n - it.len);
+}
+
+// What lane `lane` adds for an item of w: lane_part's sum of squares, the same elements in the same order (the hash and the
+// count of lane_part are never used and fall away).
+STEP_HD double trust_lane(const float* w, const X3DStepItem& it, int lane, bool vec) {
+    return lane_part(w, it.start, it.len, 0, lane, vec).sumsq;
+}
+
+STEP_HD double trust_nan() {
+    const uint64_t u = 0x7ff8000000000000ull;
+    double d;
+    memcpy(&d, &u, 8);
+    return d;
+}
+
+// the partials of x3dstep_trust as a source of tensor_part: the scratch (far), or the kernel's copy of its head in LDS
+struct SumsqSource {
+    const double* far_p;
+    const double* near_p;
+    int cached;
+    STEP_HD_MEMBER int near_end(int a, int b) const { return b < cached ? b : (a > cached ? a : cached); }
+    STEP_HD_MEMBER Part near(int i) const {
+        const Part p = {near_p[i], 0, 0};
+        return p;
+    }
+    STEP_HD_MEMBER Part far(int i) const {
+        const Part p = {far_p[i], 0, 0};
+        return p;
+    }
+};
+
+struct TrustArgs {
+    float lr, wd, gs, eps;
+    int clip;
+};
+
+// the tests of tensor s: its rate of trust and its scales finite and >= 0, its items a range of the table
+STEP_HD bool trust_tensor_ok(const X3DStepHyper& h, float eta, int a, int b, int64_t nitems) {
+    return group_scale_ok(eta) && group_scale_ok(h.lr_scale) && group_scale_ok(h.wd_scale) && a >= 0 && a < b &&
+           (int64_t)b <= nitems;
+}
+
+// The trust ratio of one tensor: fp64, every operation rounded once.  wss: the sum of squares of its weights; gss, nf: the
+// sum of squares and the count of non-finite elements of its gradient in the latest record; coef: the clipping coefficient.
+STEP_HD float trust_rule(double wss, double gss, int32_t nf, float eta, const X3DStepHyper& h, float coef, const TrustArgs& t) {
+    const double a = sqrt(wss);
+    const double b0 = sqrt(gss);
+    const double b1 = b0 * (double)t.gs;
+    const double b = b1 * (double)coef;
+    const float wd_s = t.wd * h.wd_scale;
+    const float lr_s = t.lr * h.lr_scale;
+    const double dw = (double)wd_s * a;
+    const double d0 = b + dw;
+    const double den = d0 + (double)t.eps;
+    const double num = (double)eta * a;
+    double r = num / den;
+    if (t.clip) {
+        if (lr_s > 0.0f) {
+            r = r / (double)lr_s;
+            if (r > 1.0) r = 1.0;
+        } else {
+            r = 1.0;
+        }
+    }
+    const float r32 = (float)r;
+    const bool ok = eta > 0.0f && a > 0.0 && b > 0.0 && nf == 0 && r32 >= -3.402823466e38f && r32 <= 3.402823466e38f;
+    return ok ? r32 : 1.0f;
+}
+
+// What the thread of tensor s does in launch 2 of x3dstep_trust, after the decision (the counter is not 0).
+template <class Src>
+STEP_HD void trust_tensor(const Src& src, int s, const int32_t* seg_item, int64_t nitems, const X3DStepHyper* hyper,
+                          const float* eta, const Record& rec, float coef, const TrustArgs& t, double* wsumsq, float* trust) {
+    const int a = seg_item[s], b = seg_item[s + 1];
+    const X3DStepHyper h = hyper[s];
+    const float e = eta[s];
+    if (!trust_tensor_ok(h, e, a, b, nitems)) return;
+    const double wss = tensor_part(src, a, b).sumsq;
+    wsumsq[s] = wss;
+    trust[s] = trust_rule(wss, rec.sumsq[s], rec.nf[s], e, h, coef, t);
+}
+
+// Item i of x3dstep_apply_lars: group_resolve and the tensor's trust, which must be finite and >= 0.
+STEP_HD GroupItem lars_resolve(const X3DStepItem* items, int64_t i, const X3DStepHyper* hyper, const float* trust, int S,
+                               int64_t n, const SgdArgs& a, float* t) {
+    GroupItem r = group_resolve(items, i, hyper, S, n, a);
+    if (r.len > 0) {
+        *t = trust[items[i].seg];
+        if (!group_scale_ok(*t)) r.len = 0;
+    }
+    return r;
 }
 
 // -- the kept buffers (x3dstep_keep) ---------------------------------------------------------------------------------------

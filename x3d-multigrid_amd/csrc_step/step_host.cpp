@@ -282,22 +282,8 @@ int x3dstep_check_groups(const char* who, const float* w, const float* g, const 
     return X3DSTEP_OK;
 }
 
-extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items,
-                                         int64_t nitems, const X3DStepHyper* hyper, int S, int64_t* state, const void* ring,
-                                         int R, float lr, float momentum, float weight_decay, float grad_scale, int first,
-                                         int nesterov) {
-    using namespace x3ds;
-    const char* who = "x3dstep_apply_groups_host";
-    const int rc = x3dstep_check_groups(who, w, g, m, n, items, nitems, hyper, S, state, ring, R, momentum, first, nesterov);
-    if (rc) return rc;
-    // the tables are host memory here: refuse the call for what the kernel would leave out item by item
-    for (int s = 0; s < S; ++s) {
-        if (!group_scale_ok(hyper[s].lr_scale) || !group_scale_ok(hyper[s].wd_scale)) {
-            x3dstep_set_error("%s: tensor %d: a scale that is negative or not finite (lr_scale %g, wd_scale %g)", who, s,
-                              (double)hyper[s].lr_scale, (double)hyper[s].wd_scale);
-            return X3DSTEP_EINVAL;
-        }
-    }
+// the in-order tiling of [0, n) by the items of S tensors, which the twins that walk an item table ask for
+static int tiling_host_ok(const char* who, const X3DStepItem* items, int64_t nitems, int S, int64_t n) {
     int64_t at = 0;
     int32_t seg = 0;
     for (int64_t i = 0; i < nitems; ++i) {
@@ -315,6 +301,28 @@ extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int
         x3dstep_set_error("%s: the items cover %lld of %lld elements", who, (long long)at, (long long)n);
         return X3DSTEP_EINVAL;
     }
+    return X3DSTEP_OK;
+}
+
+// x3dstep_apply_groups_host (trust null) and x3dstep_apply_lars_host after their argument checks
+static int groups_host(const char* who, float* w, const float* g, float* m, int64_t n, const X3DStepItem* items,
+                       int64_t nitems, const X3DStepHyper* hyper, const float* trust, int S, int64_t* state, const void* ring,
+                       int R, float lr, float momentum, float weight_decay, float grad_scale, int first, int nesterov) {
+    using namespace x3ds;
+    // the tables are host memory here: refuse the call for what the kernel would leave out item by item
+    for (int s = 0; s < S; ++s) {
+        if (!group_scale_ok(hyper[s].lr_scale) || !group_scale_ok(hyper[s].wd_scale)) {
+            x3dstep_set_error("%s: tensor %d: a scale that is negative or not finite (lr_scale %g, wd_scale %g)", who, s,
+                              (double)hyper[s].lr_scale, (double)hyper[s].wd_scale);
+            return X3DSTEP_EINVAL;
+        }
+        if (trust && !group_scale_ok(trust[s])) {
+            x3dstep_set_error("%s: tensor %d: a trust ratio that is negative or not finite (%g)", who, s, (double)trust[s]);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    const int rt = tiling_host_ok(who, items, nitems, S, n);
+    if (rt) return rt;
     float coef = 1.0f;
     if (state) {
         if (!apply_decision(state, ring, R, S).go) {
@@ -325,10 +333,122 @@ extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int
     }
     const SgdArgs a = {lr, momentum, weight_decay, grad_scale, first, nesterov};
     for (int64_t i = 0; i < nitems; ++i) {
-        const GroupItem c = group_resolve(items, i, hyper, S, n, a);
-        if (c.len > 0)
-            for (int l = 0; l < kLanes; ++l) group_lane(w, g, m, c, l, coef, a);
+        float t = 1.0f;
+        const GroupItem c = trust ? lars_resolve(items, i, hyper, trust, S, n, a, &t) : group_resolve(items, i, hyper, S, n, a);
+        if (c.len < 1) continue;
+        for (int l = 0; l < kLanes; ++l) {
+            if (trust)
+                group_lane<true>(w, g, m, c, l, coef, a, t);
+            else
+                group_lane(w, g, m, c, l, coef, a);
+        }
     }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_apply_groups_host(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items,
+                                         int64_t nitems, const X3DStepHyper* hyper, int S, int64_t* state, const void* ring,
+                                         int R, float lr, float momentum, float weight_decay, float grad_scale, int first,
+                                         int nesterov) {
+    const char* who = "x3dstep_apply_groups_host";
+    const int rc = x3dstep_check_groups(who, w, g, m, n, items, nitems, hyper, S, state, ring, R, momentum, first, nesterov);
+    if (rc) return rc;
+    return groups_host(who, w, g, m, n, items, nitems, hyper, nullptr, S, state, ring, R, lr, momentum, weight_decay,
+                       grad_scale, first, nesterov);
+}
+
+// -- trust ratios -----------------------------------------------------------------------------------------------------------
+extern "C" size_t x3dstep_trust_workspace_bytes(int64_t nitems) {
+    return nitems < 1 || nitems > X3DSTEP_MAX_ITEMS ? 0 : (size_t)nitems * 8;
+}
+
+int x3dstep_check_lars(const char* who, const float* w, const float* g, const float* m, int64_t n, const X3DStepItem* items,
+                       int64_t nitems, const X3DStepHyper* hyper, const float* trust, int S, const int64_t* state,
+                       const void* ring, int R, float momentum, int first, int nesterov) {
+    const int rc = x3dstep_check_groups(who, w, g, m, n, items, nitems, hyper, S, state, ring, R, momentum, first, nesterov);
+    if (rc) return rc;
+    if (!trust || ((uintptr_t)trust & 3) != 0) {
+        x3dstep_set_error("%s: a null or unaligned trust table", who);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_apply_lars_host(float* w, const float* g, float* m, int64_t n, const X3DStepItem* items, int64_t nitems,
+                                       const X3DStepHyper* hyper, const float* trust, int S, int64_t* state, const void* ring,
+                                       int R, float lr, float momentum, float weight_decay, float grad_scale, int first,
+                                       int nesterov) {
+    const char* who = "x3dstep_apply_lars_host";
+    const int rc = x3dstep_check_lars(who, w, g, m, n, items, nitems, hyper, trust, S, state, ring, R, momentum, first, nesterov);
+    if (rc) return rc;
+    return groups_host(who, w, g, m, n, items, nitems, hyper, trust, S, state, ring, R, lr, momentum, weight_decay, grad_scale,
+                       first, nesterov);
+}
+
+// the argument checks x3dstep_trust and its twin share (no pointer is followed: the tables may be device memory)
+int x3dstep_check_trust(const char* who, const float* w, int64_t n, const X3DStepItem* items, const int32_t* seg_item,
+                        int64_t nitems, const X3DStepHyper* hyper, const float* eta, int S, const int64_t* state,
+                        const void* ring, int R, const void* workspace, const double* wsumsq, const float* trust, float eps,
+                        int clip) {
+    if (!w || !items || !seg_item || !hyper || !eta || !state || !ring || !workspace || !wsumsq || !trust || n < 1 ||
+        n > ((int64_t)1 << 40) || S < 1 || S > X3DSTEP_MAX_SEGMENTS || nitems < S || nitems > X3DSTEP_MAX_ITEMS || R < 1 ||
+        (((uintptr_t)w | (uintptr_t)seg_item | (uintptr_t)hyper | (uintptr_t)eta | (uintptr_t)trust) & 3) != 0 ||
+        (((uintptr_t)items | (uintptr_t)state | (uintptr_t)ring | (uintptr_t)workspace | (uintptr_t)wsumsq) & 7) != 0) {
+        x3dstep_set_error("%s: null or unaligned pointer, n %lld outside 1 .. 2^40, S %d outside 1 .. %d, nitems %lld outside "
+                          "S .. %d or R %d < 1", who, (long long)n, S, X3DSTEP_MAX_SEGMENTS, (long long)nitems,
+                          X3DSTEP_MAX_ITEMS, R);
+        return X3DSTEP_EINVAL;
+    }
+    if (!(eps >= 0.0f && eps <= 3.402823466e38f) || (clip != 0 && clip != 1)) {
+        x3dstep_set_error("%s: eps %g negative or not finite, or clip %d outside {0, 1}", who, (double)eps, clip);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_trust_host(const float* w, int64_t n, const X3DStepItem* items, const int32_t* seg_item, int64_t nitems,
+                                  const X3DStepHyper* hyper, const float* eta, int S, const int64_t* state, const void* ring,
+                                  int R, void* workspace, double* wsumsq, float* trust, float lr, float weight_decay,
+                                  float grad_scale, float eps, int clip) {
+    using namespace x3ds;
+    const char* who = "x3dstep_trust_host";
+    const int rc = x3dstep_check_trust(who, w, n, items, seg_item, nitems, hyper, eta, S, state, ring, R, workspace, wsumsq,
+                                       trust, eps, clip);
+    if (rc) return rc;
+    // the tables are host memory here: refuse the call for what the kernels would leave out item by item, tensor by tensor
+    const int rt = tiling_host_ok(who, items, nitems, S, n);
+    if (rt) return rt;
+    for (int s = 0; s < S; ++s) {
+        const int a = seg_item[s], b = seg_item[s + 1];
+        bool ok = trust_tensor_ok(hyper[s], eta[s], a, b, nitems) && (s > 0 || a == 0) && (s + 1 < S || b == nitems);
+        for (int i = a; ok && i < b; ++i) ok = items[i].seg == s;
+        if (!ok) {
+            x3dstep_set_error("%s: tensor %d: eta %g or a scale (%g, %g) negative or not finite, or items %d .. %d are not its "
+                              "own", who, s, (double)eta[s], (double)hyper[s].lr_scale, (double)hyper[s].wd_scale, a, b);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    const int64_t step = state[X3DSTEP_S_STEP];
+    if (step == 0) {
+        x3dstep_set_error("%s: the state's step counter is 0: nothing has been measured", who);
+        return X3DSTEP_EINVAL;
+    }
+    // launch 1
+    double* part = (double*)workspace;
+    const bool vec = ((uintptr_t)w & 15) == 0;
+    for (int64_t i = 0; i < nitems; ++i) {
+        double lanes[kLanes];
+        for (int l = 0; l < kLanes; ++l) lanes[l] = trust_item_ok(items[i], S, n) ? trust_lane(w, items[i], l, vec) : trust_nan();
+        for (int off = kLanes / 2; off > 0; off >>= 1)
+            for (int l = 0; l < off; ++l) lanes[l] = lanes[l] + lanes[l + off];
+        part[i] = lanes[0];
+    }
+    // launch 2
+    const Record rec = record_at((void*)ring, R, S, step - 1);
+    const float coef = state_coef(state);
+    const TrustArgs t = {lr, weight_decay, grad_scale, eps, clip};
+    const SumsqSource src = {part, part, 0};
+    for (int s = 0; s < S; ++s) trust_tensor(src, s, seg_item, nitems, hyper, eta, rec, coef, t, wsumsq, trust);
     return X3DSTEP_OK;
 }
 

@@ -16,6 +16,14 @@ int x3dstep_check_apply(const char* who, const float* w, const float* g, const f
 int x3dstep_check_groups(const char* who, const float* w, const float* g, const float* m, int64_t n, const X3DStepItem* items,
                          int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state, const void* ring, int R,
                          float momentum, int first, int nesterov);
+// x3dstep_check_groups and the trust table
+int x3dstep_check_lars(const char* who, const float* w, const float* g, const float* m, int64_t n, const X3DStepItem* items,
+                       int64_t nitems, const X3DStepHyper* hyper, const float* trust, int S, const int64_t* state,
+                       const void* ring, int R, float momentum, int first, int nesterov);
+int x3dstep_check_trust(const char* who, const float* w, int64_t n, const X3DStepItem* items, const int32_t* seg_item,
+                        int64_t nitems, const X3DStepHyper* hyper, const float* eta, int S, const int64_t* state,
+                        const void* ring, int R, const void* workspace, const double* wsumsq, const float* trust, float eps,
+                        int clip);
 int x3dstep_check_ema(const char* who, const float* e, const float* w, int64_t n, const int64_t* state, float decay);
 int x3dstep_check_swap(const char* who, const float* a, const float* b, int64_t n);
 // need_state: x3dstep_keep, which reads the state whatever the mode; the others pass X3DSTEP_KEEP_SAVE, x3dstep_swap_keep

@@ -41,7 +41,7 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
         skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
-        head_lr_scale=1.0, nesterov=False):
+        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
     every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
@@ -59,7 +59,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               world=world, base_bn_splits=base_bn_splits, clip_grad_norm=clip_grad_norm, monitor=monitor,
                               skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
                               ema_warmup=ema_warmup, precise_bn=precise_bn, wd_exempt_1d=wd_exempt_1d,
-                              head_lr_scale=head_lr_scale, nesterov=nesterov)
+                              head_lr_scale=head_lr_scale, nesterov=nesterov, lars=lars, lars_clip=lars_clip,
+                              lars_eps=lars_eps)
 
 
 def init_distributed():
@@ -133,6 +134,11 @@ def main(run_fn, default_save):
     parser.add_argument('--head-lr-scale', type=float, default=1.0, metavar='X',
                         help='train the classifier fc2.* at X times the base learning rate (default 1)')
     parser.add_argument('--nesterov', action='store_true', help='Nesterov momentum (off by default)')
+    parser.add_argument('--lars', type=float, nargs='?', const=0.001, default=None, metavar='ETA',
+                        help='layer-wise adaptive rate scaling on the GPU: every tensor\'s update times eta |w| / (|g| + wd |w| '
+                             '+ eps), parameters with ndim <= 1 exempt; bare: eta 0.001 (off by default)')
+    parser.add_argument('--lars-clip', action='store_true', help='with --lars: min(ratio / lr, 1) (LARC clipping mode)')
+    parser.add_argument('--lars-eps', type=float, default=1e-8, metavar='X', help='with --lars: eps of the ratio (default 1e-8)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -151,7 +157,8 @@ def main(run_fn, default_save):
                rank=rank, world=world, clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False,
                skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, ema_decay=args.ema_decay,
                ema_warmup=not args.no_ema_warmup, precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d,
-               head_lr_scale=args.head_lr_scale, nesterov=args.nesterov, **size)
+               head_lr_scale=args.head_lr_scale, nesterov=args.nesterov, lars=args.lars, lars_clip=args.lars_clip,
+               lars_eps=args.lars_eps, **size)
     finally:
         if pg is not None:
             import torch.distributed as dist

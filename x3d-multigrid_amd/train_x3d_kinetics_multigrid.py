@@ -206,7 +206,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
         frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8,
-        ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False, head_lr_scale=1.0, nesterov=False):
+        ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False, head_lr_scale=1.0, nesterov=False,
+        lars=None, lars_clip=False, lars_eps=1e-8):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -240,8 +241,14 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     wd_exempt_1d / head_lr_scale / nesterov: Trainer(tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale),
     nesterov=) -- no weight decay on the parameters with ndim <= 1, fc2.* at a multiple of the base rate, Nesterov momentum;
     the schedule keeps driving the base rate.  With any of them rank 0 prints one line before training (tensors and elements
-    exempt from decay, tensors at a scaled rate) and the optimizer's state in a checkpoint gains 'tensor_hyper'."""
+    exempt from decay, tensors at a scaled rate) and the optimizer's state in a checkpoint gains 'tensor_hyper'.
+    lars / lars_clip / lars_eps: Trainer(lars=dict(eta=lars, clip=lars_clip, eps=lars_eps)) -- layer-wise adaptive rate
+    scaling: every tensor's update times its trust ratio eta |w| / (|g| + wd |w| + eps), the parameters with ndim <= 1
+    exempt; lars_clip: min(ratio / lr, 1).  It implies the monitor and the hyper table, so their lines and fields appear
+    too; rank 0 prints one more line before training (tensors adapted and exempt, eta, eps, clip), the log line gains
+    `trust MIN/MEDIAN/MAX` over the adapted tensors, and the optimizer's state in a checkpoint gains 'lars'."""
     from x3dhip import hypergroups
+    from x3dhip import lars as larsmod
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -291,9 +298,12 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     optimizer = Trainer(model, lr=lr, momentum=0.9, weight_decay=5e-5, process_group=pg, world_size=world,
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update, clip_grad_norm=clip_grad_norm,
                         monitor=monitor, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                        tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov)
+                        tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov,
+                        lars=None if lars is None else dict(eta=lars, clip=lars_clip, eps=lars_eps))
     if rank == 0 and hasattr(optimizer, 'hyper'):
         print(hypergroups.describe(optimizer))
+    if rank == 0 and lars is not None:
+        print(larsmod.describe(optimizer))
     mon = getattr(optimizer, 'monitor', None)
     ema = getattr(optimizer, 'ema', None)
     lr_sched = MultiStepLR(optimizer, lr_schedule)
@@ -426,6 +436,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                                                                                   float(mon.last_coef()))
                 if skip_nonfinite:
                     gline += ' skipped {}'.format(mon.skip_report(max_skip_run))
+                if lars is not None:
+                    gline += ' ' + larsmod.log_field(optimizer)
                 if rank == 0:
                     dt = time.time() - t0
                     print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s{}'.format(
@@ -554,6 +566,11 @@ if __name__ == '__main__':
     parser.add_argument('--head-lr-scale', type=float, default=1.0, metavar='X',
                         help='train the classifier fc2.* at X times the base learning rate (default 1)')
     parser.add_argument('--nesterov', action='store_true', help='Nesterov momentum (off by default)')
+    parser.add_argument('--lars', type=float, nargs='?', const=0.001, default=None, metavar='ETA',
+                        help='layer-wise adaptive rate scaling on the GPU: every tensor\'s update times eta |w| / (|g| + wd |w| '
+                             '+ eps), parameters with ndim <= 1 exempt; bare: eta 0.001 (off by default)')
+    parser.add_argument('--lars-clip', action='store_true', help='with --lars: min(ratio / lr, 1) (LARC clipping mode)')
+    parser.add_argument('--lars-eps', type=float, default=1e-8, metavar='X', help='with --lars: eps of the ratio (default 1e-8)')
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -584,4 +601,4 @@ if __name__ == '__main__':
         clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, skip_nonfinite=args.skip_nonfinite,
         max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
         precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d, head_lr_scale=args.head_lr_scale,
-        nesterov=args.nesterov)
+        nesterov=args.nesterov, lars=args.lars, lars_clip=args.lars_clip, lars_eps=args.lars_eps)

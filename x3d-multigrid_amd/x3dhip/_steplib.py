@@ -63,6 +63,11 @@ SIGNATURES = {
     "x3dstep_hyper_bytes": (_Z, []),
     "x3dstep_apply_groups": (_I, [_P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I, _P]),
     "x3dstep_apply_groups_host": (_I, [_P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I]),
+    "x3dstep_trust_workspace_bytes": (_Z, [_L]),
+    "x3dstep_trust": (_I, [_P, _L, _P, _P, _L, _P, _P, _I, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _I, _P]),
+    "x3dstep_trust_host": (_I, [_P, _L, _P, _P, _L, _P, _P, _I, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _I]),
+    "x3dstep_apply_lars": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I, _P]),
+    "x3dstep_apply_lars_host": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I]),
     "x3dstep_keep": (_I, [_P, _I, _P, _L, _P, _L, _P, _I, _P]),
     "x3dstep_keep_host": (_I, [_P, _I, _P, _L, _P, _L, _P, _I]),
     "x3dstep_ema": (_I, [_P, _P, _L, _P, _L, _F, _I, _P]),

@@ -259,6 +259,128 @@ def apply_groups_host(w, g, m, tables, hyper, state, ring, R, lr, momentum=0.9, 
                                                    nesterov))
 
 
+def trust_workspace_bytes(nitems):
+    b = _steplib.lib().x3dstep_trust_workspace_bytes(int(nitems))
+    if b == 0:
+        raise ValueError("trust_workspace_bytes: %d items outside 1 .. %d" % (nitems, _steplib.MAX_ITEMS))
+    return int(b)
+
+
+def _need_hyper(who, hyper, S, dev):
+    if (not isinstance(hyper, torch.Tensor) or hyper.device != dev or hyper.dtype != torch.float32
+            or tuple(hyper.shape) != (S, 2) or not hyper.is_contiguous()):
+        raise ValueError("%s: hyper must be a contiguous float32 [%d, 2] on %s" % (who, S, dev))
+
+
+def _need_hyper_np(who, hyper, S):
+    if hyper.dtype == _steplib.HYPER_DT:
+        ok = hyper.ndim == 1 and hyper.size == S
+    else:
+        ok = hyper.dtype == np.float32 and hyper.shape == (S, 2)
+    if not ok or not hyper.flags.c_contiguous:
+        raise ValueError("%s: hyper must be a contiguous HYPER_DT [%d] or float32 [%d, 2]" % (who, S, S))
+
+
+def _need_vec(who, name, t, dtype, k, dev):
+    if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()
+            and t.numel() == k):
+        raise ValueError("%s: %s must be a contiguous %s [%d] on %s" % (who, name, dtype, k, dev))
+
+
+def _need_vec_np(who, name, a, dtype, k, writeable=False):
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.ndim == 1 and a.size == k and a.flags.c_contiguous
+            and (a.flags.writeable or not writeable)):
+        raise ValueError("%s: %s must be a contiguous %s [%d]" % (who, name, np.dtype(dtype).name, k))
+
+
+def _trust_args(who, eps, clip):
+    eps = float(eps)
+    if not (np.isfinite(eps) and eps >= 0.0) or clip not in (0, 1, False, True):
+        raise ValueError("%s: eps must be finite and >= 0 and clip 0 or 1 (got %r, %r)" % (who, eps, clip))
+    return eps, int(clip)
+
+
+def trust(w, tables, hyper, eta, state, ring, R, workspace, wsumsq, trust_out, lr, weight_decay=5e-5, grad_scale=1.0,
+          eps=1e-8, clip=False):
+    """The LARS trust ratios, two launches on the current stream after `measure` / `observe` on the same state and ring:
+    wsumsq[s] (float64 [S]) the sum of squares of tensor s of w, as `measure` would record it on w, and trust_out[s]
+    (float32 [S]) = eta[s] |w_s| / (|g_s| + wd_s |w_s| + eps), with `clip` min(that / lr_s, 1); exactly 1 where eta[s] is 0,
+    a norm is 0 or the gradient was not finite (include/x3dstep.h).  eta: float32 [S]; hyper: float32 [S, 2]; workspace:
+    uint8, trust_workspace_bytes(nitems); all on the tables' device.  w, the state and the ring are only read."""
+    R = int(R)
+    dev = _on_gpu("trust", tables.device)
+    _check_device("trust", w, tables, None, state, ring, R)
+    _need_hyper("trust", hyper, tables.S, dev)
+    _need_vec("trust", "eta", eta, torch.float32, tables.S, dev)
+    _need_vec("trust", "wsumsq", wsumsq, torch.float64, tables.S, dev)
+    _need_vec("trust", "trust_out", trust_out, torch.float32, tables.S, dev)
+    need = trust_workspace_bytes(tables.nitems)
+    if (not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8
+            or not workspace.is_contiguous() or workspace.numel() < need):
+        raise ValueError("trust: workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (need, dev))
+    eps, clip = _trust_args("trust", eps, clip)
+    check(_steplib.lib().x3dstep_trust(ptr(w), tables.n, ptr(tables.d_items), ptr(tables.d_seg_item), tables.nitems,
+                                       ptr(hyper), ptr(eta), tables.S, ptr(state), ptr(ring), R, ptr(workspace), ptr(wsumsq),
+                                       ptr(trust_out), float(lr), float(weight_decay), float(grad_scale), eps, clip, stream()))
+
+
+def trust_host(w, tables, hyper, eta, state, ring, R, workspace, wsumsq, trust_out, lr, weight_decay=5e-5, grad_scale=1.0,
+               eps=1e-8, clip=False):
+    """The CPU twin of `trust` on numpy arrays (wsumsq float64 [S] and trust_out float32 [S] are written)."""
+    R = int(R)
+    _check_host("trust_host", w, tables, None, state, ring, R, writeable=False)
+    _need_hyper_np("trust_host", hyper, tables.S)
+    _need_vec_np("trust_host", "eta", eta, np.float32, tables.S)
+    _need_vec_np("trust_host", "wsumsq", wsumsq, np.float64, tables.S, True)
+    _need_vec_np("trust_host", "trust_out", trust_out, np.float32, tables.S, True)
+    need = trust_workspace_bytes(tables.nitems)
+    if workspace.dtype != np.uint8 or not workspace.flags.c_contiguous or workspace.size < need:
+        raise ValueError("trust_host: workspace must be a contiguous uint8 array of at least %d bytes" % need)
+    check(_steplib.lib().x3dstep_trust_host(_np_ptr(w), tables.n, _np_ptr(tables.items), _np_ptr(tables.seg_item),
+                                            tables.nitems, _np_ptr(hyper), _np_ptr(eta), tables.S, _np_ptr(state),
+                                            _np_ptr(ring), R, _np_ptr(workspace), _np_ptr(wsumsq), _np_ptr(trust_out),
+                                            float(lr), float(weight_decay), float(grad_scale), float(eps), int(clip)))
+
+
+def apply_lars(w, g, m, tables, hyper, trust_in, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, grad_scale=1.0,
+               first=False, nesterov=False):
+    """`apply_groups` with the decayed gradient of tensor s multiplied by trust_in[s] (float32 [S] on the tables' device,
+    what `trust` wrote) before the momentum; every trust 1: the bits of `apply_groups` (include/x3dstep.h)."""
+    R = int(R)
+    dev = _on_gpu("apply_lars", tables.device)
+    for name, t in (("w", w), ("g", g), ("m", m)):
+        _need_flat("apply_lars", name, t, tables.n, dev)
+    _need_hyper("apply_lars", hyper, tables.S, dev)
+    _need_vec("apply_lars", "trust_in", trust_in, torch.float32, tables.S, dev)
+    if state is not None:
+        _check_device("apply_lars", g, tables, None, state, ring, R)
+    first, nesterov = _group_flags("apply_lars", momentum, first, nesterov)
+    check(_steplib.lib().x3dstep_apply_lars(ptr(w), ptr(g), ptr(m), tables.n, ptr(tables.d_items), tables.nitems,
+                                            ptr(hyper), ptr(trust_in), tables.S, None if state is None else ptr(state),
+                                            None if state is None else ptr(ring), R if state is not None else 0,
+                                            float(lr), float(momentum), float(weight_decay), float(grad_scale), first,
+                                            nesterov, stream()))
+
+
+def apply_lars_host(w, g, m, tables, hyper, trust_in, state, ring, R, lr, momentum=0.9, weight_decay=5e-5, grad_scale=1.0,
+                    first=False, nesterov=False):
+    """The CPU twin of `apply_lars` on numpy arrays (w and m are updated in place)."""
+    R = int(R)
+    for name, a, wr in (("w", w, True), ("g", g, False), ("m", m, True)):
+        _need_flat_np("apply_lars_host", name, a, tables.n, wr)
+    _need_hyper_np("apply_lars_host", hyper, tables.S)
+    _need_vec_np("apply_lars_host", "trust_in", trust_in, np.float32, tables.S)
+    if state is not None:
+        _check_host("apply_lars_host", g, tables, None, state, ring, R, writeable=False)
+    first, nesterov = _group_flags("apply_lars_host", momentum, first, nesterov)
+    check(_steplib.lib().x3dstep_apply_lars_host(_np_ptr(w), _np_ptr(g), _np_ptr(m), tables.n, _np_ptr(tables.items),
+                                                 tables.nitems, _np_ptr(hyper), _np_ptr(trust_in), tables.S,
+                                                 None if state is None else _np_ptr(state),
+                                                 None if state is None else _np_ptr(ring), R if state is not None else 0,
+                                                 float(lr), float(momentum), float(weight_decay), float(grad_scale), first,
+                                                 nesterov))
+
+
 class KeepTable:
     """The table `keep` takes for a list of small float32 buffers: where each lies in the snapshot (every buffer starts on
     a multiple of four elements, so that a 16-byte aligned buffer is copied in 16-byte groups), the item table of the

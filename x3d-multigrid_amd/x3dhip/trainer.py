@@ -121,7 +121,7 @@ class Trainer:
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
                  objective="ce", clip_grad_norm=None, monitor=False, skip_nonfinite=False, ema_decay=None,
-                 ema_warmup=True, tensor_hyper=None, nesterov=False):
+                 ema_warmup=True, tensor_hyper=None, nesterov=False, lars=None):
         """overlap: multi-rank steps are captured as two graphs around the first gradient bucket (False: single graph,
         all-reduce after the whole backward); force_split: the two-graph form on a single rank too (tests);
         force_collectives: all-reduce on a one-rank process group (the single-GPU RCCL test).  Round 4: constructor
@@ -189,6 +189,21 @@ class Trainer:
         without the key loads as before).  lr_scale = 0 is arithmetic, not a freeze: the momentum still moves and no
         backward pass is skipped.  Both at their defaults: no attribute, no launch, the update kernels called as before.
 
+        lars: layer-wise adaptive rate scaling (You et al. 2017).  A float (the rate of trust eta) or dict(eta=0.001,
+        eps=1e-8, clip=False, exempt_1d=True, exempt=()): every tensor's decayed gradient is multiplied by its trust ratio
+        eta |w| / (|g| + wd_s |w| + eps) before the momentum (clip=True: min(ratio / lr_s, 1), apex's LARC clipping mode).
+        Every parameter with ndim <= 1 gets eta = 0 -- a trust of exactly 1 -- unless exempt_1d=False; `exempt` holds
+        further fnmatch patterns (one that matches nothing raises).  Creates a lars.TrustTable (`self.lars`).  The
+        gradient's norms are read from the monitor's record and the scales from the hyper table, so lars implies a monitor
+        (as skip_nonfinite does) and a HyperTable (as nesterov does).  The update stays one sequence: measure or observe,
+        stepops.trust (two launches: the weights' sums of squares, the ratios), stepops.apply_lars in the place of
+        stepops.apply_groups, the restore; with skip_nonfinite the update reads the state and the ring, without it they
+        are not passed, exactly as for apply_groups.  Same place as ever: outside every captured graph, `lr` a host value,
+        on the updating call only under accumulation; data parallel: every rank computes the same ratios from the same
+        weights and the same all-reduced gradient, no collective is added.  state_dict() gains a top-level 'lars'
+        ({'names', 'eta', 'eps', 'clip'}), which load_state_dict restores.  None (the default): no attribute, not one
+        launch, the same checkpoint keys.
+
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
         afterwards is not part of the flat buffers and would not be trained."""
@@ -223,18 +238,36 @@ class Trainer:
                                    force_collectives=force_collectives)
         self.skip_nonfinite = bool(skip_nonfinite)
         self._keep = self._keep_old = None
-        if clip_grad_norm is not None or monitor or self.skip_nonfinite:
+        if clip_grad_norm is not None or monitor or self.skip_nonfinite or lars is not None:
             from .gradmonitor import GradMonitor
             ring = 64 if (monitor is True or not monitor) else int(monitor)
             self.monitor = GradMonitor(self.fp, [k for k, _ in model.named_parameters()], ring=ring,
                                        max_norm=clip_grad_norm, inv_world=1.0 / world_size)
-        if tensor_hyper is not None or nesterov:
+        if tensor_hyper is not None or nesterov or lars is not None:
             from .hypergroups import HyperTable
             if nesterov and not float(momentum) > 0.0:
                 raise ValueError("nesterov needs momentum > 0 (got %r)" % (momentum,))
             self.hyper = HyperTable(self.fp, [k for k, _ in model.named_parameters()], monitor=getattr(self, "monitor", None))
             if tensor_hyper:
                 self.hyper.apply(tensor_hyper)
+        if lars is not None:
+            from .lars import TrustTable
+            cfg = dict(eta=0.001, eps=1e-8, clip=False, exempt_1d=True, exempt=())
+            if isinstance(lars, dict):
+                extra = set(lars) - set(cfg)
+                if extra:
+                    raise ValueError("lars: unknown keys %s" % sorted(extra))
+                cfg.update(lars)
+            else:
+                cfg["eta"] = float(lars)
+            named = list(model.named_parameters())
+            self.lars = TrustTable(self.fp, [k for k, _ in named], self.monitor, self.hyper, eta=cfg["eta"], eps=cfg["eps"],
+                                   clip=cfg["clip"])
+            if cfg["exempt_1d"]:
+                self.lars.eta[[i for i, (_, p) in enumerate(named) if p.dim() <= 1]] = 0.0
+            for pattern in cfg["exempt"]:
+                self.lars._set(pattern, 0.0)
+            self.lars.upload()
         if ema_decay is not None:
             from .weightema import WeightEMA
             self.ema = WeightEMA(self.fp, model, ema_decay, warmup=ema_warmup, monitor=getattr(self, "monitor", None))
@@ -372,6 +405,7 @@ class Trainer:
         """One sequence whatever the configuration: measure or observe, the update, the restore."""
         mon = getattr(self, "monitor", None)
         hy = getattr(self, "hyper", None)
+        la = getattr(self, "lars", None)
         g = self.param_groups[0]
         guarded = self.skip_nonfinite
         w, gr, m = self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom
@@ -382,7 +416,12 @@ class Trainer:
             mon.measure(grad)                # the decision and the coefficient stay on the device
         elif mon is not None:                # statistics (and clipping) of exactly what the update is about to apply
             mon.observe(grad)                # scales the gradient in place
-        if hy is not None:                   # per-tensor scales and / or Nesterov: one launch that knows the tensors
+        if la is not None:                   # trust ratios: the weights' norms, the ratios, the update that takes them
+            la.compute(w, g['lr'], g['weight_decay'], 1.0 / self.world)
+            stepops.apply_lars(w, gr, m, hy.tables, hy.hyper, la.trust, mon.state if guarded else None,
+                               mon.ring if guarded else None, mon.R if guarded else 0, *arith, first=self.first,
+                               nesterov=bool(g['nesterov']))
+        elif hy is not None:                 # per-tensor scales and / or Nesterov: one launch that knows the tensors
             stepops.apply_groups(w, gr, m, hy.tables, hy.hyper, mon.state if guarded else None,
                                  mon.ring if guarded else None, mon.R if guarded else 0, *arith, first=self.first,
                                  nesterov=bool(g['nesterov']))
@@ -608,6 +647,9 @@ class Trainer:
         hy = getattr(self, "hyper", None)
         if hy is not None:
             sd['tensor_hyper'] = hy.state_dict()
+        la = getattr(self, "lars", None)
+        if la is not None:
+            sd['lars'] = la.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -618,6 +660,9 @@ class Trainer:
         hy = getattr(self, "hyper", None)
         if hy is not None and sd.get('tensor_hyper') is not None:
             hy.load_state_dict(sd['tensor_hyper'])
+        la = getattr(self, "lars", None)
+        if la is not None and sd.get('lars') is not None:
+            la.load_state_dict(sd['lars'])
         st = sd.get('state', {})
         if st:
             for i, (o, k) in enumerate(self.fp.offsets):
