@@ -81,3 +81,16 @@ def csrc_step_sha16():
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
+
+
+def csrc_mix_sha16():
+    """The same identity for the mixing library (libx3dmix.so): sha256 over csrc_mix/ (every file, by name) and
+    include/x3dmix.h, first 16 hex digits.  Kept apart from csrc_sha16, which the gradient-hash record is keyed on."""
+    h = hashlib.sha256()
+    d = os.path.join(ROOT, "x3d-multigrid_amd", "csrc_mix")
+    files = sorted(f for f in glob.glob(os.path.join(d, "*")) if os.path.isfile(f) and not f.endswith(".o")) + \
+        [os.path.join(ROOT, "include", "x3dmix.h")]
+    for f in files:
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, "rb").read())
+    return h.hexdigest()[:16]

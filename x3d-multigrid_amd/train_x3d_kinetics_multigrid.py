@@ -201,13 +201,19 @@ def stored_dataset(frames_mod, resident, pack, kw, subset, rank, world, common):
                                                      index_bits=index_bits, **common, **kw)
 
 
+def mixing_on(mixup=0.0, cutmix=0.0, mix_prob=None, mix_switch_prob=None, label_smoothing=0.0):
+    """Does any of the mixing arguments of `run` ask for the soft-target objective."""
+    return bool(mixup > 0 or cutmix > 0 or label_smoothing > 0 or mix_prob is not None or mix_switch_prob is not None)
+
+
 def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_UPSCALE, steps=0, max_steps_run=None,
         iterations_per_epoch=None, load_ckpt=None, save_model='models/x3d_multigrid_kinetics_rgb_sgd_',
         save_every=4000, use_graph=True, x3d_version=X3D_VERSION, log_every=20, val_every=None, val_batches=2,
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
         frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8,
         ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False, head_lr_scale=1.0, nesterov=False,
-        lars=None, lars_clip=False, lars_eps=1e-8):
+        lars=None, lars_clip=False, lars_eps=1e-8, mixup=0.0, cutmix=0.0, mix_prob=None, mix_switch_prob=None,
+        label_smoothing=0.0):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -246,7 +252,13 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     scaling: every tensor's update times its trust ratio eta |w| / (|g| + wd |w| + eps), the parameters with ndim <= 1
     exempt; lars_clip: min(ratio / lr, 1).  It implies the monitor and the hyper table, so their lines and fields appear
     too; rank 0 prints one more line before training (tensors adapted and exempt, eta, eps, clip), the log line gains
-    `trust MIN/MEDIAN/MAX` over the adapted tensors, and the optimizer's state in a checkpoint gains 'lars'."""
+    `trust MIN/MEDIAN/MAX` over the adapted tensors, and the optimizer's state in a checkpoint gains 'lars'.
+    mixup / cutmix / mix_prob / mix_switch_prob / label_smoothing: any of them (an alpha or a smoothing above 0, or one of the
+    probabilities given) trains with Trainer(objective="soft_ce") and puts a mixing.BatchMixer, seeded 1234 + rank, between
+    every batch (synthetic or from frames) and train_step: the clips are mixed by one launch, straight into the graph's
+    static input once it exists, and the labels become soft targets [B, 400].  Rank 0 prints one line before training; the
+    log line's acc stays against each sample's own hard label.  The mixer's generator is not in a checkpoint: a resumed run
+    restarts it from its seed.  With none of them the lines, the checkpoint keys and the bits are as before."""
     from x3dhip import hypergroups
     from x3dhip import lars as larsmod
     from x3dhip.trainer import Trainer
@@ -299,7 +311,18 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                         use_graph=use_graph, num_steps_per_update=num_steps_per_update, clip_grad_norm=clip_grad_norm,
                         monitor=monitor, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
                         tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov,
-                        lars=None if lars is None else dict(eta=lars, clip=lars_clip, eps=lars_eps))
+                        lars=None if lars is None else dict(eta=lars, clip=lars_clip, eps=lars_eps),
+                        **(dict(objective="soft_ce") if mixing_on(mixup, cutmix, mix_prob, mix_switch_prob, label_smoothing)
+                           else {}))
+    mixer = None
+    if optimizer.objective == "soft_ce":
+        from x3dhip.mixing import BatchMixer
+        mixer = BatchMixer(400, mixup_alpha=mixup, cutmix_alpha=cutmix, prob=1.0 if mix_prob is None else mix_prob,
+                           switch_prob=0.5 if mix_switch_prob is None else mix_switch_prob,
+                           label_smoothing=label_smoothing, seed=1234 + rank)
+        if rank == 0:
+            print('mixing: mixup alpha {:g} cutmix alpha {:g} prob {:g} switch prob {:g} label smoothing {:g}'.format(
+                mixer.mixup_alpha, mixer.cutmix_alpha, mixer.prob, mixer.switch_prob, mixer.label_smoothing))
     if rank == 0 and hasattr(optimizer, 'hyper'):
         print(hypergroups.describe(optimizer))
     if rank == 0 and lars is not None:
@@ -420,8 +443,12 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                 picks = [sampler.randrange(len(folder_ds)) for _ in range(B)]
                 inputs, labels, _, _ = folder_ds.batch(picks, task, long_ind)
                 T, H = inputs.shape[2], inputs.shape[3]
+            step_in, step_lab = inputs, labels
+            if mixer is not None:               # labels stays the hard label: the log line's acc is against it
+                step_in, step_lab = mixer(inputs, labels,
+                                          out=optimizer.static_inputs(inputs.shape) if use_graph else None)
             loss, logits = optimizer.train_step(
-                inputs, labels, pre_step=lambda: lr_warmup(lr, steps - st_steps, warmup_steps, optimizer))
+                step_in, step_lab, pre_step=lambda: lr_warmup(lr, steps - st_steps, warmup_steps, optimizer))
             clips += n_global
             if not optimizer.stepped:           # a micro-batch of an accumulated step (num_steps_per_update > 1)
                 continue
@@ -571,6 +598,16 @@ if __name__ == '__main__':
                              '+ eps), parameters with ndim <= 1 exempt; bare: eta 0.001 (off by default)')
     parser.add_argument('--lars-clip', action='store_true', help='with --lars: min(ratio / lr, 1) (LARC clipping mode)')
     parser.add_argument('--lars-eps', type=float, default=1e-8, metavar='X', help='with --lars: eps of the ratio (default 1e-8)')
+    parser.add_argument('--mixup', type=float, default=0.0, metavar='A',
+                        help='mixup with lam ~ Beta(A, A) on the GPU (0: off); trains against soft targets')
+    parser.add_argument('--cutmix', type=float, default=0.0, metavar='A',
+                        help='CutMix with lam ~ Beta(A, A), one box over all frames (0: off); trains against soft targets')
+    parser.add_argument('--mix-prob', type=float, default=None, metavar='P',
+                        help='probability that a batch is mixed at all (default 1)')
+    parser.add_argument('--mix-switch-prob', type=float, default=None, metavar='P',
+                        help='with --mixup and --cutmix: probability that a batch is CutMix (default 0.5)')
+    parser.add_argument('--label-smoothing', type=float, default=0.0, metavar='E',
+                        help="label smoothing (timm's rule) in the soft targets (0: off)")
     args = parser.parse_args()
     if (args.pack is not None and args.resident == 'files') or (args.val_pack is not None and args.val_resident == 'files'):
         parser.error('--pack / --val-pack is read into a store: give --resident / --val-resident hbm or host')
@@ -601,4 +638,6 @@ if __name__ == '__main__':
         clip_grad_norm=args.clip_grad_norm, monitor=args.monitor or False, skip_nonfinite=args.skip_nonfinite,
         max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
         precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d, head_lr_scale=args.head_lr_scale,
-        nesterov=args.nesterov, lars=args.lars, lars_clip=args.lars_clip, lars_eps=args.lars_eps)
+        nesterov=args.nesterov, lars=args.lars, lars_clip=args.lars_clip, lars_eps=args.lars_eps,
+        mixup=args.mixup, cutmix=args.cutmix, mix_prob=args.mix_prob, mix_switch_prob=args.mix_switch_prob,
+        label_smoothing=args.label_smoothing)

@@ -116,7 +116,7 @@ class Trainer:
     """Optimizer-like object (``param_groups``, ``state_dict`` in torch.optim.SGD's format) that
     owns the whole training step."""
 
-    OBJECTIVES = ("ce", "bce", "loc")
+    OBJECTIVES = ("ce", "bce", "loc", "soft_ce")
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
@@ -134,6 +134,9 @@ class Trainer:
           "loc": task 'loc', (cls_loss + loc_loss) / 2 of charades_losses.charades_loc_loss on the per-frame logits,
                  labels float [B, n_classes, TL] at any TL (train_x3d_charades_loc.py:168-189); `last_losses` holds
                  (cls_loss, loc_loss) of the latest step as device tensors.
+          "soft_ce": task 'class', mean softmax cross entropy against soft targets, labels float [B, n_classes]
+                 (F.cross_entropy(logits, probabilities); what mixing.BatchMixer makes of int64 labels under mixup, CutMix
+                 and label smoothing): the "ce" head with mixops.soft_ce in the place of ops.head_ce.
         The loss returned by train_step is the micro-batch objective; num_steps_per_update divides the gradient only.
 
         clip_grad_norm / monitor: either creates a gradmonitor.GradMonitor (`self.monitor`) that records per-tensor
@@ -210,9 +213,9 @@ class Trainer:
         if objective not in self.OBJECTIVES:
             raise ValueError("objective must be one of %s (got %r)" % (self.OBJECTIVES, objective))
         task = getattr(model, "task", "class")
-        if (objective == "bce" and task != "class") or (objective == "loc" and task != "loc"):
+        if (objective in ("bce", "soft_ce") and task != "class") or (objective == "loc" and task != "loc"):
             raise ValueError("objective %r needs a model with task %r (got task %r)"
-                             % (objective, "class" if objective == "bce" else "loc", task))
+                             % (objective, "loc" if objective == "loc" else "class", task))
         self.objective = objective
         self.last_losses = None
         self.model = model
@@ -317,13 +320,16 @@ class Trainer:
         hd, logits = ops.head_fwd(pooled, w1v, model.fc2.weight.data, model.fc2.bias.data, p, rng)
         if self.objective == "bce":
             loss, dlog = ops.head_bce(logits, y.contiguous(), 1.0, rng)
+        elif self.objective == "soft_ce":
+            from . import mixops
+            loss, dlog = mixops.soft_ce(logits, y.contiguous(), 1.0, rng)
         else:
             loss, dlog = ops.head_ce(logits, y.reshape(-1).contiguous(), rng)
         dpooled, _, _, _ = ops.head_bwd(dlog, hd, pooled, w1v, model.fc2.weight.data, p, outs=outs)
         return loss.view(()), logits.unsqueeze(2), dpooled
 
     def _check_labels(self, x, y):
-        """Labels of the "bce" / "loc" objectives, checked on the host before anything is launched ("ce" keeps its
+        """Labels of the "bce" / "soft_ce" / "loc" objectives, checked on the host before anything is launched ("ce" keeps its
         behaviour: its labels are checked by the kernels' wrappers)."""
         if self.objective == "ce":
             return
@@ -334,9 +340,10 @@ class Trainer:
             raise ValueError("objective %r needs float32 labels (got %s)"
                              % (self.objective, getattr(y, "dtype", type(y).__name__)))
         B, C = x.shape[0], model.fc2.out_features
-        if self.objective == "bce":
+        if self.objective in ("bce", "soft_ce"):
             if tuple(y.shape) != (B, C):
-                raise ValueError("objective 'bce' needs labels [B, n_classes] = %s (got %s)" % ((B, C), tuple(y.shape)))
+                raise ValueError("objective %r needs labels [B, n_classes] = %s (got %s)"
+                                 % (self.objective, (B, C), tuple(y.shape)))
         elif y.dim() != 3 or tuple(y.shape[:2]) != (B, C) or y.shape[2] < 1:
             raise ValueError("objective 'loc' needs labels [B, n_classes, TL] with B, n_classes = %s (got %s)"
                              % ((B, C), tuple(y.shape)))
@@ -435,7 +442,7 @@ class Trainer:
 
     # -- public -----------------------------------------------------------------------------
     def step(self, x, y):
-        """One optimizer step on clips x[B,3,T,H,W], labels y (objective "ce": [B, 1] int64; "bce": float [B, n_classes];
+        """One optimizer step on clips x[B,3,T,H,W], labels y (objective "ce": [B, 1] int64; "bce" / "soft_ce": float [B, n_classes];
         "loc": float [B, n_classes, TL]).  Returns (loss, logits)."""
         return self.train_step(x, y)
 
