@@ -287,6 +287,94 @@ int x3dstep_apply_lars_host(float* w, const float* g, float* m, int64_t n, const
                             float lr, float momentum, float weight_decay, float grad_scale, int first, int nesterov);
 
 /*
+ * Second-moment updates: Adam with L2, AdamW (Loshchilov & Hutter 2019) and LAMB (You et al. 2020) on the flat buffers, with
+ * a second flat state buffer v (exp_avg_sq) next to m (exp_avg).  The walk is x3dstep_apply_groups': one wave per item,
+ * X3DSTEP_ITEMS_PER_GROUP items to a workgroup, the grid from nitems alone; inside an item 16-byte groups when the item's
+ * addresses in all the buffers of the launch are congruent mod 16, element by element otherwise; a lane's loads for a batch of
+ * four groups are issued before that batch's first store; every element of an output is stored at most once.  No LDS in the
+ * item launches, no float atomics, no allocation, no synchronisation: capturable.
+ *   decision rule   x3dstep_apply_groups', word for word.  state non-null: every thread reads the counter, the `nonfinite`
+ *                   field of the latest record and the coefficient word; nonfinite > 0: no store to w, m or v; a counter of
+ *                   0: no store at all, and the twin refuses; thread 0 of workgroup 0 of x3dstep_adam and of
+ *                   x3dstep_lamb_apply writes state[X3DSTEP_S_SKIP], [X3DSTEP_S_SKIPPED] and [X3DSTEP_S_RUN].  state null:
+ *                   the unguarded form, coefficient 1, nothing read from or written to a state (ring and R are ignored).
+ *   tensor rule     lr_s = lr * hyper[seg].lr_scale; wd_s = weight_decay * hyper[seg].wd_scale: fp32, each rounded once,
+ *                   once per item.
+ *   count rule      x3dstep_ema's: k = count + (state ? state[X3DSTEP_S_STEP] - state[X3DSTEP_S_SKIPPED] : 0), formed by every
+ *                   thread of an applied update (a skipping launch's counting thread alone reads S_SKIPPED, before it writes
+ *                   it).  At the update's launches S_SKIPPED does not yet count this step, so k is the 1-based index of this
+ *                   update among the applied ones: a skipped update does not advance the bias correction.  k < 1: the twin
+ *                   refuses, the kernel stores nothing (the state words included).
+ *   correction rule fp64, once per wave: p1 = b1^k, p2 = b2^k by binary exponentiation in which every product is carried as
+ *                   an unevaluated sum of two doubles (Veltkamp's split: fp64 multiplies and adds only, each rounded once;
+ *                   pow_count of step_core.h, shared by kernel and twin), the leading part taken: within one ulp of the
+ *                   power, where plain repeated squaring doubles its rounding error at every step (about k ulp; 9e4 ulp at
+ *                   k = 10^6, b = 0.9999) and a libm pow would not give the same bits on both sides.
+ *                   bc1 = 1 - p1; bc2 = 1 - p2; step_s = (float)((double) lr_s / bc1); rbc2 = (float) sqrt(bc2);
+ *                   omb1 = (float)(1 - (double) b1); omb2 = (float)(1 - (double) b2); bc1f = (float) bc1; bc2f = (float) bc2
+ *   per-item tests  x3dstep_apply_groups': seg, len, start and both scales; x3dstep_lamb_apply also trust[seg] finite and
+ *                   >= 0.  An item that fails one is left untouched (x3dstep_lamb_moments: and gets NaN partials).
+ *
+ * x3dstep_adam: one launch.  Element rule, fp32, every operation rounded once (no contraction; sqrtf and / correctly rounded):
+ *     gi = coef == 1.0f ? g[i] : g[i] * coef;      t = gi * grad_scale
+ *     decoupled == 0:  t = fmaf(wd_s, w[i], t)                                  (Adam with L2)
+ *     m' = fmaf(b1, m[i], omb1 * t);               v' = fmaf(b2, v[i], omb2 * (t * t))
+ *     den = sqrtf(v') / rbc2 + eps
+ *     w1  = decoupled ? fmaf(-(lr_s * wd_s), w[i], w[i]) : w[i]                 (AdamW: w * (1 - lr wd))
+ *     w'  = w1 - step_s * (m' / den)
+ * torch.optim.AdamW / Adam (amsgrad off) in the order of torch's single-tensor path.  g is never written.
+ *
+ * LAMB: three launches, always the decoupled form, without a gradient pre-clipping of its own (the coefficient of
+ * x3dstep_measure is the clipping).  The direction of an element, fp32: t, m', v' as above;
+ *     mh = m' / bc1f;  vh = v' / bc2f;  r = fmaf(wd_s, w[i], mh / (sqrtf(vh) + eps))
+ *   x3dstep_lamb_moments  stores m' and v' (or nothing under the decision rule) and writes no state word.  Per item it writes
+ *              two fp64 partials, the sum of (double) r * (double) r and of (double) w * (double) w, with the lane assignment,
+ *              the order within a lane and the halving reduction of `sumsq` above (16-byte loads when w, g, m and v are all
+ *              16-byte aligned); a wave adds its item's partials from what it loads before it stores anything.  workspace:
+ *              fp64 [2 * nitems] (x3dstep_lamb_workspace_bytes(nitems), 8-byte aligned): the partials of r, then those of w.
+ *   x3dstep_lamb_trust    one workgroup, shaped like launch 2 of x3dstep_trust: per tensor the items are added in item order
+ *              with the compensated sum, so that wsumsq[s] and rsumsq[s] are, bit for bit, the sumsq[s] x3dstep_measure
+ *              would record on w and on r.  a = sqrt(wsumsq[s]); b = sqrt(rsumsq[s]); trust[s] = (float)(a / b) when
+ *              adapt[s] != 0, a > 0, b > 0, the record's nonfinite[s] == 0 (with a state) and the quotient is finite, else
+ *              1.0f.  adapt: uint8 [S] on the device, 0: exempt.  Per-tensor tests: both scales finite and >= 0,
+ *              0 <= seg_item[s] < seg_item[s + 1] <= nitems: a tensor that fails one gets no store.  Under the decision
+ *              rule a skipped step stores nothing here: the three outputs keep the latest applied update's values.
+ *   x3dstep_lamb_apply    recomputes r from the stored m', v' and from w (the same expression: the same bits) and stores
+ *              w' = w[i] - (lr_s * trust_s) * r; writes the three skip words under the decision rule.  m and v are only read.
+ *
+ * The twins refuse what x3dstep_apply_groups_host and x3dstep_trust_host refuse, and also a null or misaligned v, v
+ * overlapping w, g or m, b1 or b2 outside [0, 1) or NaN, eps < 0 or not finite, decoupled outside {0, 1} and k < 1 (the entry
+ * points too, except what only device memory tells).  A refused call writes nothing.
+ */
+size_t x3dstep_lamb_workspace_bytes(int64_t nitems);
+int x3dstep_adam(float* w, const float* g, float* m, float* v, int64_t n, const X3DStepItem* items, int64_t nitems,
+                 const X3DStepHyper* hyper, int S, int64_t* state, const void* ring, int R, int64_t count, float lr, float b1,
+                 float b2, float eps, float weight_decay, float grad_scale, int decoupled, void* stream);
+int x3dstep_adam_host(float* w, const float* g, float* m, float* v, int64_t n, const X3DStepItem* items, int64_t nitems,
+                      const X3DStepHyper* hyper, int S, int64_t* state, const void* ring, int R, int64_t count, float lr,
+                      float b1, float b2, float eps, float weight_decay, float grad_scale, int decoupled);
+int x3dstep_lamb_moments(const float* w, const float* g, float* m, float* v, int64_t n, const X3DStepItem* items,
+                         int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state, const void* ring, int R,
+                         int64_t count, float b1, float b2, float eps, float weight_decay, float grad_scale, void* workspace,
+                         void* stream);
+int x3dstep_lamb_moments_host(const float* w, const float* g, float* m, float* v, int64_t n, const X3DStepItem* items,
+                              int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state, const void* ring, int R,
+                              int64_t count, float b1, float b2, float eps, float weight_decay, float grad_scale,
+                              void* workspace);
+int x3dstep_lamb_trust(const int32_t* seg_item, int64_t nitems, const X3DStepHyper* hyper, const uint8_t* adapt, int S,
+                       const int64_t* state, const void* ring, int R, int64_t count, const void* workspace, double* wsumsq,
+                       double* rsumsq, float* trust, void* stream);
+int x3dstep_lamb_trust_host(const int32_t* seg_item, int64_t nitems, const X3DStepHyper* hyper, const uint8_t* adapt, int S,
+                            const int64_t* state, const void* ring, int R, int64_t count, const void* workspace,
+                            double* wsumsq, double* rsumsq, float* trust);
+int x3dstep_lamb_apply(float* w, const float* m, const float* v, int64_t n, const X3DStepItem* items, int64_t nitems,
+                       const X3DStepHyper* hyper, const float* trust, int S, int64_t* state, const void* ring, int R,
+                       int64_t count, float lr, float b1, float b2, float eps, float weight_decay, void* stream);
+int x3dstep_lamb_apply_host(float* w, const float* m, const float* v, int64_t n, const X3DStepItem* items, int64_t nitems,
+                            const X3DStepHyper* hyper, const float* trust, int S, int64_t* state, const void* ring, int R,
+                            int64_t count, float lr, float b1, float b2, float eps, float weight_decay);
+
+/*
  * Saves and restores small buffers that a forward pass overwrites (the running statistics of batch normalisation).
  *   table  X3DStepKeep [nbuf]: the live buffers and where each lies in snap (fp32 [snap_n]); the ranges do not overlap
  *   items  the item table x3dstep_build_items gives for a segment table of snap (tensor s is buffer s; a tensor may be

@@ -202,7 +202,8 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
         save_every=1000, use_graph=True, num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0,
         device=None, process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
         skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
-        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8):
+        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8, optimizer_name='sgd', betas=(0.9, 0.999),
+        adam_eps=1e-8):
     """One shared body of the two scripts' run().  task 'class': objective 'bce', validate_cls; task 'loc': objective
     'loc', validate_loc.  anno: the annotation file or its dict; videos: {id: uint8 CUDA tensor [n, H, W, 3]}.
     load_ckpt: a Kinetics checkpoint loaded before replace_logits(157); resume: a checkpoint of this loop (model,
@@ -239,7 +240,12 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
     scaling, the parameters with ndim <= 1 exempt.  It implies the monitor and the hyper table, so their lines and fields
     appear too; rank 0 prints one more line before training (tensors adapted and exempt, eta, eps, clip), the training log
     line gains `trust MIN/MEDIAN/MAX` over the adapted tensors, and 'optimizer_state_dict' gains 'lars', which `resume`
-    restores."""
+    restores.
+    optimizer_name / betas / adam_eps: Trainer(optimizer=, betas=, adam_eps=) -- 'adamw', 'adam' or 'lamb' in the place of SGD
+    on the same flat buffers (x3dhip/adamw.py).  Rank 0 prints one more line before training (the optimizer, betas, eps, the
+    tensors exempt from decay and, for lamb, from adaptation), with lamb the log line gains `trust MIN/MEDIAN/MAX`, and the
+    optimizer's state in a checkpoint takes torch.optim.AdamW's layout with a top-level 'optimizer'."""
+    from x3dhip import adamw as adammod
     from x3dhip import hypergroups
     from x3dhip import lars as larsmod
     from x3dhip.trainer import Trainer
@@ -294,11 +300,15 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                         ema_decay=ema_decay, ema_warmup=ema_warmup,
                         tensor_hyper=hypergroups.recipe(x3d, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov,
                         lars=None if lars is None else dict(eta=lars, clip=lars_clip, eps=lars_eps),
+                        **(dict(optimizer=optimizer_name, betas=tuple(betas), adam_eps=adam_eps)
+                           if optimizer_name != 'sgd' else {}),
                         **(dict(process_group=process_group, world_size=world) if ddp else {}))
     if hasattr(optimizer, 'hyper'):
         say(hypergroups.describe(optimizer))
     if lars is not None:
         say(larsmod.describe(optimizer))
+    if optimizer_name != 'sgd':
+        say(adammod.describe(optimizer, x3d))
     mon = getattr(optimizer, 'monitor', None)
     ema = getattr(optimizer, 'ema', None)
     lr_sched = ReduceLROnPlateau(optimizer, mode='min', patience=2, factor=0.1)
@@ -396,6 +406,8 @@ def run(task, anno, videos, init_lr, max_epochs, batch_size, save_model, x3d_ver
                                 gline += ' skipped {}'.format(mon.skip_report(max_skip_run))
                             if lars is not None:
                                 gline += ' ' + larsmod.log_field(optimizer)
+                            if optimizer_name == 'lamb':
+                                gline += ' ' + adammod.log_field(optimizer)
                             if loc:
                                 say(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} Tot Loss: {:.4f} mAP: {:.4f}{}'
                                       .format(epochs, phase, steps, float(tot_loc_loss) / n, float(tot_cls_loss) / n,

@@ -396,58 +396,101 @@ STEP_HD GroupItem group_resolve(const X3DStepItem* items, int64_t i, const X3DSt
     return r;
 }
 
-constexpr int kGroupPieces = 4;      // 16-byte groups of w, g and m a lane holds at once: a batch
+constexpr int kGroupPieces = 4;      // 16-byte groups of every buffer a lane holds at once: a batch
 constexpr int kGroupBatches = X3DSTEP_ITEM / (4 * kLanes * kGroupPieces);      // batches that cover a full item: 2
 
-// What lane `lane` of the item's wave updates.  When the three addresses of the item are congruent mod 16: `head` elements
-// up to the 16-byte grid one by one (lane j the j-th), the 16-byte groups q = lane, lane + 64, .. in batches of
-// kGroupPieces (a batch's loads of w, g and m before its first store), then the tail one by one.  Otherwise the elements
-// j = lane, lane + 64, ...  Every element of the item is stored once; nothing outside it is read or written.  kTrust: the
-// element rule of x3dstep_apply_lars, which multiplies by `trust`, the tensor's ratio.
+// An element rule of the update walk (rule_lane) says:
+//   kBufs         how many flat buffers it takes (all of them are loaded); kStores: the mask of those the walk stores
+//   one(x)        the rule on one element of each buffer, x[kBufs]
+// and holds what the item's tensor gave it (the rates, the trust).
+template <class Rule>
+STEP_HD void rule_at(const Rule& rule, float* const* p, int j) {
+    float x[Rule::kBufs];
+#pragma unroll
+    for (int b = 0; b < Rule::kBufs; ++b) x[b] = p[b][j];
+    rule.one(x);
+#pragma unroll
+    for (int b = Rule::kBufs - 1; b >= 0; --b)
+        if (Rule::kStores >> b & 1) p[b][j] = x[b];
+}
+
+// What lane `lane` of the item's wave updates.  When the addresses of the item in all the buffers are congruent mod 16:
+// `head` elements up to the 16-byte grid one by one (lane j the j-th), the 16-byte groups q = lane, lane + 64, .. in batches
+// of kGroupPieces (a batch's loads of every buffer before its first store), then the tail one by one.  Otherwise the
+// elements j = lane, lane + 64, ...  Every element of the item is stored once per stored buffer, the last buffer first;
+// nothing outside the item is read or written.
+template <class Rule>
+STEP_HD void rule_lane(const Rule& rule, float* const (&base)[Rule::kBufs], int64_t start, int len, int lane) {
+    constexpr int B = Rule::kBufs;
+    static_assert(B == 3 || B == 4, "the update walk takes three or four buffers");
+    float* p[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) p[b] = base[b] + start;
+    bool same = mod16(p[0]) == mod16(p[1]) && mod16(p[0]) == mod16(p[2]);
+    if constexpr (B == 4) same = same && mod16(p[0]) == mod16(p[3]);
+    const Plan pl = walk_plan(mod16(p[0]), same, len);
+    if (!pl.vec) {
+        for (int j = lane; j < len; j += kLanes) rule_at(rule, p, j);
+        return;
+    }
+    const int head = (int)pl.head, groups = (int)pl.groups, tail = (int)pl.tail;
+    Vec4* u[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) u[b] = (Vec4*)(p[b] + head);
+#pragma unroll
+    for (int t = 0; t < kGroupBatches; ++t) {        // groups <= X3DSTEP_ITEM / 4 = kGroupBatches * kGroupPieces * kLanes
+        const int q0 = lane + t * kGroupPieces * kLanes;
+        if (q0 >= groups) break;
+        Vec4 v[B][kGroupPieces];
+#pragma unroll
+        for (int k = 0; k < kGroupPieces; ++k) {
+            const int q = q0 + k * kLanes;
+            if (q < groups) {
+#pragma unroll
+                for (int b = 0; b < B; ++b) v[b][k] = u[b][q];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kGroupPieces; ++k) {
+            const int q = q0 + k * kLanes;
+            if (q < groups) {
+                for (int e = 0; e < 4; ++e) {
+                    float x[B];
+#pragma unroll
+                    for (int b = 0; b < B; ++b) x[b] = v[b][k].v[e];
+                    rule.one(x);
+#pragma unroll
+                    for (int b = 0; b < B; ++b)
+                        if (Rule::kStores >> b & 1) v[b][k].v[e] = x[b];
+                }
+#pragma unroll
+                for (int b = B - 1; b >= 0; --b)
+                    if (Rule::kStores >> b & 1) u[b][q] = v[b][k];
+            }
+        }
+    }
+    if (lane < head) rule_at(rule, p, lane);
+    if (lane < len - tail) rule_at(rule, p, tail + lane);
+}
+
+// the element rule of x3dstep_apply_groups over w, g, m; kTrust: that of x3dstep_apply_lars, which multiplies by `trust`
+template <bool kTrust>
+struct SgdRule {
+    static constexpr int kBufs = 3;
+    static constexpr unsigned kStores = 5;
+    float coef;
+    SgdArgs a;
+    float lr_s, wd_s, trust;
+    STEP_HD_MEMBER void one(float (&x)[3]) const { sgd_one<false, kTrust>(x[0], x[1], x[2], coef, a, lr_s, wd_s, trust); }
+};
+
+// the grouped update of one lane: rule_lane over w, g and m
 template <bool kTrust = false>
 STEP_HD void group_lane(float* w, const float* g, float* m, const GroupItem& c, int lane, float coef, const SgdArgs& a,
                         float trust = 1.0f) {
-    float* wi = w + c.start;
-    const float* gi = g + c.start;
-    float* mi = m + c.start;
-    const Plan p = walk_plan(mod16(wi), mod16(wi) == mod16(gi) && mod16(wi) == mod16(mi), c.len);
-    if (!p.vec) {
-        for (int j = lane; j < c.len; j += kLanes)
-            sgd_one<false, kTrust>(wi[j], gi[j], mi[j], coef, a, c.lr_s, c.wd_s, trust);
-        return;
-    }
-    const int head = (int)p.head, groups = (int)p.groups, tail = (int)p.tail;
-    Vec4* wu = (Vec4*)(wi + head);
-    const Vec4* gu = (const Vec4*)(gi + head);
-    Vec4* mu = (Vec4*)(mi + head);
-#pragma unroll
-    for (int b = 0; b < kGroupBatches; ++b) {        // groups <= X3DSTEP_ITEM / 4 = kGroupBatches * kGroupPieces * kLanes
-        const int q0 = lane + b * kGroupPieces * kLanes;
-        if (q0 >= groups) break;
-        Vec4 wv[kGroupPieces], gv[kGroupPieces], mv[kGroupPieces];
-#pragma unroll
-        for (int k = 0; k < kGroupPieces; ++k) {
-            const int q = q0 + k * kLanes;
-            if (q < groups) {
-                wv[k] = wu[q];
-                gv[k] = gu[q];
-                mv[k] = mu[q];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kGroupPieces; ++k) {
-            const int q = q0 + k * kLanes;
-            if (q < groups) {
-                for (int e = 0; e < 4; ++e)
-                    sgd_one<false, kTrust>(wv[k].v[e], gv[k].v[e], mv[k].v[e], coef, a, c.lr_s, c.wd_s, trust);
-                mu[q] = mv[k];
-                wu[q] = wv[k];
-            }
-        }
-    }
-    if (lane < head) sgd_one<false, kTrust>(wi[lane], gi[lane], mi[lane], coef, a, c.lr_s, c.wd_s, trust);
-    if (lane < c.len - tail)
-        sgd_one<false, kTrust>(wi[tail + lane], gi[tail + lane], mi[tail + lane], coef, a, c.lr_s, c.wd_s, trust);
+    const SgdRule<kTrust> rule = {coef, a, c.lr_s, c.wd_s, trust};
+    float* const base[3] = {w, (float*)g, m};
+    rule_lane(rule, base, c.start, c.len, lane);
 }
 
 // -- trust ratios (x3dstep_trust, x3dstep_apply_lars) ----------------------------------------------------------------------
@@ -545,6 +588,242 @@ STEP_HD GroupItem lars_resolve(const X3DStepItem* items, int64_t i, const X3DSte
         if (!group_scale_ok(*t)) r.len = 0;
     }
     return r;
+}
+
+// -- second-moment updates (x3dstep_adam, x3dstep_lamb_*) -------------------------------------------------------------------
+// b^k for k >= 0, the same bits in the kernel and in the twin: binary exponentiation in which every product is carried as
+// an unevaluated sum of two doubles (the exact product of the leading parts by Veltkamp's split, fp64 multiplies and adds
+// only, each rounded once), so that the rounding of one squaring is not doubled by the next: the leading part is within
+// one ulp of the power.  A libm pow would differ between the two sides.
+struct Pair {
+    double hi, lo;
+};
+
+STEP_HD Pair pair_mul(const Pair& x, const Pair& y) {
+    const double p = x.hi * y.hi;
+    const double cx = 134217729.0 * x.hi;
+    const double xh = cx - (cx - x.hi);
+    const double xl = x.hi - xh;
+    const double cy = 134217729.0 * y.hi;
+    const double yh = cy - (cy - y.hi);
+    const double yl = y.hi - yh;
+    const double e0 = ((xh * yh - p) + xh * yl + xl * yh) + xl * yl;      // x.hi * y.hi - p, exact above the subnormals
+    const double e = e0 + (x.hi * y.lo + x.lo * y.hi);
+    Pair r;
+    r.hi = p + e;
+    r.lo = e - (r.hi - p);
+    return r;
+}
+
+STEP_HD double pow_count(double b, int64_t k) {
+    Pair r = {1.0, 0.0}, x = {b, 0.0};
+    while (k > 0) {
+        if (k & 1) r = pair_mul(r, x);
+        k >>= 1;
+        if (k > 0) x = pair_mul(x, x);
+    }
+    return r.hi;
+}
+
+struct AdamArgs {
+    float lr, b1, b2, eps, wd, gs;
+    int decoupled;
+};
+
+STEP_HD int64_t ema_count(const int64_t* state, int64_t count);      // the count rule: the weight average's, below
+
+// b1 and b2 in [0, 1), eps finite and >= 0 (a NaN fails every comparison)
+STEP_HD bool adam_args_ok(float b1, float b2, float eps, int decoupled) {
+    return b1 >= 0.0f && b1 < 1.0f && b2 >= 0.0f && b2 < 1.0f && eps >= 0.0f && eps <= 3.402823466e38f &&
+           (decoupled == 0 || decoupled == 1);
+}
+
+// The start of a launch of these updates: the decision rule of apply_begin, then the count rule of ema_count (k: the
+// 1-based index of this update among the applied ones).  false: the lane stores nothing.  `counting`: the one thread
+// of the launch that writes the three skip words (no launch of x3dstep_lamb_moments / _trust has one).  S_SKIPPED is read
+// after the decision, by the lanes of an applied update alone: a skipping launch's counting thread is its only reader.
+STEP_HD bool adam_begin(int64_t* state, const void* ring, int R, int S, int64_t count, bool counting, float* coef,
+                        int64_t* k) {
+    *coef = 1.0f;
+    if (!state) {
+        *k = count;
+        return count >= 1;
+    }
+    const Decision d = apply_decision(state, ring, R, S);
+    if (!d.go) return false;
+    if (d.skip) {
+        if (counting && ema_count(state, count) >= 1) apply_counters(state, true);
+        return false;
+    }
+    *k = ema_count(state, count);
+    if (*k < 1) return false;
+    if (counting) apply_counters(state, false);
+    *coef = d.coef;
+    return true;
+}
+
+// the correction rule: fp64, each value rounded once
+struct AdamCorr {
+    double bc1, bc2;
+    float rbc2, omb1, omb2, bc1f, bc2f;
+};
+
+STEP_HD AdamCorr adam_corr(int64_t k, float b1, float b2) {
+    AdamCorr c;
+    c.bc1 = 1.0 - pow_count((double)b1, k);
+    c.bc2 = 1.0 - pow_count((double)b2, k);
+    c.rbc2 = (float)sqrt(c.bc2);
+    c.omb1 = (float)(1.0 - (double)b1);
+    c.omb2 = (float)(1.0 - (double)b2);
+    c.bc1f = (float)c.bc1;
+    c.bc2f = (float)c.bc2;
+    return c;
+}
+
+STEP_HD float adam_step_size(float lr_s, const AdamCorr& c) { return (float)((double)lr_s / c.bc1); }
+
+// the gradient an element's moments take, before the L2 term: the clipping multiply, then grad_scale
+STEP_HD float adam_grad(float g, float coef, float gs) {
+    const float gi = coef == 1.0f ? g : scale_one(g, coef);
+    return gi * gs;
+}
+
+// both moments of one element, fp32, every operation rounded once
+STEP_HD void adam_moments(float t, float& m, float& v, const AdamArgs& a, const AdamCorr& c) {
+    const float p = c.omb1 * t;
+    const float tt = t * t;
+    const float q = c.omb2 * tt;
+    m = fmaf(a.b1, m, p);
+    v = fmaf(a.b2, v, q);
+}
+
+// x3dstep_adam over w, g, m, v: torch.optim.Adam / AdamW in the order of torch's single-tensor path
+struct AdamRule {
+    static constexpr int kBufs = 4;
+    static constexpr unsigned kStores = 13;
+    AdamArgs a;
+    AdamCorr c;
+    float coef, wd_s, step_s, lrwd;      // lrwd: lr_s * wd_s, rounded once
+    STEP_HD_MEMBER void one(float (&x)[4]) const {
+        const float w = x[0];
+        float t = adam_grad(x[1], coef, a.gs);
+        if (!a.decoupled) t = fmaf(wd_s, w, t);
+        adam_moments(t, x[2], x[3], a, c);
+        const float sq = sqrtf(x[3]);
+        const float d0 = sq / c.rbc2;
+        const float den = d0 + a.eps;
+        const float w1 = a.decoupled ? fmaf(-lrwd, w, w) : w;
+        const float u = x[2] / den;
+        const float du = step_s * u;
+        x[0] = w1 - du;
+    }
+};
+
+// the direction of an element of LAMB from its new moments: the corrected Adam quotient plus the decay term
+STEP_HD float lamb_dir(float w, float m1, float v1, float eps, float wd_s, const AdamCorr& c) {
+    const float mh = m1 / c.bc1f;
+    const float vh = v1 / c.bc2f;
+    const float sq = sqrtf(vh);
+    const float den = sq + eps;
+    const float u = mh / den;
+    return fmaf(wd_s, w, u);
+}
+
+// launch 1 of LAMB over g, m, v: the moments
+struct LambMomentsRule {
+    static constexpr int kBufs = 3;
+    static constexpr unsigned kStores = 6;
+    AdamArgs a;
+    AdamCorr c;
+    float coef;
+    STEP_HD_MEMBER void one(float (&x)[3]) const { adam_moments(adam_grad(x[0], coef, a.gs), x[1], x[2], a, c); }
+};
+
+// launch 3 of LAMB over w, m, v: the direction again from the stored moments, and the step along it
+struct LambApplyRule {
+    static constexpr int kBufs = 3;
+    static constexpr unsigned kStores = 1;
+    AdamArgs a;
+    AdamCorr c;
+    float wd_s, lrt;                     // lrt: lr_s * trust_s, rounded once
+    STEP_HD_MEMBER void one(float (&x)[3]) const {
+        const float r = lamb_dir(x[0], x[1], x[2], a.eps, wd_s, c);
+        const float dr = lrt * r;
+        x[0] = x[0] - dr;
+    }
+};
+
+struct LambSums {
+    double r, w;
+};
+
+// What lane `lane` adds for an item in launch 1 of LAMB, before any store: the squares of the direction r (from the
+// moments the launch is about to store) and of w, over lane_part's elements in lane_part's order (the groups of four
+// elements q = lane, lane + 64, .. by (start mod 4 + j) / 4; `vec`: all four buffers are 16-byte aligned).
+STEP_HD LambSums lamb_lane_sums(const float* w, const float* g, const float* m, const float* v, const GroupItem& it, int lane,
+                                bool vec, const LambMomentsRule& rule) {
+    LambSums s = {0.0, 0.0};
+    const int r0 = (int)(it.start & 3);
+    const int groups = (r0 + it.len + 3) >> 2;
+    for (int q = lane; q < groups; q += kLanes) {
+        const int j0 = 4 * q - r0;
+        Vec4 wv, gv, mv, vv;
+        const bool whole = j0 >= 0 && j0 + 4 <= it.len;
+        if (vec && whole) {
+            wv = *(const Vec4*)(w + it.start + j0);
+            gv = *(const Vec4*)(g + it.start + j0);
+            mv = *(const Vec4*)(m + it.start + j0);
+            vv = *(const Vec4*)(v + it.start + j0);
+        } else {
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + e;
+                const bool in = j >= 0 && j < it.len;
+                wv.v[e] = in ? w[it.start + j] : 0.0f;
+                gv.v[e] = in ? g[it.start + j] : 0.0f;
+                mv.v[e] = in ? m[it.start + j] : 0.0f;
+                vv.v[e] = in ? v[it.start + j] : 0.0f;
+            }
+        }
+        for (int e = 0; e < 4; ++e) {
+            const int j = j0 + e;
+            if (j < 0 || j >= it.len) continue;
+            float x[3] = {gv.v[e], mv.v[e], vv.v[e]};
+            rule.one(x);
+            const double r = (double)lamb_dir(wv.v[e], x[1], x[2], rule.a.eps, it.wd_s, rule.c);
+            const double wd = (double)wv.v[e];
+            s.r = s.r + r * r;           // the product of two widened fp32 values is exact
+            s.w = s.w + wd * wd;
+        }
+    }
+    return s;
+}
+
+// the tests of tensor s in launch 2 of LAMB: its scales finite and >= 0, its items a range of the table
+STEP_HD bool lamb_tensor_ok(const X3DStepHyper& h, int a, int b, int64_t nitems) {
+    return group_scale_ok(h.lr_scale) && group_scale_ok(h.wd_scale) && a >= 0 && a < b && (int64_t)b <= nitems;
+}
+
+// the trust ratio of one tensor of LAMB: |w| / |r| in fp64, rounded to fp32 once; 1 where it does not apply
+STEP_HD float lamb_trust_rule(double wss, double rss, int adapt, int32_t nf) {
+    const double a = sqrt(wss);
+    const double b = sqrt(rss);
+    const float q = (float)(a / b);
+    const bool ok = adapt != 0 && a > 0.0 && b > 0.0 && nf == 0 && q >= 0.0f && q <= 3.402823466e38f;
+    return ok ? q : 1.0f;
+}
+
+// What the thread of tensor s does in launch 2 of LAMB, after the decision.  nf: the record's counts, or null without a state.
+template <class Src>
+STEP_HD void lamb_tensor(const Src& rsrc, const Src& wsrc, int s, const int32_t* seg_item, int64_t nitems,
+                         const X3DStepHyper* hyper, const uint8_t* adapt, const int32_t* nf, double* wsumsq, double* rsumsq,
+                         float* trust) {
+    const int a = seg_item[s], b = seg_item[s + 1];
+    if (!lamb_tensor_ok(hyper[s], a, b, nitems)) return;
+    const double wss = tensor_part(wsrc, a, b).sumsq;
+    const double rss = tensor_part(rsrc, a, b).sumsq;
+    wsumsq[s] = wss;
+    rsumsq[s] = rss;
+    trust[s] = lamb_trust_rule(wss, rss, adapt[s], nf ? nf[s] : 0);
 }
 
 // -- the kept buffers (x3dstep_keep) ---------------------------------------------------------------------------------------

@@ -452,6 +452,246 @@ extern "C" int x3dstep_trust_host(const float* w, int64_t n, const X3DStepItem* 
     return X3DSTEP_OK;
 }
 
+// -- second-moment updates ----------------------------------------------------------------------------------------------------
+extern "C" size_t x3dstep_lamb_workspace_bytes(int64_t nitems) {
+    return nitems < 1 || nitems > X3DSTEP_MAX_ITEMS ? 0 : (size_t)nitems * 16;
+}
+
+int x3dstep_check_adam(const char* who, const float* w, const float* g, const float* m, const float* v, bool need_g, int64_t n,
+                       const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state,
+                       const void* ring, int R, int64_t count, float b1, float b2, float eps, int decoupled) {
+    if (!w || (need_g && !g) || !m || !v || !items || !hyper || n < 1 || n > ((int64_t)1 << 40) || nitems < 1 ||
+        nitems > X3DSTEP_MAX_ITEMS || S < 1 || S > X3DSTEP_MAX_SEGMENTS ||
+        (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)hyper) & 3) != 0 ||
+        ((uintptr_t)items & 7) != 0) {
+        x3dstep_set_error("%s: null or unaligned pointer, n %lld outside 1 .. 2^40, nitems %lld outside 1 .. %d or S %d outside "
+                          "1 .. %d", who, (long long)n, (long long)nitems, X3DSTEP_MAX_ITEMS, S, X3DSTEP_MAX_SEGMENTS);
+        return X3DSTEP_EINVAL;
+    }
+    const float* p[4] = {w, g, m, v};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (p[a] && p[b] && ranges_overlap(p[a], p[b], n)) {
+                x3dstep_set_error("%s: w, g, m and v overlap", who);
+                return X3DSTEP_EINVAL;
+            }
+    if (state && (!ring || R < 1 || (((uintptr_t)state | (uintptr_t)ring) & 7) != 0)) {
+        x3dstep_set_error("%s: a state without a ring, an unaligned state or ring, or R %d < 1", who, R);
+        return X3DSTEP_EINVAL;
+    }
+    if (!x3ds::adam_args_ok(b1, b2, eps, decoupled)) {
+        x3dstep_set_error("%s: b1 %g or b2 %g outside [0, 1), eps %g negative or not finite, or decoupled %d outside {0, 1}", who,
+                          (double)b1, (double)b2, (double)eps, decoupled);
+        return X3DSTEP_EINVAL;
+    }
+    if (!state && count < 1) {
+        x3dstep_set_error("%s: without a state the count %lld is the number of this update: it must be >= 1", who,
+                          (long long)count);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+int x3dstep_check_lamb_moments(const char* who, const float* w, const float* g, const float* m, const float* v, int64_t n,
+                               const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper, int S,
+                               const int64_t* state, const void* ring, int R, int64_t count, float b1, float b2, float eps,
+                               const void* workspace) {
+    const int rc = x3dstep_check_adam(who, w, g, m, v, true, n, items, nitems, hyper, S, state, ring, R, count, b1, b2, eps, 1);
+    if (rc) return rc;
+    if (!workspace || ((uintptr_t)workspace & 7) != 0) {
+        x3dstep_set_error("%s: a null or unaligned workspace", who);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+int x3dstep_check_lamb_trust(const char* who, const int32_t* seg_item, int64_t nitems, const X3DStepHyper* hyper,
+                             const uint8_t* adapt, int S, const int64_t* state, const void* ring, int R, int64_t count,
+                             const void* workspace, const double* wsumsq, const double* rsumsq, const float* trust) {
+    if (!seg_item || !hyper || !adapt || !workspace || !wsumsq || !rsumsq || !trust || S < 1 || S > X3DSTEP_MAX_SEGMENTS ||
+        nitems < S || nitems > X3DSTEP_MAX_ITEMS || (((uintptr_t)seg_item | (uintptr_t)hyper | (uintptr_t)trust) & 3) != 0 ||
+        (((uintptr_t)workspace | (uintptr_t)wsumsq | (uintptr_t)rsumsq) & 7) != 0 || wsumsq == rsumsq) {
+        x3dstep_set_error("%s: null, unaligned or repeated pointer, S %d outside 1 .. %d or nitems %lld outside S .. %d", who, S,
+                          X3DSTEP_MAX_SEGMENTS, (long long)nitems, X3DSTEP_MAX_ITEMS);
+        return X3DSTEP_EINVAL;
+    }
+    if (state && (!ring || R < 1 || (((uintptr_t)state | (uintptr_t)ring) & 7) != 0)) {
+        x3dstep_set_error("%s: a state without a ring, an unaligned state or ring, or R %d < 1", who, R);
+        return X3DSTEP_EINVAL;
+    }
+    if (!state && count < 1) {
+        x3dstep_set_error("%s: without a state the count %lld is the number of this update: it must be >= 1", who,
+                          (long long)count);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+int x3dstep_check_lamb_apply(const char* who, const float* w, const float* m, const float* v, int64_t n,
+                             const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper, const float* trust, int S,
+                             const int64_t* state, const void* ring, int R, int64_t count, float b1, float b2, float eps) {
+    const int rc = x3dstep_check_adam(who, w, nullptr, m, v, false, n, items, nitems, hyper, S, state, ring, R, count, b1, b2, eps,
+                                      1);
+    if (rc) return rc;
+    if (!trust || ((uintptr_t)trust & 3) != 0) {
+        x3dstep_set_error("%s: a null or unaligned trust table", who);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+// What the twins of these updates refuse where the kernels leave out or leave at once (the tables and the state are host
+// memory here): a scale or a trust that is negative or not finite, an item table that is not the in-order tiling, a
+// counter of 0 and k < 1.
+static int adam_host_ok(const char* who, const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper,
+                        const float* trust, int S, int64_t n, const int64_t* state, const void* ring, int R, int64_t count) {
+    using namespace x3ds;
+    for (int s = 0; s < S; ++s) {
+        if (!group_scale_ok(hyper[s].lr_scale) || !group_scale_ok(hyper[s].wd_scale)) {
+            x3dstep_set_error("%s: tensor %d: a scale that is negative or not finite (lr_scale %g, wd_scale %g)", who, s,
+                              (double)hyper[s].lr_scale, (double)hyper[s].wd_scale);
+            return X3DSTEP_EINVAL;
+        }
+        if (trust && !group_scale_ok(trust[s])) {
+            x3dstep_set_error("%s: tensor %d: a trust ratio that is negative or not finite (%g)", who, s, (double)trust[s]);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    if (items) {
+        const int rt = tiling_host_ok(who, items, nitems, S, n);
+        if (rt) return rt;
+    }
+    if (state && !apply_decision(state, ring, R, S).go) {
+        x3dstep_set_error("%s: the state's step counter is 0: nothing has been measured", who);
+        return X3DSTEP_EINVAL;
+    }
+    const int64_t k = ema_count(state, count);
+    if (k < 1) {
+        x3dstep_set_error("%s: the number of this update among the applied ones is %lld: it must be >= 1", who, (long long)k);
+        return X3DSTEP_EINVAL;
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_adam_host(float* w, const float* g, float* m, float* v, int64_t n, const X3DStepItem* items,
+                                 int64_t nitems, const X3DStepHyper* hyper, int S, int64_t* state, const void* ring, int R,
+                                 int64_t count, float lr, float b1, float b2, float eps, float weight_decay, float grad_scale,
+                                 int decoupled) {
+    using namespace x3ds;
+    const char* who = "x3dstep_adam_host";
+    int rc = x3dstep_check_adam(who, w, g, m, v, true, n, items, nitems, hyper, S, state, ring, R, count, b1, b2, eps, decoupled);
+    if (!rc) rc = adam_host_ok(who, items, nitems, hyper, nullptr, S, n, state, ring, R, count);
+    if (rc) return rc;
+    float coef;
+    int64_t k;
+    if (!adam_begin(state, ring, R, S, count, true, &coef, &k)) return X3DSTEP_OK;
+    const AdamArgs a = {lr, b1, b2, eps, weight_decay, grad_scale, decoupled};
+    const SgdArgs sa = {a.lr, 0.0f, a.wd, a.gs, 0, 0};
+    const AdamCorr corr = adam_corr(k, b1, b2);
+    float* const base[4] = {w, (float*)g, m, v};
+    for (int64_t i = 0; i < nitems; ++i) {
+        const GroupItem c = group_resolve(items, i, hyper, S, n, sa);
+        if (c.len < 1) continue;
+        const AdamRule rule = {a, corr, coef, c.wd_s, adam_step_size(c.lr_s, corr), c.lr_s * c.wd_s};
+        for (int l = 0; l < kLanes; ++l) rule_lane(rule, base, c.start, c.len, l);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_lamb_moments_host(const float* w, const float* g, float* m, float* v, int64_t n, const X3DStepItem* items,
+                                         int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state,
+                                         const void* ring, int R, int64_t count, float b1, float b2, float eps,
+                                         float weight_decay, float grad_scale, void* workspace) {
+    using namespace x3ds;
+    const char* who = "x3dstep_lamb_moments_host";
+    int rc = x3dstep_check_lamb_moments(who, w, g, m, v, n, items, nitems, hyper, S, state, ring, R, count, b1, b2, eps, workspace);
+    if (!rc) rc = adam_host_ok(who, items, nitems, hyper, nullptr, S, n, state, ring, R, count);
+    if (rc) return rc;
+    float coef;
+    int64_t k;
+    if (!adam_begin((int64_t*)state, ring, R, S, count, false, &coef, &k)) return X3DSTEP_OK;
+    const AdamArgs a = {0.0f, b1, b2, eps, weight_decay, grad_scale, 1};
+    const SgdArgs sa = {0.0f, 0.0f, a.wd, a.gs, 0, 0};
+    const LambMomentsRule rule = {a, adam_corr(k, b1, b2), coef};
+    const bool vec = (((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    double* rpart = (double*)workspace;
+    double* wpart = rpart + nitems;
+    float* const base[3] = {(float*)g, m, v};
+    for (int64_t i = 0; i < nitems; ++i) {
+        const GroupItem c = group_resolve(items, i, hyper, S, n, sa);
+        LambSums lanes[kLanes];
+        for (int l = 0; l < kLanes; ++l) {
+            const LambSums bad = {trust_nan(), trust_nan()};
+            lanes[l] = c.len > 0 ? lamb_lane_sums(w, g, m, v, c, l, vec, rule) : bad;
+        }
+        for (int off = kLanes / 2; off > 0; off >>= 1)
+            for (int l = 0; l < off; ++l) {
+                lanes[l].r = lanes[l].r + lanes[l + off].r;
+                lanes[l].w = lanes[l].w + lanes[l + off].w;
+            }
+        rpart[i] = lanes[0].r;
+        wpart[i] = lanes[0].w;
+        if (c.len < 1) continue;
+        for (int l = 0; l < kLanes; ++l) rule_lane(rule, base, c.start, c.len, l);
+    }
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_lamb_trust_host(const int32_t* seg_item, int64_t nitems, const X3DStepHyper* hyper, const uint8_t* adapt,
+                                       int S, const int64_t* state, const void* ring, int R, int64_t count,
+                                       const void* workspace, double* wsumsq, double* rsumsq, float* trust) {
+    using namespace x3ds;
+    const char* who = "x3dstep_lamb_trust_host";
+    int rc = x3dstep_check_lamb_trust(who, seg_item, nitems, hyper, adapt, S, state, ring, R, count, workspace, wsumsq, rsumsq,
+                                      trust);
+    if (rc) return rc;
+    for (int s = 0; s < S; ++s) {
+        const int a = seg_item[s], b = seg_item[s + 1];
+        if (!(lamb_tensor_ok(hyper[s], a, b, nitems) && (s > 0 || a == 0) && (s + 1 < S || b == nitems))) {
+            x3dstep_set_error("%s: tensor %d: a scale (%g, %g) negative or not finite, or items %d .. %d are not a range of the "
+                              "table", who, s, (double)hyper[s].lr_scale, (double)hyper[s].wd_scale, a, b);
+            return X3DSTEP_EINVAL;
+        }
+    }
+    rc = adam_host_ok(who, nullptr, nitems, hyper, nullptr, S, 0, state, ring, R, count);
+    if (rc) return rc;
+    float coef;
+    int64_t k;
+    if (!adam_begin((int64_t*)state, ring, R, S, count, false, &coef, &k)) return X3DSTEP_OK;
+    const int32_t* nf = state ? record_at((void*)ring, R, S, state[X3DSTEP_S_STEP] - 1).nf : nullptr;
+    const double* rpart = (const double*)workspace;
+    const SumsqSource rsrc = {rpart, rpart, 0};
+    const SumsqSource wsrc = {rpart + nitems, rpart + nitems, 0};
+    for (int s = 0; s < S; ++s) lamb_tensor(rsrc, wsrc, s, seg_item, nitems, hyper, adapt, nf, wsumsq, rsumsq, trust);
+    return X3DSTEP_OK;
+}
+
+extern "C" int x3dstep_lamb_apply_host(float* w, const float* m, const float* v, int64_t n, const X3DStepItem* items,
+                                       int64_t nitems, const X3DStepHyper* hyper, const float* trust, int S, int64_t* state,
+                                       const void* ring, int R, int64_t count, float lr, float b1, float b2, float eps,
+                                       float weight_decay) {
+    using namespace x3ds;
+    const char* who = "x3dstep_lamb_apply_host";
+    int rc = x3dstep_check_lamb_apply(who, w, m, v, n, items, nitems, hyper, trust, S, state, ring, R, count, b1, b2, eps);
+    if (!rc) rc = adam_host_ok(who, items, nitems, hyper, trust, S, n, state, ring, R, count);
+    if (rc) return rc;
+    float coef;
+    int64_t k;
+    if (!adam_begin(state, ring, R, S, count, true, &coef, &k)) return X3DSTEP_OK;
+    const AdamArgs a = {lr, b1, b2, eps, weight_decay, 1.0f, 1};
+    const SgdArgs sa = {a.lr, 0.0f, a.wd, a.gs, 0, 0};
+    const AdamCorr corr = adam_corr(k, b1, b2);
+    float* const base[3] = {w, (float*)m, (float*)v};
+    for (int64_t i = 0; i < nitems; ++i) {
+        float t = 1.0f;
+        const GroupItem c = lars_resolve(items, i, hyper, trust, S, n, sa, &t);
+        if (c.len < 1) continue;
+        const LambApplyRule rule = {a, corr, c.wd_s, c.lr_s * t};
+        for (int l = 0; l < kLanes; ++l) rule_lane(rule, base, c.start, c.len, l);
+    }
+    return X3DSTEP_OK;
+}
+
 extern "C" int x3dstep_keep_host(const X3DStepKeep* table, int nbuf, const X3DStepItem* items, int64_t nitems, float* snap,
                                  int64_t snap_n, const int64_t* state, int mode) {
     using namespace x3ds;

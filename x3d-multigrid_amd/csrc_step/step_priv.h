@@ -24,6 +24,21 @@ int x3dstep_check_trust(const char* who, const float* w, int64_t n, const X3DSte
                         int64_t nitems, const X3DStepHyper* hyper, const float* eta, int S, const int64_t* state,
                         const void* ring, int R, const void* workspace, const double* wsumsq, const float* trust, float eps,
                         int clip);
+// The second-moment updates: the pointer, size and table checks of x3dstep_check_groups over w, g (need_g: x3dstep_lamb_apply
+// has none), m and v, then b1, b2, eps, decoupled and, without a state, the count
+int x3dstep_check_adam(const char* who, const float* w, const float* g, const float* m, const float* v, bool need_g, int64_t n,
+                       const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper, int S, const int64_t* state,
+                       const void* ring, int R, int64_t count, float b1, float b2, float eps, int decoupled);
+int x3dstep_check_lamb_moments(const char* who, const float* w, const float* g, const float* m, const float* v, int64_t n,
+                               const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper, int S,
+                               const int64_t* state, const void* ring, int R, int64_t count, float b1, float b2, float eps,
+                               const void* workspace);
+int x3dstep_check_lamb_trust(const char* who, const int32_t* seg_item, int64_t nitems, const X3DStepHyper* hyper,
+                             const uint8_t* adapt, int S, const int64_t* state, const void* ring, int R, int64_t count,
+                             const void* workspace, const double* wsumsq, const double* rsumsq, const float* trust);
+int x3dstep_check_lamb_apply(const char* who, const float* w, const float* m, const float* v, int64_t n,
+                             const X3DStepItem* items, int64_t nitems, const X3DStepHyper* hyper, const float* trust, int S,
+                             const int64_t* state, const void* ring, int R, int64_t count, float b1, float b2, float eps);
 int x3dstep_check_ema(const char* who, const float* e, const float* w, int64_t n, const int64_t* state, float decay);
 int x3dstep_check_swap(const char* who, const float* a, const float* b, int64_t n);
 // need_state: x3dstep_keep, which reads the state whatever the mode; the others pass X3DSTEP_KEEP_SAVE, x3dstep_swap_keep

@@ -41,7 +41,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
         skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
-        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8):
+        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8, optimizer_name='sgd', betas=(0.9, 0.999),
+        adam_eps=1e-8):
     """The reference's run() (train_x3d_charades.py:53-215) over a charades.Charades dataset.  videos: {id: uint8 CUDA
     tensor [n, H, W, 3] or frames.StoredVideo}; None: synthetic videos of round(24 * duration) frames of video_hw noise for
     every video of the annotation file, on `device` (default cuda:0).  device: where the run takes place; it must be the
@@ -60,7 +61,7 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
                               ema_warmup=ema_warmup, precise_bn=precise_bn, wd_exempt_1d=wd_exempt_1d,
                               head_lr_scale=head_lr_scale, nesterov=nesterov, lars=lars, lars_clip=lars_clip,
-                              lars_eps=lars_eps)
+                              lars_eps=lars_eps, optimizer_name=optimizer_name, betas=betas, adam_eps=adam_eps)
 
 
 def init_distributed():
@@ -139,6 +140,12 @@ def main(run_fn, default_save):
                              '+ eps), parameters with ndim <= 1 exempt; bare: eta 0.001 (off by default)')
     parser.add_argument('--lars-clip', action='store_true', help='with --lars: min(ratio / lr, 1) (LARC clipping mode)')
     parser.add_argument('--lars-eps', type=float, default=1e-8, metavar='X', help='with --lars: eps of the ratio (default 1e-8)')
+    parser.add_argument('--optimizer', choices=('sgd', 'adamw', 'adam', 'lamb'), default='sgd',
+                        help='the update rule on the GPU: SGD with momentum (default), AdamW, Adam with L2, or LAMB')
+    parser.add_argument('--betas', type=float, nargs=2, default=(0.9, 0.999), metavar=('B1', 'B2'),
+                        help='with an adaptive --optimizer: the decay rates of the two moments (default 0.9 0.999)')
+    parser.add_argument('--adam-eps', type=float, default=1e-8, metavar='X',
+                        help='with an adaptive --optimizer: eps of the denominator (default 1e-8)')
     args = parser.parse_args()
     if args.gpu is not None:
         os.environ["CUDA_VISIBLE_DEVICES"] = args.gpu
@@ -158,7 +165,8 @@ def main(run_fn, default_save):
                skip_nonfinite=args.skip_nonfinite, max_skip_run=args.max_skip_run, ema_decay=args.ema_decay,
                ema_warmup=not args.no_ema_warmup, precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d,
                head_lr_scale=args.head_lr_scale, nesterov=args.nesterov, lars=args.lars, lars_clip=args.lars_clip,
-               lars_eps=args.lars_eps, **size)
+               lars_eps=args.lars_eps, optimizer_name=args.optimizer, betas=tuple(args.betas), adam_eps=args.adam_eps,
+               **size)
     finally:
         if pg is not None:
             import torch.distributed as dist

@@ -33,7 +33,8 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
         num_steps_per_update=1, crop_size=None, c_size=224, dropout=0.5, seed=0, device=None, video_hw=(36, 48),
         process_group=None, rank=0, world=1, base_bn_splits=1, clip_grad_norm=None, monitor=False,
         skip_nonfinite=False, max_skip_run=8, ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False,
-        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8):
+        head_lr_scale=1.0, nesterov=False, lars=None, lars_clip=False, lars_eps=1e-8, optimizer_name='sgd', betas=(0.9, 0.999),
+        adam_eps=1e-8):
     """The reference's run() (train_x3d_charades_loc.py:54-221) over a charades.Charades dataset with task='loc'.
     Arguments as train_x3d_charades.run."""
     if not isinstance(anno, dict):
@@ -49,7 +50,7 @@ def run(init_lr=INIT_LR, max_epochs=100, anno=CHARADES_ANNO, batch_size=BS * BS_
                               skip_nonfinite=skip_nonfinite, max_skip_run=max_skip_run, ema_decay=ema_decay,
                               ema_warmup=ema_warmup, precise_bn=precise_bn, wd_exempt_1d=wd_exempt_1d,
                               head_lr_scale=head_lr_scale, nesterov=nesterov, lars=lars, lars_clip=lars_clip,
-                              lars_eps=lars_eps)
+                              lars_eps=lars_eps, optimizer_name=optimizer_name, betas=betas, adam_eps=adam_eps)
 
 
 if __name__ == '__main__':

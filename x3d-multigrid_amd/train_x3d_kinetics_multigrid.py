@@ -212,8 +212,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         val_batch_size=2, val_crops=3, num_steps_per_update=1, clip_size=None, act_dtype=torch.float32,
         frames_root=None, val_frames=None, clip_grad_norm=None, monitor=False, skip_nonfinite=False, max_skip_run=8,
         ema_decay=None, ema_warmup=True, precise_bn=None, wd_exempt_1d=False, head_lr_scale=1.0, nesterov=False,
-        lars=None, lars_clip=False, lars_eps=1e-8, mixup=0.0, cutmix=0.0, mix_prob=None, mix_switch_prob=None,
-        label_smoothing=0.0):
+        lars=None, lars_clip=False, lars_eps=1e-8, optimizer_name='sgd', betas=(0.9, 0.999), adam_eps=1e-8,
+        mixup=0.0, cutmix=0.0, mix_prob=None, mix_switch_prob=None, label_smoothing=0.0):
     """The reference's training loop (train_x3d_kinetics_multigrid.py:157-292) on synthetic clips, or on folders of JPEG
     frames: frames_root is a dict(root=, anno=, labels=[, subset='train', threads=8, entropy='host']) for
     frames.FolderKinetics.from_annotation, or a ready frames.FolderKinetics (its own crop size then sets the clip
@@ -253,6 +253,10 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     exempt; lars_clip: min(ratio / lr, 1).  It implies the monitor and the hyper table, so their lines and fields appear
     too; rank 0 prints one more line before training (tensors adapted and exempt, eta, eps, clip), the log line gains
     `trust MIN/MEDIAN/MAX` over the adapted tensors, and the optimizer's state in a checkpoint gains 'lars'.
+    optimizer_name / betas / adam_eps: Trainer(optimizer=, betas=, adam_eps=) -- 'adamw', 'adam' or 'lamb' in the place of SGD
+    on the same flat buffers (x3dhip/adamw.py).  Rank 0 prints one more line before training (the optimizer, betas, eps, the
+    tensors exempt from decay and, for lamb, from adaptation), with lamb the log line gains `trust MIN/MEDIAN/MAX`, and the
+    optimizer's state in a checkpoint takes torch.optim.AdamW's layout with a top-level 'optimizer'.
     mixup / cutmix / mix_prob / mix_switch_prob / label_smoothing: any of them (an alpha or a smoothing above 0, or one of the
     probabilities given) trains with Trainer(objective="soft_ce") and puts a mixing.BatchMixer, seeded 1234 + rank, between
     every batch (synthetic or from frames) and train_step: the clips are mixed by one launch, straight into the graph's
@@ -260,6 +264,7 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
     log line's acc stays against each sample's own hard label.  The mixer's generator is not in a checkpoint: a resumed run
     restarts it from its seed.  With none of them the lines, the checkpoint keys and the bits are as before."""
     from x3dhip import hypergroups
+    from x3dhip import adamw as adammod
     from x3dhip import lars as larsmod
     from x3dhip.trainer import Trainer
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -312,6 +317,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                         monitor=monitor, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
                         tensor_hyper=hypergroups.recipe(model, wd_exempt_1d, head_lr_scale) or None, nesterov=nesterov,
                         lars=None if lars is None else dict(eta=lars, clip=lars_clip, eps=lars_eps),
+                        **(dict(optimizer=optimizer_name, betas=tuple(betas), adam_eps=adam_eps)
+                           if optimizer_name != 'sgd' else {}),
                         **(dict(objective="soft_ce") if mixing_on(mixup, cutmix, mix_prob, mix_switch_prob, label_smoothing)
                            else {}))
     mixer = None
@@ -327,6 +334,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
         print(hypergroups.describe(optimizer))
     if rank == 0 and lars is not None:
         print(larsmod.describe(optimizer))
+    if rank == 0 and optimizer_name != 'sgd':
+        print(adammod.describe(optimizer, model))
     mon = getattr(optimizer, 'monitor', None)
     ema = getattr(optimizer, 'ema', None)
     lr_sched = MultiStepLR(optimizer, lr_schedule)
@@ -465,6 +474,8 @@ def run(init_lr=INIT_LR, warmup_steps=8000, max_epochs=120, batch_size=BS * BS_U
                     gline += ' skipped {}'.format(mon.skip_report(max_skip_run))
                 if lars is not None:
                     gline += ' ' + larsmod.log_field(optimizer)
+                if optimizer_name == 'lamb':
+                    gline += ' ' + adammod.log_field(optimizer)
                 if rank == 0:
                     dt = time.time() - t0
                     print(' step {} long {} shape ({},{},{}) loss {:.4f} acc {:.3f} lr {:.5f}  {:.1f} clips/s{}'.format(
@@ -598,6 +609,12 @@ if __name__ == '__main__':
                              '+ eps), parameters with ndim <= 1 exempt; bare: eta 0.001 (off by default)')
     parser.add_argument('--lars-clip', action='store_true', help='with --lars: min(ratio / lr, 1) (LARC clipping mode)')
     parser.add_argument('--lars-eps', type=float, default=1e-8, metavar='X', help='with --lars: eps of the ratio (default 1e-8)')
+    parser.add_argument('--optimizer', choices=('sgd', 'adamw', 'adam', 'lamb'), default='sgd',
+                        help='the update rule on the GPU: SGD with momentum (default), AdamW, Adam with L2, or LAMB')
+    parser.add_argument('--betas', type=float, nargs=2, default=(0.9, 0.999), metavar=('B1', 'B2'),
+                        help='with an adaptive --optimizer: the decay rates of the two moments (default 0.9 0.999)')
+    parser.add_argument('--adam-eps', type=float, default=1e-8, metavar='X',
+                        help='with an adaptive --optimizer: eps of the denominator (default 1e-8)')
     parser.add_argument('--mixup', type=float, default=0.0, metavar='A',
                         help='mixup with lam ~ Beta(A, A) on the GPU (0: off); trains against soft targets')
     parser.add_argument('--cutmix', type=float, default=0.0, metavar='A',
@@ -639,5 +656,6 @@ if __name__ == '__main__':
         max_skip_run=args.max_skip_run, ema_decay=args.ema_decay, ema_warmup=not args.no_ema_warmup,
         precise_bn=args.precise_bn, wd_exempt_1d=args.wd_exempt_1d, head_lr_scale=args.head_lr_scale,
         nesterov=args.nesterov, lars=args.lars, lars_clip=args.lars_clip, lars_eps=args.lars_eps,
+        optimizer_name=args.optimizer, betas=tuple(args.betas), adam_eps=args.adam_eps,
         mixup=args.mixup, cutmix=args.cutmix, mix_prob=args.mix_prob, mix_switch_prob=args.mix_switch_prob,
         label_smoothing=args.label_smoothing)

@@ -68,6 +68,15 @@ SIGNATURES = {
     "x3dstep_trust_host": (_I, [_P, _L, _P, _P, _L, _P, _P, _I, _P, _P, _I, _P, _P, _P, _F, _F, _F, _F, _I]),
     "x3dstep_apply_lars": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I, _P]),
     "x3dstep_apply_lars_host": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _F, _F, _F, _F, _I, _I]),
+    "x3dstep_lamb_workspace_bytes": (_Z, [_L]),
+    "x3dstep_adam": (_I, [_P, _P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _L, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "x3dstep_adam_host": (_I, [_P, _P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _L, _F, _F, _F, _F, _F, _F, _I]),
+    "x3dstep_lamb_moments": (_I, [_P, _P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _L, _F, _F, _F, _F, _F, _P, _P]),
+    "x3dstep_lamb_moments_host": (_I, [_P, _P, _P, _P, _L, _P, _L, _P, _I, _P, _P, _I, _L, _F, _F, _F, _F, _F, _P]),
+    "x3dstep_lamb_trust": (_I, [_P, _L, _P, _P, _I, _P, _P, _I, _L, _P, _P, _P, _P, _P]),
+    "x3dstep_lamb_trust_host": (_I, [_P, _L, _P, _P, _I, _P, _P, _I, _L, _P, _P, _P, _P]),
+    "x3dstep_lamb_apply": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _L, _F, _F, _F, _F, _F, _P]),
+    "x3dstep_lamb_apply_host": (_I, [_P, _P, _P, _L, _P, _L, _P, _P, _I, _P, _P, _I, _L, _F, _F, _F, _F, _F]),
     "x3dstep_keep": (_I, [_P, _I, _P, _L, _P, _L, _P, _I, _P]),
     "x3dstep_keep_host": (_I, [_P, _I, _P, _L, _P, _L, _P, _I]),
     "x3dstep_ema": (_I, [_P, _P, _L, _P, _L, _F, _I, _P]),

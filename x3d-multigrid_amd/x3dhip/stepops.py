@@ -381,6 +381,182 @@ def apply_lars_host(w, g, m, tables, hyper, trust_in, state, ring, R, lr, moment
                                                  nesterov))
 
 
+def lamb_workspace_bytes(nitems):
+    b = _steplib.lib().x3dstep_lamb_workspace_bytes(int(nitems))
+    if b == 0:
+        raise ValueError("lamb_workspace_bytes: %d items outside 1 .. %d" % (nitems, _steplib.MAX_ITEMS))
+    return int(b)
+
+
+def _adam_args(who, betas, eps, decoupled=1):
+    b1, b2 = (float(b) for b in betas)
+    eps = float(eps)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError("%s: betas must lie in [0, 1) (got %r)" % (who, (b1, b2)))
+    if not (np.isfinite(eps) and eps >= 0.0) or decoupled not in (0, 1, False, True):
+        raise ValueError("%s: eps must be finite and >= 0 and decoupled 0 or 1 (got %r, %r)" % (who, eps, decoupled))
+    return b1, b2, eps, int(decoupled)
+
+
+def _state_args(state, ring, R):
+    """(state, ring, R) as the C ABI takes them from torch tensors: nulls and 0 for the unguarded form."""
+    if state is None:
+        return None, None, 0
+    return ptr(state), ptr(ring), int(R)
+
+
+def _state_args_np(state, ring, R):
+    if state is None:
+        return None, None, 0
+    return _np_ptr(state), _np_ptr(ring), int(R)
+
+
+def _need_bytes(who, name, t, need, dev):
+    if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous()
+            or t.numel() < need):
+        raise ValueError("%s: %s must be a contiguous uint8 tensor of at least %d bytes on %s" % (who, name, need, dev))
+
+
+def _need_bytes_np(who, name, a, need):
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or not a.flags.c_contiguous or a.size < need:
+        raise ValueError("%s: %s must be a contiguous uint8 array of at least %d bytes" % (who, name, need))
+
+
+def adam(w, g, m, v, tables, hyper, state, ring, R, count, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+         grad_scale=1.0, decoupled=True):
+    """Adam (decoupled=False: weight decay as an L2 term of the gradient) or AdamW (decoupled=True), one launch on the
+    current stream: torch.optim.Adam / AdamW's single-tensor arithmetic with tensor s at the rate lr * hyper[s, 0] and the
+    decay weight_decay * hyper[s, 1] (include/x3dstep.h).  m: exp_avg, v: exp_avg_sq, float32 [n] like w and g.  state: the
+    monitor's int64 [STATE_WORDS] after `measure` on the same state and ring (the guarded form: the clipping coefficient
+    is applied, a non-finite step stores nothing and is counted), or None.  The bias correction is that of update
+    k = count + (state: the updates applied so far, this one included); without a state count is k itself."""
+    dev = _on_gpu("adam", tables.device)
+    for name, t in (("w", w), ("g", g), ("m", m), ("v", v)):
+        _need_flat("adam", name, t, tables.n, dev)
+    _need_hyper("adam", hyper, tables.S, dev)
+    if state is not None:
+        _check_device("adam", g, tables, None, state, ring, int(R))
+    b1, b2, eps, decoupled = _adam_args("adam", betas, eps, decoupled)
+    check(_steplib.lib().x3dstep_adam(ptr(w), ptr(g), ptr(m), ptr(v), tables.n, ptr(tables.d_items), tables.nitems,
+                                      ptr(hyper), tables.S, *_state_args(state, ring, R), int(count), float(lr), b1, b2, eps,
+                                      float(weight_decay), float(grad_scale), decoupled, stream()))
+
+
+def adam_host(w, g, m, v, tables, hyper, state, ring, R, count, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              grad_scale=1.0, decoupled=True):
+    """The CPU twin of `adam` on numpy arrays (w, m and v are updated in place).  The scalars go to the library as they
+    are: it is the twin that refuses them."""
+    for name, a, wr in (("w", w, True), ("g", g, False), ("m", m, True), ("v", v, True)):
+        _need_flat_np("adam_host", name, a, tables.n, wr)
+    _need_hyper_np("adam_host", hyper, tables.S)
+    if state is not None:
+        _check_host("adam_host", g, tables, None, state, ring, int(R), writeable=False)
+    check(_steplib.lib().x3dstep_adam_host(_np_ptr(w), _np_ptr(g), _np_ptr(m), _np_ptr(v), tables.n, _np_ptr(tables.items),
+                                           tables.nitems, _np_ptr(hyper), tables.S, *_state_args_np(state, ring, R),
+                                           int(count), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                           float(weight_decay), float(grad_scale), int(decoupled)))
+
+
+def lamb_moments(w, g, m, v, tables, hyper, state, ring, R, count, workspace, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0,
+                 grad_scale=1.0):
+    """Launch 1 of LAMB on the current stream: the new moments into m and v and, per item, the fp64 sums of squares of the
+    direction r and of w into workspace (uint8, lamb_workspace_bytes(nitems)).  w and g are only read."""
+    dev = _on_gpu("lamb_moments", tables.device)
+    for name, t in (("w", w), ("g", g), ("m", m), ("v", v)):
+        _need_flat("lamb_moments", name, t, tables.n, dev)
+    _need_hyper("lamb_moments", hyper, tables.S, dev)
+    _need_bytes("lamb_moments", "workspace", workspace, lamb_workspace_bytes(tables.nitems), dev)
+    if state is not None:
+        _check_device("lamb_moments", g, tables, None, state, ring, int(R))
+    b1, b2, eps, _ = _adam_args("lamb_moments", betas, eps)
+    check(_steplib.lib().x3dstep_lamb_moments(ptr(w), ptr(g), ptr(m), ptr(v), tables.n, ptr(tables.d_items), tables.nitems,
+                                              ptr(hyper), tables.S, *_state_args(state, ring, R), int(count), b1, b2, eps,
+                                              float(weight_decay), float(grad_scale), ptr(workspace), stream()))
+
+
+def lamb_moments_host(w, g, m, v, tables, hyper, state, ring, R, count, workspace, betas=(0.9, 0.999), eps=1e-6,
+                      weight_decay=0.0, grad_scale=1.0):
+    """The CPU twin of `lamb_moments` on numpy arrays (m, v and the workspace are written)."""
+    for name, a, wr in (("w", w, False), ("g", g, False), ("m", m, True), ("v", v, True)):
+        _need_flat_np("lamb_moments_host", name, a, tables.n, wr)
+    _need_hyper_np("lamb_moments_host", hyper, tables.S)
+    _need_bytes_np("lamb_moments_host", "workspace", workspace, lamb_workspace_bytes(tables.nitems))
+    if state is not None:
+        _check_host("lamb_moments_host", g, tables, None, state, ring, int(R), writeable=False)
+    check(_steplib.lib().x3dstep_lamb_moments_host(_np_ptr(w), _np_ptr(g), _np_ptr(m), _np_ptr(v), tables.n,
+                                                   _np_ptr(tables.items), tables.nitems, _np_ptr(hyper), tables.S,
+                                                   *_state_args_np(state, ring, R), int(count), float(betas[0]),
+                                                   float(betas[1]), float(eps), float(weight_decay), float(grad_scale),
+                                                   _np_ptr(workspace)))
+
+
+def lamb_trust(tables, hyper, adapt, state, ring, R, count, workspace, wsumsq, rsumsq, trust_out):
+    """Launch 2 of LAMB: per tensor wsumsq[s] and rsumsq[s] (float64 [S]: the sums of squares of the weights and of the
+    direction, as `measure` would record them) and trust_out[s] (float32 [S]) = |w_s| / |r_s|; exactly 1 where adapt[s]
+    (uint8 [S]) is 0, a norm is 0 or the gradient was not finite."""
+    dev = _on_gpu("lamb_trust", tables.device)
+    _need_hyper("lamb_trust", hyper, tables.S, dev)
+    _need_vec("lamb_trust", "adapt", adapt, torch.uint8, tables.S, dev)
+    _need_vec("lamb_trust", "wsumsq", wsumsq, torch.float64, tables.S, dev)
+    _need_vec("lamb_trust", "rsumsq", rsumsq, torch.float64, tables.S, dev)
+    _need_vec("lamb_trust", "trust_out", trust_out, torch.float32, tables.S, dev)
+    _need_bytes("lamb_trust", "workspace", workspace, lamb_workspace_bytes(tables.nitems), dev)
+    if state is not None:
+        _need_state("lamb_trust", state, dev)
+        _need_bytes("lamb_trust", "ring", ring, int(R) * tables.record_bytes, dev)
+    check(_steplib.lib().x3dstep_lamb_trust(ptr(tables.d_seg_item), tables.nitems, ptr(hyper), ptr(adapt), tables.S,
+                                            *_state_args(state, ring, R), int(count), ptr(workspace), ptr(wsumsq),
+                                            ptr(rsumsq), ptr(trust_out), stream()))
+
+
+def lamb_trust_host(tables, hyper, adapt, state, ring, R, count, workspace, wsumsq, rsumsq, trust_out, seg_item=None):
+    """The CPU twin of `lamb_trust` on numpy arrays (seg_item: another table than the tables' own, for the tests)."""
+    _need_hyper_np("lamb_trust_host", hyper, tables.S)
+    _need_vec_np("lamb_trust_host", "adapt", adapt, np.uint8, tables.S)
+    _need_vec_np("lamb_trust_host", "wsumsq", wsumsq, np.float64, tables.S, True)
+    _need_vec_np("lamb_trust_host", "rsumsq", rsumsq, np.float64, tables.S, True)
+    _need_vec_np("lamb_trust_host", "trust_out", trust_out, np.float32, tables.S, True)
+    _need_bytes_np("lamb_trust_host", "workspace", workspace, lamb_workspace_bytes(tables.nitems))
+    if state is not None:
+        _state_ptr_np("lamb_trust_host", state)
+        _need_bytes_np("lamb_trust_host", "ring", ring, int(R) * tables.record_bytes)
+    si = tables.seg_item if seg_item is None else np.ascontiguousarray(seg_item, dtype=np.int32)
+    check(_steplib.lib().x3dstep_lamb_trust_host(_np_ptr(si), tables.nitems, _np_ptr(hyper), _np_ptr(adapt), tables.S,
+                                                 *_state_args_np(state, ring, R), int(count), _np_ptr(workspace),
+                                                 _np_ptr(wsumsq), _np_ptr(rsumsq), _np_ptr(trust_out)))
+
+
+def lamb_apply(w, m, v, tables, hyper, trust_in, state, ring, R, count, lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0):
+    """Launch 3 of LAMB: w <- w - (lr_s * trust_in[s]) * r with r recomputed from the stored moments; counts the skips
+    in the state as `apply` does.  m and v are only read."""
+    dev = _on_gpu("lamb_apply", tables.device)
+    for name, t in (("w", w), ("m", m), ("v", v)):
+        _need_flat("lamb_apply", name, t, tables.n, dev)
+    _need_hyper("lamb_apply", hyper, tables.S, dev)
+    _need_vec("lamb_apply", "trust_in", trust_in, torch.float32, tables.S, dev)
+    if state is not None:
+        _check_device("lamb_apply", w, tables, None, state, ring, int(R))
+    b1, b2, eps, _ = _adam_args("lamb_apply", betas, eps)
+    check(_steplib.lib().x3dstep_lamb_apply(ptr(w), ptr(m), ptr(v), tables.n, ptr(tables.d_items), tables.nitems, ptr(hyper),
+                                            ptr(trust_in), tables.S, *_state_args(state, ring, R), int(count), float(lr), b1,
+                                            b2, eps, float(weight_decay), stream()))
+
+
+def lamb_apply_host(w, m, v, tables, hyper, trust_in, state, ring, R, count, lr, betas=(0.9, 0.999), eps=1e-6,
+                    weight_decay=0.0):
+    """The CPU twin of `lamb_apply` on numpy arrays (w is updated in place)."""
+    for name, a, wr in (("w", w, True), ("m", m, False), ("v", v, False)):
+        _need_flat_np("lamb_apply_host", name, a, tables.n, wr)
+    _need_hyper_np("lamb_apply_host", hyper, tables.S)
+    _need_vec_np("lamb_apply_host", "trust_in", trust_in, np.float32, tables.S)
+    if state is not None:
+        _check_host("lamb_apply_host", w, tables, None, state, ring, int(R), writeable=False)
+    check(_steplib.lib().x3dstep_lamb_apply_host(_np_ptr(w), _np_ptr(m), _np_ptr(v), tables.n, _np_ptr(tables.items),
+                                                 tables.nitems, _np_ptr(hyper), _np_ptr(trust_in), tables.S,
+                                                 *_state_args_np(state, ring, R), int(count), float(lr), float(betas[0]),
+                                                 float(betas[1]), float(eps), float(weight_decay)))
+
+
 class KeepTable:
     """The table `keep` takes for a list of small float32 buffers: where each lies in the snapshot (every buffer starts on
     a multiple of four elements, so that a 16-byte aligned buffer is copied in 16-byte groups), the item table of the

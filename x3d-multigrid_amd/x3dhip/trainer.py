@@ -121,7 +121,8 @@ class Trainer:
     def __init__(self, model, lr, momentum=0.9, weight_decay=5e-5, process_group=None, world_size=1,
                  use_graph=False, num_steps_per_update=1, overlap=True, force_split=False, force_collectives=False,
                  objective="ce", clip_grad_norm=None, monitor=False, skip_nonfinite=False, ema_decay=None,
-                 ema_warmup=True, tensor_hyper=None, nesterov=False, lars=None):
+                 ema_warmup=True, tensor_hyper=None, nesterov=False, lars=None, optimizer="sgd", betas=(0.9, 0.999),
+                 adam_eps=1e-8, lamb=None):
         """overlap: multi-rank steps are captured as two graphs around the first gradient bucket (False: single graph,
         all-reduce after the whole backward); force_split: the two-graph form on a single rank too (tests);
         force_collectives: all-reduce on a one-rank process group (the single-GPU RCCL test).  Round 4: constructor
@@ -207,6 +208,25 @@ class Trainer:
         ({'names', 'eta', 'eps', 'clip'}), which load_state_dict restores.  None (the default): no attribute, not one
         launch, the same checkpoint keys.
 
+        optimizer / betas / adam_eps / lamb: optimizer = "sgd" (the default: everything above), "adamw" (decoupled weight
+        decay, torch.optim.AdamW), "adam" (weight decay as an L2 term, torch.optim.Adam) or "lamb" (You et al. 2020: the
+        AdamW direction scaled per tensor by |w| / |direction|).  Anything but "sgd" creates an adamw.AdamState
+        (`self.adam`), which holds the second-moment flat buffer (fp.mom is exp_avg), and implies a HyperTable as nesterov
+        does; the monitor is created only where clip_grad_norm, monitor or skip_nonfinite ask for one.  The update stays
+        one sequence: measure or observe, stepops.adam (one launch) or the three LAMB launches (moments and partial sums,
+        per-tensor sums and ratios, the step), the restore; with skip_nonfinite the update reads the state and the ring --
+        the clipping coefficient, the skip, and the count of applied updates for the bias correction, which a skipped update
+        does not advance -- without it the host counts the updates.  `momentum` is not used.  lamb: None or dict(
+        exempt_1d=True, exempt=()): every parameter with ndim <= 1 is exempt from the adaptation (a trust of exactly 1)
+        unless exempt_1d=False; `exempt` holds further fnmatch patterns (one that matches nothing raises).  nesterov=True or
+        lars= with an adaptive optimizer raises ValueError.  Same place as ever: after the all-reduce and `pre_step`, outside
+        every captured graph, on the updating call only under accumulation, grad_scale = 1 / world, no collective added.
+        state_dict() takes torch.optim.AdamW's layout: state[i] = {'step', 'exp_avg', 'exp_avg_sq'} ('step' is the count of
+        applied updates: reading it is the one host read, at checkpoint time only), param_groups[0] gains 'betas', 'eps' and
+        'amsgrad': False, a top-level 'optimizer' holds the name and, for lamb, 'lamb' the names and the adaptation flags;
+        load_state_dict restores the buffers and continues the count, and raises on a checkpoint of another optimizer.
+        "sgd": no attribute, no allocation, not one launch, the same checkpoint keys.
+
         The Trainer re-homes the model's parameters into flat buffers (FlatParams) when it is constructed: a fine-tune
         that swaps the classifier calls model.replace_logits(n) BEFORE constructing the Trainer -- a head replaced
         afterwards is not part of the flat buffers and would not be trained."""
@@ -246,7 +266,14 @@ class Trainer:
             ring = 64 if (monitor is True or not monitor) else int(monitor)
             self.monitor = GradMonitor(self.fp, [k for k, _ in model.named_parameters()], ring=ring,
                                        max_norm=clip_grad_norm, inv_world=1.0 / world_size)
-        if tensor_hyper is not None or nesterov or lars is not None:
+        if optimizer not in ("sgd", "adamw", "adam", "lamb"):
+            raise ValueError("optimizer must be one of 'sgd', 'adamw', 'adam', 'lamb' (got %r)" % (optimizer,))
+        adaptive = optimizer != "sgd"
+        if adaptive and (nesterov or lars is not None):
+            raise ValueError("nesterov and lars belong to SGD: optimizer %r takes neither" % (optimizer,))
+        if lamb is not None and optimizer != "lamb":
+            raise ValueError("lamb= needs optimizer='lamb' (got %r)" % (optimizer,))
+        if tensor_hyper is not None or nesterov or lars is not None or adaptive:
             from .hypergroups import HyperTable
             if nesterov and not float(momentum) > 0.0:
                 raise ValueError("nesterov needs momentum > 0 (got %r)" % (momentum,))
@@ -271,6 +298,23 @@ class Trainer:
             for pattern in cfg["exempt"]:
                 self.lars._set(pattern, 0.0)
             self.lars.upload()
+        if adaptive:
+            from .adamw import AdamState
+            named = list(model.named_parameters())
+            self.adam = AdamState(self.fp, [k for k, _ in named], self.hyper, monitor=getattr(self, "monitor", None),
+                                  mode=optimizer, betas=betas, eps=adam_eps, guarded=self.skip_nonfinite)
+            self.param_groups[0].update(betas=self.adam.betas, eps=self.adam.eps, amsgrad=False)
+            if optimizer == "lamb":
+                cfg = dict(exempt_1d=True, exempt=())
+                extra = set(lamb or {}) - set(cfg)
+                if extra:
+                    raise ValueError("lamb: unknown keys %s" % sorted(extra))
+                cfg.update(lamb or {})
+                if cfg["exempt_1d"]:
+                    self.adam.adapt[[i for i, (_, p) in enumerate(named) if p.dim() <= 1]] = 0
+                for pattern in cfg["exempt"]:
+                    self.adam.exempt(pattern)
+                self.adam.upload()
         if ema_decay is not None:
             from .weightema import WeightEMA
             self.ema = WeightEMA(self.fp, model, ema_decay, warmup=ema_warmup, monitor=getattr(self, "monitor", None))
@@ -413,6 +457,7 @@ class Trainer:
         mon = getattr(self, "monitor", None)
         hy = getattr(self, "hyper", None)
         la = getattr(self, "lars", None)
+        ad = getattr(self, "adam", None)
         g = self.param_groups[0]
         guarded = self.skip_nonfinite
         w, gr, m = self.fp.flat, self.fp.grad if grad is None else grad, self.fp.mom
@@ -423,7 +468,9 @@ class Trainer:
             mon.measure(grad)                # the decision and the coefficient stay on the device
         elif mon is not None:                # statistics (and clipping) of exactly what the update is about to apply
             mon.observe(grad)                # scales the gradient in place
-        if la is not None:                   # trust ratios: the weights' norms, the ratios, the update that takes them
+        if ad is not None:                   # Adam, AdamW or LAMB: both moments, the count from the state when guarded
+            ad.update(w, gr, m, g['lr'], g['weight_decay'], 1.0 / self.world)
+        elif la is not None:                 # trust ratios: the weights' norms, the ratios, the update that takes them
             la.compute(w, g['lr'], g['weight_decay'], 1.0 / self.world)
             stepops.apply_lars(w, gr, m, hy.tables, hy.hyper, la.trust, mon.state if guarded else None,
                                mon.ring if guarded else None, mon.R if guarded else 0, *arith, first=self.first,
@@ -647,7 +694,10 @@ class Trainer:
     # -- torch.optim.SGD-compatible state (reference checkpoints, train...:185-187,286-291) ---
     def state_dict(self):
         state = {}
-        if not self.first:
+        ad = getattr(self, "adam", None)
+        if ad is not None:
+            state = ad.state_entries()
+        elif not self.first:
             for i, (o, k) in enumerate(self.fp.offsets):
                 state[i] = {'momentum_buffer': self.fp.mom[o:o + k].view(self.fp.params[i].shape).clone()}
         sd = {'state': state, 'param_groups': [dict(self.param_groups[0])]}
@@ -657,9 +707,17 @@ class Trainer:
         la = getattr(self, "lars", None)
         if la is not None:
             sd['lars'] = la.state_dict()
+        if ad is not None:
+            sd['optimizer'] = ad.mode
+            if ad.mode == "lamb":
+                sd['lamb'] = ad.lamb_state_dict()
         return sd
 
     def load_state_dict(self, sd):
+        ad = getattr(self, "adam", None)
+        mine, theirs = "sgd" if ad is None else ad.mode, sd.get('optimizer', 'sgd')
+        if mine != theirs:
+            raise ValueError("load_state_dict: a checkpoint of optimizer %r into a trainer with optimizer %r" % (theirs, mine))
         g = sd['param_groups'][0]
         for k in ('lr', 'momentum', 'weight_decay'):
             if k in g:
@@ -671,6 +729,12 @@ class Trainer:
         if la is not None and sd.get('lars') is not None:
             la.load_state_dict(sd['lars'])
         st = sd.get('state', {})
+        if ad is not None:
+            if ad.mode == "lamb" and sd.get('lamb') is not None:
+                ad.load_lamb_state_dict(sd['lamb'])
+            ad.load_state_entries(st)
+            self.first = False
+            return
         if st:
             for i, (o, k) in enumerate(self.fp.offsets):
                 buf = st.get(i, st.get(str(i)))
